@@ -15,6 +15,9 @@ workload (N=1): the configuration BASELINE.json's metric is quoted on ("@100k co
                 rank r ingests the r-th contiguous chunk of the 500M-pair stream, the link tables are
                 merged with one exchange, and the MCL row blocks are all-gathered every iteration
                 (haphic_amd/sharded.py).
+plain run     : sets up, warms up, times --steps steps and prints the line (ms_per_step = wall time of one timed step);
+                --dump-outputs DIR also writes what the last step computed.  --full adds every leg after the timed
+                region: text tokeniser, inflation sweep, oracle parity, seam sequence, CPU baseline, run() end to end.
 """
 import argparse
 import json
@@ -29,6 +32,7 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s peak (6.3 TB/s achievable)
+DUMP_MAX_ENTRIES = 1 << 19  # --dump-outputs: at most 9 arrays of this many 8-byte entries, 36 MB in all
 
 
 def parse():
@@ -63,7 +67,15 @@ def parse():
                          'staged through host memory over gloo (haphic_amd.host_transport) — runs N ranks on ONE GPU, a functional proof of '
                          'the multi-rank path on a box without xGMI; its timings say nothing about scaling')
     ap.add_argument('--master-port', type=int, default=0, help='rendezvous port of the self-launch (0: pick a free one)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also run every leg beside the headline (text tokeniser, inflation '
+                    'sweep, oracle parity, seam sequence, CPU baseline, run() end to end; N > 1: the sharded sweep). Without it a run '
+                    'sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed (clusters, MCL result, link matrix) '
+                    'as DIR/<name>.npy, float32 / float64, a fixed seeded sample of any array longer than %d entries' % DUMP_MAX_ENTRIES)
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def self_launch(args):
@@ -176,12 +188,15 @@ def main():
         t_pre = 0.0
         t3 = time.perf_counter()
         state.update(t_ingest=t1 - t0, t_pre=t_pre, n_iter=n_iter, conv=conv, stats=stats, t_total=t3 - t0)
-        res.free()
+        if state.get('keep_outputs'):
+            state['outputs'] = (m, res, (att, ptr, mem))     # written by dump_outputs after the timed region, which frees res
+        else:
+            res.free()
         if state.get('keep_matrix'):
             state['matrix'] = m                      # the parity leg (after the timed region) re-uses the last link matrix
         elif state.get('keep_block'):
             state['block'], state['shape'] = m, shape        # the N-rank sweep leg re-uses this rank's row block of the link matrix
-        else:
+        elif not state.get('keep_outputs'):
             m.free()
 
     def barrier():
@@ -201,8 +216,10 @@ def main():
     t_ing = t_mcl = t_pre = 0.0
     iters = 0
     for k_step in range(args.steps):
-        state['keep_matrix'] = (k_step == args.steps - 1) and world == 1 and not sharded_path and not (args.no_parity and args.sweep <= 1)
-        state['keep_block'] = (k_step == args.steps - 1) and sharded_path and world > 1 and args.sweep > 1
+        last = k_step == args.steps - 1
+        state['keep_matrix'] = last and args.full and world == 1 and not sharded_path and not (args.no_parity and args.sweep <= 1)
+        state['keep_block'] = last and args.full and sharded_path and world > 1 and args.sweep > 1
+        state['keep_outputs'] = last and bool(args.dump_outputs) and rank == 0
         step()
         t_ing += state['t_ingest']; t_mcl += state['t_mcl']; t_pre += state['t_pre']; iters += state['n_iter']
     barrier()
@@ -304,39 +321,42 @@ def main():
                           'contigs': int(n), 'pairs_per_gpu': local_pairs, 'full_keys': int(state['n_full']),
                           'flank_keys': int(state['n_flank']), 'link_matrix_nnz': int(state['nnz_link'])},
                'mcl_iters_per_s': mcl['iters_per_s'], 'ingest': ingest, 'mcl': mcl, 'roofline': roofline}
-        if world == 1 and args.text_lines:
-            out['ingest']['text'] = text_leg(args, gen, id1, p1, id2, p2, dev)
         if sharded_path:
             out['ingest']['sharded_build_ms_last_step'] = state.get('shard_ms')
             # rank 0's clocks per step, to lay next to DESIGN.md 5.2: [ms, bytes received by this rank, calls]
             out['mcl']['sharded_stage_ms_bytes_calls_per_step'] = {k_: [v[0] / K, v[1] / K, v[2] / K] for k_, v in (mcl_stages or {}).items()}
-        if state.get('matrix') is not None and args.sweep > 1:
-            try:
-                out['sweep'] = sweep_leg(args, state['matrix'], t_mcl / K)
-            except RuntimeError as e:
-                out['sweep'] = {'error': str(e)[:300]}
-        if state.get('matrix') is not None and not args.no_parity:
-            out['parity'] = parity_leg(args, state.pop('matrix'))
-        elif state.get('matrix') is not None:
-            state.pop('matrix').free()
-        if world == 1 and not sharded_path and not args.no_seam:
-            try:
-                out['seam_e2e'] = seam_leg(args, gen, id1, p1, id2, p2)
-            except Exception as e:                       # noqa: BLE001 — a leg after the timed region must never take the line down
-                out['seam_e2e'] = {'error': '%s: %s' % (type(e).__name__, str(e)[:300])}
-        if not args.no_cpu_baseline and world == 1:          # a reported baseline of the N = 1 line only
-            out['cpu_baseline'] = cpu_baseline(args, gen, table, flank, id1, p1, id2, p2, state)
-        if world == 1 and not sharded_path and not args.no_run_e2e:
-            # ONE wall clock over run()'s own sequence from the .pairs file (a1 + alignments.bed -> S5 -> HT_links.pkl -> paired_links.clm ->
-            # filter_fragments -> full_links.pkl -> dict_to_matrix -> run_mcl_clustering with its 20 inflation directories), after everything else
-            try:
-                sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tools'))
-                import c3_run
-                torch.cuda.empty_cache()
-                _lib.check(_lib.load().hhx_pool_trim())
-                out['run_e2e'] = c3_run.run_job(pairs=local_pairs, nchrs=args.nchrs, gen=gen, arrays=[id1, p1, id2, p2], device=dev)
-            except Exception as e:                       # noqa: BLE001 — a leg after the timed region must never take the line down
-                out['run_e2e'] = {'error': '%s: %s' % (type(e).__name__, str(e)[:300])}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *state.pop('outputs'), state, kept=state.get('matrix') is not None or state.get('block') is not None)
+        if args.full:
+            if world == 1 and args.text_lines:
+                out['ingest']['text'] = text_leg(args, gen, id1, p1, id2, p2, dev)
+            if state.get('matrix') is not None and args.sweep > 1:
+                try:
+                    out['sweep'] = sweep_leg(args, state['matrix'], t_mcl / K)
+                except RuntimeError as e:
+                    out['sweep'] = {'error': str(e)[:300]}
+            if state.get('matrix') is not None and not args.no_parity:
+                out['parity'] = parity_leg(args, state.pop('matrix'))
+            elif state.get('matrix') is not None:
+                state.pop('matrix').free()
+            if world == 1 and not sharded_path and not args.no_seam:
+                try:
+                    out['seam_e2e'] = seam_leg(args, gen, id1, p1, id2, p2)
+                except Exception as e:                       # noqa: BLE001 — a leg after the timed region must never take the line down
+                    out['seam_e2e'] = {'error': '%s: %s' % (type(e).__name__, str(e)[:300])}
+            if not args.no_cpu_baseline and world == 1:          # a reported baseline of the N = 1 line only
+                out['cpu_baseline'] = cpu_baseline(args, gen, table, flank, id1, p1, id2, p2, state)
+            if world == 1 and not sharded_path and not args.no_run_e2e:
+                # ONE wall clock over run()'s own sequence from the .pairs file (a1 + alignments.bed -> S5 -> HT_links.pkl -> paired_links.clm ->
+                # filter_fragments -> full_links.pkl -> dict_to_matrix -> run_mcl_clustering with its 20 inflation directories), after everything else
+                try:
+                    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tools'))
+                    import c3_run
+                    torch.cuda.empty_cache()
+                    _lib.check(_lib.load().hhx_pool_trim())
+                    out['run_e2e'] = c3_run.run_job(pairs=local_pairs, nchrs=args.nchrs, gen=gen, arrays=[id1, p1, id2, p2], device=dev)
+                except Exception as e:                       # noqa: BLE001 — a leg after the timed region must never take the line down
+                    out['run_e2e'] = {'error': '%s: %s' % (type(e).__name__, str(e)[:300])}
         final_out = out
     # ---- outside the timed region, every rank: run_mcl_clustering's inflation sweep (:2155-2158) shared out over the ranks
     # (sharded.sweep_sharded: ONE expansion across the ranks, the heavy iterations of the low inflations row-sharded, the light
@@ -402,6 +422,28 @@ def main():
     if sharded_path:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, m, res, clusters, state, kept):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as DIR/<name>.npy — the clusters
+    (interpret: attractor rows, member lists), the MCL result matrix and the link matrix it started from (CSR), integers as
+    float64 and values as float32, plus a summary [iterations, converged, full keys, flank keys].  An array longer than
+    DUMP_MAX_ENTRIES is replaced by the entries at a fixed seeded sample of positions, drawn from its length alone, so that
+    the indices and values of one matrix are sampled alike and two builds of the project compare entry for entry."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {'summary': np.array([state['n_iter'], bool(state['conv']), state['n_full'], state['n_flank']], np.float64)}
+    for tag, a in zip(('cluster_attractors', 'cluster_ptr', 'cluster_members'), clusters):
+        arrays[tag] = a
+    for tag, csr in (('mcl', res), ('link_matrix', m)):
+        for part, a in zip(('indptr', 'indices', 'data'), csr.to_arrays()):
+            arrays[tag + '_' + part] = a
+    res.free()
+    if not kept:                                     # else the legs of --full take the link matrix over
+        m.free()
+    for name, a in arrays.items():
+        if len(a) > DUMP_MAX_ENTRIES:
+            a = a[np.unique(np.random.default_rng(len(a)).integers(0, len(a), DUMP_MAX_ENTRIES))]
+        np.save(os.path.join(d, name + '.npy'), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def text_leg(args, gen, id1, p1, id2, p2, dev):

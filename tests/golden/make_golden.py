@@ -908,6 +908,21 @@ def gen_plot(path):
     np.savez_compressed(path, **out)
 
 
+def gen_dict_to_matrix_reversed(path):
+    """S4 on a link dict holding both (a, b) and (b, a) (tests/test_patch_reference.py::reversed_key_links): the matrix and
+    fragment index the reference's own dict_to_matrix returns for it, duplicates summed"""
+    from tests.test_patch_reference import reversed_key_links
+    names, d, frag_set = reversed_key_links()
+    m, idx = H.dict_to_matrix(dict(d), set(frag_set), dense_matrix=False, add_self_loops=True)
+    m = m.tocsc()
+    m.sum_duplicates()
+    m.sort_indices()
+    out = dict(indptr=m.indptr, indices=m.indices, data=m.data, idx_names=np.array(list(idx), dtype='U8'),
+               idx_values=np.array(list(idx.values()), np.int64))
+    print('dict_to_matrix reversed keys: keys', len(d), 'nnz', m.nnz)
+    np.savez_compressed(path, **out)
+
+
 if __name__ == '__main__':
     assert os.environ.get('PYTHONHASHSEED') == '0', 'run with PYTHONHASHSEED=0'
     if len(sys.argv) > 1 and sys.argv[1] == 'c4_40k':         # hours of one core: never part of the default run
@@ -925,6 +940,9 @@ if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'weights':
         gen_weights(os.path.join(HERE, 'weights.npz'))
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'd2m_reversed':
+        gen_dict_to_matrix_reversed(os.path.join(HERE, 'dict_to_matrix_reversed.npz'))
+        sys.exit(0)
     gen_mcl(os.path.join(HERE, 'mcl_cases.npz'))
     gen_ingest(os.path.join(HERE, 'ingest_ctgs.npz'), os.path.join(HERE, 'ingest_bins.npz'))
     gen_pipeline(os.path.join(HERE, 'pipeline_toy.npz'))
@@ -939,3 +957,4 @@ if __name__ == '__main__':
     gen_reassign(os.path.join(HERE, 'reassign.npz'))
     gen_plot(os.path.join(HERE, 'plot.npz'))
     gen_ingest_wide(os.path.join(HERE, 'ingest_wide.npz'))
+    gen_dict_to_matrix_reversed(os.path.join(HERE, 'dict_to_matrix_reversed.npz'))
