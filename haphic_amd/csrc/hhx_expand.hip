@@ -2543,6 +2543,7 @@ int hhx_expand_impl(const hhx_csr *a, const hhx_csr *b, const CodedOperand &code
         HHX_HIP(hipMemcpyAsync(hc, counts.p, sizeof hc, hipMemcpyDeviceToHost, g_stream));
         HHX_HIP(hipMemcpyAsync(hw, cursors.p + 5, sizeof hw, hipMemcpyDeviceToHost, g_stream));
         HHX_HIP(hipStreamSynchronize(g_stream));
+        const unsigned cls_rows[4] = {hc[0], hc[1], hc[2], hc[3]};      // what k_classify decided, before the hash kernel hands rows back
         ExParams P;
         P.Ap = a->indptr.p; P.Aj = a->indices.p; P.Ax = a->data.p;
         P.Bp = b->indptr.p; P.Bj = b->indices.p; P.Bx = b->data.p;
@@ -2597,6 +2598,17 @@ int hhx_expand_impl(const hhx_csr *a, const hhx_csr *b, const CodedOperand &code
             HHX_HIP(hipStreamSynchronize(g_stream));
         }
         const unsigned n_hash_rows = hc[3];
+        // per-class row counts of this attempt (profile counters, reported once the attempt stands): the tests assert which classes ran
+        auto count_classes = [&](i32 n_win_launch) {
+            if (!prof_enabled()) return;
+            prof_count("expand_rows_window", (i64)cls_rows[0]);
+            prof_count("expand_rows_compact", (i64)cls_rows[1]);
+            prof_count("expand_rows_tiny", (i64)cls_rows[2]);
+            prof_count("expand_rows_hash", (i64)cls_rows[3]);
+            prof_count("expand_rows_hash_to_window", (i64)hc[0] - (i64)cls_rows[0]);
+            prof_count("expand_rows_hash_to_compact", (i64)hc[1] - (i64)cls_rows[1]);
+            if (hc[0]) prof_count("expand_window_n_win", n_win_launch);
+        };
         // ---- rows of the window class grouped by attractor (k_expand_group): decided once per call
         if (group_mode < 0 || (group_mode == 1 && attempt > 0)) {
             group_mode = 0;
@@ -2794,6 +2806,7 @@ int hhx_expand_impl(const hhx_csr *a, const hhx_csr *b, const CodedOperand &code
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count(), cur[2] ? "  OVERFLOW -> retry" : "");
         if (dense) {                                   // the rows are in coded.dense_out; nothing to pack
             if (hc[0] != (unsigned)n_rows) return fail("expand (dense): %u of %d rows took the window class", hc[0], n_rows);
+            count_classes(n_win_use);
             if (prof_enabled()) {                      // what the launches actually walked (the symmetric mode skips the blocks J < I)
                 prof_count("expand_window_products", (i64)cur[8]);
                 prof_count("expand_window_a_reads", (i64)cur[9]);
@@ -2825,6 +2838,7 @@ int hhx_expand_impl(const hhx_csr *a, const hhx_csr *b, const CodedOperand &code
         g_expand_demand.out = (i64)cur[1];
         g_expand_demand.cand = (i64)cur[0];
         if (attempt) prof_count("expand_pool_retries", attempt);
+        count_classes(n_win_use);
         return pack_rows_to_csr(n_rows, n_cols, row_cnt.p, indptr.p, row_off.p, out_col.p, out_val.p, out);
     }
     return fail("expand: survivor pool kept overflowing");

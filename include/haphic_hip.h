@@ -72,7 +72,10 @@ int hhx_profile_reset(void);
 int hhx_profile_get(const char *kernel, double *total_ms, int64_t *launches);
 /* event counters gathered while profiling is on: "expand_window_products" (products streamed by
  * k_expand_window_pass), "expand_window_a_reads" (entries of A staged, summed over the column windows),
- * "ingest_records" (read pairs that survive the map stage) */
+ * "ingest_records" (read pairs that survive the map stage); per fused expansion, the rows k_classify puts in each class —
+ * "expand_rows_window", "expand_rows_compact", "expand_rows_tiny", "expand_rows_hash" — the hash-class rows the hash kernel hands
+ * back ("expand_rows_hash_to_window", "expand_rows_hash_to_compact"), the column windows of the window-class launch
+ * ("expand_window_n_win") and the survivor-pool retries ("expand_pool_retries") */
 int hhx_profile_counter(const char *name, int64_t *value);
 
 /* ---------------------------------------------------------------- matrices */

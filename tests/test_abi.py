@@ -1,5 +1,6 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library builds for gfx950, loads without a GPU
 and exports exactly the symbols include/haphic_hip.h declares (no compute calls here)."""
+import ast
 import os
 import re
 
@@ -81,3 +82,45 @@ def test_tune_knobs_documented_and_refused_when_unknown():
     assert lib.hhx_tune(b'no_such_knob', 1) != 0
     assert b'unknown knob' in lib.hhx_last_error()
     assert lib.hhx_tune(b'block_tiles', 0) == 0 and lib.hhx_tune(b'block_tiles', -2 ** 63) == 0
+
+
+def _is_gpu_mark(node):
+    """pytest.mark.gpu, or a list / tuple holding it"""
+    if isinstance(node, (ast.List, ast.Tuple)):
+        return any(_is_gpu_mark(e) for e in node.elts)
+    return isinstance(node, ast.Attribute) and node.attr == 'gpu' and isinstance(node.value, ast.Attribute) and node.value.attr == 'mark'
+
+
+def _tune_literals(tree):
+    """the knob names of every _lib.tune('<name>', ...) call below `tree`"""
+    out = set()
+    for node in ast.walk(tree):
+        if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'tune' and isinstance(node.func.value, ast.Name)
+                and node.func.value.id == '_lib' and node.args and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str)):
+            out.add(node.args[0].value)
+    return out
+
+
+def test_every_tune_knob_is_set_by_a_gpu_test():
+    """"EVERY setting of every knob gives the same results" (include/haphic_hip.h) is only as good as the tests that switch the knobs:
+    every name hhx_tune accepts must be set, by name, by some _lib.tune('<name>', ...) call of a gpu-marked test module or test"""
+    rt = open(os.path.join(ROOT, 'haphic_amd', 'csrc', 'hhx_runtime.hip')).read()
+    block = re.search(r'k_tune_names\[\]\s*=\s*\{(.*?)nullptr\};', rt, flags=re.S).group(1)
+    block = re.sub(r'#ifdef HHX_PROBE_BUILD.*?#endif', '', block, flags=re.S)
+    names = set(re.findall(r'"([a-z0-9_]+)"', block))
+    assert len(names) >= 10
+    covered = set()
+    tests = os.path.join(ROOT, 'tests')
+    for f in sorted(os.listdir(tests)):
+        if not (f.startswith('test_') and f.endswith('.py')):
+            continue
+        tree = ast.parse(open(os.path.join(tests, f)).read(), filename=f)
+        module_gpu = any(isinstance(n, ast.Assign) and any(isinstance(t, ast.Name) and t.id == 'pytestmark' for t in n.targets) and _is_gpu_mark(n.value)
+                         for n in tree.body)
+        if module_gpu:
+            covered |= _tune_literals(tree)
+            continue
+        for n in ast.walk(tree):
+            if isinstance(n, ast.FunctionDef) and n.name.startswith('test') and any(_is_gpu_mark(dec) for dec in n.decorator_list):
+                covered |= _tune_literals(n)
+    assert names <= covered, 'hhx_tune knobs no gpu test sets: %s' % sorted(names - covered)

@@ -5,6 +5,7 @@ import pytest
 
 from haphic_amd import _lib
 from oracle import oracle as orc
+from tests import expand_classes as ec
 
 pytestmark = pytest.mark.gpu
 
@@ -194,6 +195,8 @@ def test_mcl_deterministic_and_larger():
     assert n1 == n2 and all(np.array_equal(x, y) for x, y in zip(a1, a2)), 'run-to-run bits differ'
     o = orc.mcl(A2, 2, 2.0, 60, 1e-4, spgemm_mode=1, fx_shift=52)
     assert o[3] == n1 and o[4] == c1
+    assert np.array_equal(a1[0], o[0]) and np.array_equal(a1[1], o[1]), 'final pattern differs from the oracle'
+    assert np.array_equal(a1[2], o[2]), 'final values differ from the oracle (inflation 2: bit-equal)'
     assert clusters_of(*_lib.interpret(r1)) == clusters_of(*orc.interpret(o[:3]))
 
 
@@ -603,20 +606,33 @@ def oracle_fused(A, B, infl, pruning=1e-4, shift=52):
 
 @pytest.mark.parametrize('hash_max', [0, 4_000_000])          # 0: the window / compact / tiny classes alone; default: rows try the LDS hash table first
 @pytest.mark.parametrize('n,block,deg_in,deg_out,infl', [
-    (3000, 100, 20, 1, 2.0),        # window mode, one window
-    (40000, 400, 60, 1, 2.0),       # window mode, several column windows (n_cols > LDS capacity)
-    (40000, 50, 4, 0, 2.0),         # compact (bitmap-rank) mode
-    (5000, 100, 10, 2, 1.4),        # pow() path
-    (70000, 10, 2, 1, 3.0),         # tiny rows
-    (8000, 8000, 40, 0, 2.0),       # ~4500 distinct columns per row: leaves the hash class for the window class
-    (20000, 10000, 40, 0, 2.0),     # the same, below the window class's product count: leaves it for the compact class
+    # the classes k_classify gives at hash_max 0 | 4 M (tests/expand_classes.py: asserted against the device's counters below)
+    (3000, 100, 20, 1, 2.0),        # compact, one bitmap | hash
+    (40000, 400, 60, 1, 2.0),       # compact, one LDS rank window (f below window_min, <= 1462 distinct columns) | hash
+    (40000, 50, 4, 0, 2.0),         # compact + a few tiny rows | hash
+    (5000, 100, 10, 2, 1.4),        # pow() path: compact | hash
+    (70000, 10, 2, 1, 3.0),         # tiny + compact | tiny + hash
+    (8000, 8000, 40, 0, 2.0),       # window, one column window | hash: ~4500 distinct columns per row, handed back to the window class
+    (20000, 10000, 40, 0, 2.0),     # compact, most rows over two LDS rank windows | hash, handed back to the compact class (below window_min)
+    (4000, 200, 40, 20, 2.0),       # window, one column window | hash, most rows handed back to the window class
+    (21000, 200, 40, 20, 2.0),      # window (two column windows: n_cols > 20352) + compact | hash, handed back to both
 ])
 def test_fused_expand_inflate_prune(n, block, deg_in, deg_out, infl, hash_max):
     A = clustered_stochastic(n, block, deg_in, deg_out, 31)
     d = _lib.DeviceCSR.from_arrays(*A)
     _lib.tune('hash_max', hash_max)
     try:
-        p, f, nnz_c = _lib.expand_inflate_prune(d, d, infl, 1e-4)
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        try:
+            p, f, nnz_c = _lib.expand_inflate_prune(d, d, infl, 1e-4)
+        finally:
+            _lib.profile_enable(False)
+        cnt = {k: _lib.profile_counter('expand_rows_' + k) for k in ('window', 'compact', 'tiny', 'hash', 'hash_to_window')}
+        want = ec.classes(A, A, hash_max)
+        assert tuple(cnt[k] for k in ('window', 'compact', 'tiny', 'hash')) == tuple(want[k] for k in ('window', 'compact', 'tiny', 'hash')), (cnt, ec.describe(want))
+        if cnt['window'] + cnt['hash_to_window']:
+            assert _lib.profile_counter('expand_window_n_win') == want['n_win']
         ref, ref_nnz_c = oracle_fused(A, A, infl)
         got = p.to_arrays()
         assert nnz_c == ref_nnz_c
@@ -730,14 +746,16 @@ def test_mcl_links_class_stream_iteration0():
         _lib.tune('cls', 0)                                          # generic (column, value) stream
         r0, n0, c0 = _lib.mcl(links, 2, 2.0, 200, 1e-4, links=True)
         one0 = _lib.mcl(links, 2, 2.0, 1, 1e-4, links=True)[0].to_arrays()
-        for cls, nc, tile_u in ((1, 1, 0), (1, 3, 0), (1, 2, 0), (1, 3, 1), (1, 3, 2), (1, 1, 3), (1, 3, 4), (1, 2, 8), (0, 3, 1), (0, 3, 2), (0, 3, 3),
-                                (0, 3, 4)):
+        for cls, nc, tile_u, bal in ((1, 1, 0, 1), (1, 3, 0, 1), (1, 2, 0, 1), (1, 3, 1, 1), (1, 3, 2, 1), (1, 1, 3, 1), (1, 3, 4, 1), (1, 2, 8, 1),
+                                     (1, 1, 0, 0), (1, 3, 2, 0), (1, 2, 8, 0), (0, 3, 1, 1), (0, 3, 2, 1), (0, 3, 3, 1), (0, 3, 4, 1)):
             _lib.tune('cls', cls)
             _lib.tune('cls_nc', nc)
             _lib.tune('tile_u', tile_u)
+            _lib.tune('cls_balance', bal)                            # 0: the class stream's segments unbalanced
             one = _lib.mcl(links, 2, 2.0, 1, 1e-4, links=True)[0].to_arrays()
-            assert all(np.array_equal(x, y) for x, y in zip(one, one0)), 'stream layout changed bits: %r' % ((cls, nc, tile_u),)
+            assert all(np.array_equal(x, y) for x, y in zip(one, one0)), 'stream layout changed bits: %r' % ((cls, nc, tile_u, bal),)
     finally:
+        _lib.tune('cls_balance', None)
         _lib.tune('cls', 1)
         _lib.tune('cls_nc', 1)
         _lib.tune('tile_u', 0)
@@ -865,6 +883,16 @@ def test_dense_sweep_equals_fused_iteration0():
             assert all(np.array_equal(x, y) for x, y in zip(g_.to_arrays(), ref.to_arrays())), 'multi-inflation epilogue, group %r, inflation %r' % (group, r)
             g_.free()
     whole.free()
+    # without the first guess of the pool sizes (tune "dense_seed_hint" 0): the first pass learns the demand itself — the same bits
+    _lib.tune('dense_seed_hint', 0)
+    try:
+        whole = _lib.DenseRows(links, 0, n)
+        for r, g_ in zip((1.4, 3.0), whole.inflate_prune_multi((1.4, 3.0), 1e-4)):
+            assert all(np.array_equal(x, y) for x, y in zip(g_.to_arrays(), want[r][0].to_arrays())), 'dense_seed_hint 0, inflation %r' % r
+            g_.free()
+        whole.free()
+    finally:
+        _lib.tune('dense_seed_hint', None)
     # the block stored as its UPPER BLOCK TRIANGLE alone (what an order the square does not fit for takes: n = 200k on one GPU) —
     # the lower blocks are never written, the epilogue turns them one block row at a time: the same bits
     _lib.tune('dense_tri', 1)
