@@ -11,6 +11,10 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
   --keep-reference-ingest    leave S5 / a1 (parse_alignments*, pairs_generator*) to the reference
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
+  --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
+                             byte-identical to the one-rank run.  Under torchrun (RANK / WORLD_SIZE set) its ranks are used instead.
+  --host-transport           with --gpus: gloo through host memory instead of RCCL, for ranks that share a device (the default when N
+                             exceeds the number of devices)
 """
 import os
 import sys
@@ -46,6 +50,13 @@ def main(argv=None):
     command = argv.pop(0)
     if command not in ('cluster', 'plot'):
         raise SystemExit('haphic_amd wraps the "cluster" and "plot" steps only (got {!r}); run the other steps with the reference'.format(command))
+    from . import ranks
+    gpus, host_transport = ranks.take_args(argv)
+    if command == 'plot' and (gpus or 1) > 1:
+        raise SystemExit('--gpus is a flag of the "cluster" step only')
+    if (gpus or 1) > 1 and not ranks.in_torchrun():
+        # one fresh child process per rank (never exec: this process may not replace itself), each with RANK / WORLD_SIZE / LOCAL_RANK
+        return ranks.launch([sys.executable, '-m', 'haphic_amd', command] + argv, gpus, host_transport)
     ref = _take(argv, '--reference', True) or os.environ.get('HAPHIC_REFERENCE')
     device = int(_take(argv, '--device', True) or 0)
     keep_ingest = bool(_take(argv, '--keep-reference-ingest', False))
@@ -61,6 +72,9 @@ def main(argv=None):
                 sys.modules[name] = m
     from . import _lib, patch
     _lib.check(_lib.load().hhx_set_device(device))                 # fails here, loudly, without a GPU or the library
+    ctx = ranks.init(True if host_transport else None) if command == 'cluster' else None     # a rank of a multi-rank job: its own device
+    if ctx is not None and ctx.rank > 0:
+        return ranks.run_rank(None)                                 # serve the phases rank 0 announces; rank 0 writes every file
     sys.path.insert(0, scripts)
     if command == 'plot':
         import HapHiC_plot as P                                     # needs pysam / portion / matplotlib, as the reference does
@@ -72,8 +86,7 @@ def main(argv=None):
     import HapHiC_cluster as H                                      # the unmodified reference module
     patch.patch_reference(H, ingest=not keep_ingest)
     sys.argv = ['haphic cluster'] + argv
-    H.run(H.parse_arguments(), 'HapHiC_cluster.log')                # == HapHiC_cluster.main() :2962-2967
-    return 0
+    return ranks.run_rank(lambda: H.run(H.parse_arguments(), 'HapHiC_cluster.log'))      # == HapHiC_cluster.main() :2962-2967
 
 
 if __name__ == '__main__':

@@ -148,9 +148,12 @@ SIGNATURES = {
     'hhx_byte_sink_reserve': (C.c_int, [C.c_void_p, C.c_int64, c_vpp]),
     'hhx_byte_sink_commit': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     'hhx_byte_sink_close': (C.c_int, [C.c_void_p, c_i64p]),
+    'hhx_byte_sink_open_deferred': (C.c_int, [C.c_char_p, C.c_int64, C.c_int64, c_vpp]),
+    'hhx_byte_sink_set_base': (C.c_int, [C.c_void_p, C.c_int64]),
     'hhx_pairs_parser_set_bed_sink': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_text_reader_open': (C.c_int, [C.c_char_p, C.c_int64, C.c_int, c_vpp]),
     'hhx_text_reader_open_bgzf': (C.c_int, [C.c_char_p, C.c_int64, C.c_int, c_vpp]),
+    'hhx_text_reader_open_range': (C.c_int, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, c_vpp]),
     'hhx_text_reader_next': (C.c_int, [C.c_void_p, c_vpp, c_i64p]),
     'hhx_text_reader_close': (C.c_int, [C.c_void_p]),
     'hhx_files_pending': (C.c_int, [c_i64p, c_i64p]),
@@ -552,10 +555,15 @@ def files_join():
 class ByteSink:
     """hhx_byte_sink: a file fed from device buffers through the library's file-writer thread (alignments.bed, deferred)"""
 
-    def __init__(self, path, hbm_budget_bytes=0, expected_bytes=0):
+    def __init__(self, path, hbm_budget_bytes=0, expected_bytes=0, deferred=False):
+        """deferred: the bytes go to the file at an offset given later by set_base() (hhx_byte_sink_open_deferred)"""
         self.h = C.c_void_p()
         _register_join()
-        check(load().hhx_byte_sink_open(os.fsencode(path), int(hbm_budget_bytes), int(expected_bytes), C.byref(self.h)))
+        fn = load().hhx_byte_sink_open_deferred if deferred else load().hhx_byte_sink_open
+        check(fn(os.fsencode(path), int(hbm_budget_bytes), int(expected_bytes), C.byref(self.h)))
+
+    def set_base(self, base):
+        check(load().hhx_byte_sink_set_base(self.h, int(base)))
 
     def close(self):
         """queue the close (the file is complete after files_join()); returns the bytes handed to the sink"""
@@ -569,9 +577,14 @@ class ByteSink:
 class TextReader:
     """hhx_text_reader: a text file as chunks of whole lines in pinned host memory, read ahead by threads of the library"""
 
-    def __init__(self, path, chunk_bytes=256 << 20, threads=4, bgzf=False):
-        """bgzf: the file is bgzipped (BGZF blocks inflated by the threads); RuntimeError('... is not a BGZF file ...') for anything else"""
+    def __init__(self, path, chunk_bytes=256 << 20, threads=4, bgzf=False, byte_range=None):
+        """bgzf: the file is bgzipped (BGZF blocks inflated by the threads); RuntimeError('... is not a BGZF file ...') for anything else.
+        byte_range (begin, end): only the lines whose first byte lies in it (hhx_text_reader_open_range; BGZF: compressed offsets)"""
         self.h = C.c_void_p()
+        if byte_range is not None:
+            check(load().hhx_text_reader_open_range(os.fsencode(path), int(byte_range[0]), int(byte_range[1]), int(chunk_bytes), int(threads),
+                                                    int(bool(bgzf)), C.byref(self.h)))
+            return
         fn = load().hhx_text_reader_open_bgzf if bgzf else load().hhx_text_reader_open
         check(fn(os.fsencode(path), int(chunk_bytes), int(threads), C.byref(self.h)))
 

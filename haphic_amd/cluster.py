@@ -1056,6 +1056,18 @@ class PairsText:
             if carry:
                 yield carry
 
+    def multi_rank(self):
+        """True when the ranks of a multi-rank job share this file out by byte ranges (ranks.py): plain text or BGZF.  A plain gzip stream has
+        no block boundaries to start a rank at: rank 0 reads it whole, as BAM input."""
+        from . import ranks
+        if not ranks.active():
+            return False
+        if self.aln_format == 'pairs':
+            return True
+        with open(self.path, 'rb') as f:
+            h = f.read(18)
+        return len(h) == 18 and h[:3] == b'\x1f\x8b\x08' and bool(h[3] & 4) and h[12:14] == b'BC'
+
     def batches(self, names, wide=False):
         """per chunk: (parser, n_lines) with the id / position arrays of the chunk on the device (wide: int64 positions).  The reference writes
         alignments.bed inside its generator loop (:1549-1557) and nothing in run() reads it: the BED bytes of a chunk stay in HBM, where the kernel
@@ -1069,7 +1081,15 @@ class PairsText:
         if wide:
             parser.set_wide(True)
         reader = None
-        if _lib.files_async():
+        ranked = self.multi_rank()
+        if ranked:
+            # one rank's share: the lines whose first byte lies in its byte range; its BED records go behind those of the ranks before it
+            from . import ranks
+            ctx = ranks.current()
+            byte_range = ranks.byte_ranges(os.path.getsize(self.path), ctx.world)[ctx.rank]
+            reader = _lib.TextReader(self.path, self.chunk_bytes, threads=int(os.environ.get('HAPHIC_READ_THREADS', '8')),
+                                     bgzf=self.aln_format != 'pairs', byte_range=byte_range)
+        elif _lib.files_async():
             # the native front end: the file read ahead into pinned memory by threads of the library (hhx_text_reader), alignments.bed deferred.
             # bgzipped .pairs: the BGZF blocks are inflated by those threads; a plain gzip stream (no block boundaries) keeps Python's gzip below
             threads = int(os.environ.get('HAPHIC_READ_THREADS', '8'))
@@ -1080,7 +1100,10 @@ class PairsText:
                     raise
         if reader is not None:
             size = os.path.getsize(self.path) * (1 if self.aln_format == 'pairs' else 4)                          # (text deflates ~4 x)
-            sink = _lib.ByteSink(self.bed_path, expected_bytes=int(1.45 * size)) if self.bed_path else None       # two BED records ~ 1.35 x the line
+            if ranked:
+                size //= ctx.world
+            deferred = ranked and ctx.rank > 0
+            sink = _lib.ByteSink(self.bed_path, expected_bytes=int(1.45 * size), deferred=deferred) if self.bed_path else None   # two BED records ~ 1.35 x the line
             try:
                 if sink is not None:
                     parser.set_bed_sink(sink)
@@ -1097,6 +1120,10 @@ class PairsText:
                     yield parser, n
                     st['consumer_s'] += clock() - t
                     t = clock()
+                if ranked and self.bed_path:
+                    base = ranks.bed_bases(st['bed_bytes'])
+                    if deferred:
+                        sink.set_base(base)
             finally:
                 if sink is not None:
                     parser.set_bed_sink(None)
@@ -1299,9 +1326,15 @@ def _ingest_handle(alignments, table, flank, bins, chunk=1 << 22, want_pairs=Fal
         if sweep_follows and (text or bam) and not bins:
             _prewarm_dense_block(table.n_frag)   # run() goes on to run_mcl_clustering: its dense block is taken from the driver while the file is read
         if text:                             # a1 on the device: text chunk -> id arrays -> ingest, nothing returns to the host
+            ranked = alignments.multi_rank()
+            if ranked:                       # the other ranks tokenise their byte ranges of the file meanwhile (ranks.py, phase `ingest`)
+                from . import ranks
+                ranks.announce('ingest', ranks.ingest_spec(alignments, table.ctg_names, table.wide))
             for parser, k in alignments.batches(table.ctg_names, wide=table.wide):
                 if k:
                     ing.push_device(k, *parser.device_arrays()[:4], wide=table.wide)
+            if ranked:
+                ranks.gather_into(ing, table.wide)      # their pairs behind rank 0's, in rank order: the file's order
         elif bam:                            # f4: BGZF inflate on host threads, record decode on the device
             for _reader, k, ptrs in alignments.batches(table.ctg_names):
                 ing.push_device(k, *ptrs)
@@ -1639,6 +1672,12 @@ def run_mcl_clustering(link_matrix, bin_set, frag_len_dict, frag_index_dict, exp
     else:
         m = _to_device(link_matrix)
     n = m.shape3[0]
+    from . import ranks
+    if dist is None and ranks.active():                              # a multi-rank job: the other ranks join the sweep (ranks.py, phase `sweep`)
+        dist = ranks.share_sweep(m, dict(bin_set=bin_set, frag_len_dict=frag_len_dict, frag_index_dict=frag_index_dict, expansion=expansion,
+                                         min_inflation=min_inflation, max_inflation=max_inflation, inflation_step=inflation_step,
+                                         max_iter=max_iter, pruning=pruning, fa_dict={k: [None, v[1], v[2]] for k, v in fa_dict.items()},
+                                         nchrs=nchrs, outdir_root=outdir_root))
     # The reference pre-expands once (:2146-2147) and restarts every inflation from that matrix.  M^e is nearly dense: as a
     # CSR matrix it is materialised only while it is guaranteed to fit scipy's int32 index range (n^2 < 2^31).  Beyond that
     # (and always when a sweep of several inflations is asked for with expansion 2 on a matrix of that size) the rows of M^2

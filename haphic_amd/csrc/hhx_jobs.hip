@@ -10,6 +10,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <deque>
 #include <memory>
@@ -248,6 +249,16 @@ struct hhx_byte_sink {
     int device = 0;
     std::thread allocator;
     std::string alloc_err;
+    // a sink opened by hhx_byte_sink_open_deferred: where its bytes go in the file is known only at hhx_byte_sink_set_base.  Until then the
+    // committed ranges stay parked in their slabs; when the HBM budget runs out they spill, in order, to a part file beside the target
+    // (`spill`), which the set_base job copies into place in front of the parked ranges
+    struct Range { Slab *slab; void *dev; i64 n; hipEvent_t ev; };
+    bool deferred = false, based = false;
+    std::vector<Range> parked;
+    FileSink spill;
+    std::string spill_path;
+    bool spill_opened = false;
+    i64 spilled = 0, base = 0;
 
     void alloc_loop() {
         (void)hipSetDevice(device);
@@ -269,16 +280,21 @@ struct hhx_byte_sink {
     }
 };
 
-extern "C" int hhx_byte_sink_open(const char *path, int64_t hbm_budget_bytes, int64_t expected_bytes, hhx_byte_sink **out) {
+static int submit_range(hhx_byte_sink *s, hhx_byte_sink::Slab *slab, void *dev, int64_t n_bytes, hipEvent_t ev, bool spill);
+
+static int byte_sink_open(const char *path, int64_t hbm_budget_bytes, int64_t expected_bytes, bool deferred, hhx_byte_sink **out) {
     if (!path || !out) return fail("hhx_byte_sink_open: null pointer");
     int dev = 0;
     HHX_HIP(hipGetDevice(&dev));
-    const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
-    if (fd < 0) return fail("cannot open %s for writing: %s", path, strerror(errno));
+    const int fd = deferred ? -1 : ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);      // deferred: opened (never truncated) by the set_base job
+    if (!deferred && fd < 0) return fail("cannot open %s for writing: %s", path, strerror(errno));
+    static std::atomic<int> n_deferred(0);
     auto *s = new hhx_byte_sink();
     s->path = path;
     s->device = dev;
     s->out.fd = fd;                      // the pinned buffers and the pwrite() threads are made by the first range's job, on the writer thread
+    s->deferred = deferred;
+    if (deferred) s->spill_path = s->path + ".part." + std::to_string((long long)getpid()) + "." + std::to_string(n_deferred++);
     if (hbm_budget_bytes <= 0) {
         size_t f = 0, t = 0;
         if (hipMemGetInfo(&f, &t) != hipSuccess) { (void)hipGetLastError(); t = (size_t)64 << 30; }
@@ -297,6 +313,105 @@ extern "C" int hhx_byte_sink_open(const char *path, int64_t hbm_budget_bytes, in
     return 0;
 }
 
+extern "C" int hhx_byte_sink_open(const char *path, int64_t hbm_budget_bytes, int64_t expected_bytes, hhx_byte_sink **out) {
+    return byte_sink_open(path, hbm_budget_bytes, expected_bytes, false, out);
+}
+
+// a byte sink whose place in the file is not known yet (one rank's share of alignments.bed: it starts where the ranks before it end)
+extern "C" int hhx_byte_sink_open_deferred(const char *path, int64_t hbm_budget_bytes, int64_t expected_bytes, hhx_byte_sink **out) {
+    return byte_sink_open(path, hbm_budget_bytes, expected_bytes, true, out);
+}
+
+static int copy_into(int from, int to, i64 n, i64 at) {
+    std::vector<unsigned char> b((size_t)8 << 20);
+    for (i64 done = 0; done < n;) {
+        const ssize_t k = ::pread(from, b.data(), (size_t)std::min<i64>((i64)b.size(), n - done), done);
+        if (k <= 0) return fail("reading a part file failed: %s", strerror(k < 0 ? errno : EIO));
+        for (ssize_t w = 0; w < k;) {
+            const ssize_t m = ::pwrite(to, b.data() + w, (size_t)(k - w), at + done + w);
+            if (m <= 0) return fail("writing failed: %s", strerror(m < 0 ? errno : EIO));
+            w += m;
+        }
+        done += k;
+    }
+    return 0;
+}
+
+// the deferred sink's bytes start at file offset `base`: the spilled part goes into place, then the parked ranges and every later one behind it
+extern "C" int hhx_byte_sink_set_base(hhx_byte_sink *s, int64_t base) {
+    if (!s || base < 0) return fail("hhx_byte_sink_set_base: bad argument");
+    std::vector<hhx_byte_sink::Range> todo;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (!s->deferred || s->based) return fail("hhx_byte_sink_set_base: %s", s->deferred ? "the base is already set" : "not a deferred sink");
+        s->based = true;
+        s->base = base;
+        todo.swap(s->parked);
+    }
+    (void)files_submit("place " + s->path, s, [s]() -> int {
+        const int fd = ::open(s->path.c_str(), O_WRONLY | O_CREAT, 0666);
+        if (fd < 0) { s->failed = true; return fail("cannot open %s for writing: %s", s->path.c_str(), strerror(errno)); }
+        s->out.fd = fd;
+        s->out.pos = s->base + s->spilled;
+        if (!s->spill_opened || s->failed) return 0;
+        int rc = s->spill.close();
+        s->spill_opened = false;
+        const int part = rc ? -1 : ::open(s->spill_path.c_str(), O_RDONLY);
+        if (!rc && part < 0) rc = fail("cannot open %s: %s", s->spill_path.c_str(), strerror(errno));
+        if (!rc) rc = copy_into(part, fd, s->spilled, s->base);
+        if (part >= 0) ::close(part);
+        ::unlink(s->spill_path.c_str());
+        if (rc) s->failed = true;
+        return rc;
+    }, 0);
+    for (auto &r : todo) (void)submit_range(s, r.slab, r.dev, r.n, r.ev, false);
+    return 0;
+}
+
+// the file-writer job of one committed range: to the file (or, spill, to the part file of a deferred sink), then the slab goes back
+static int submit_range(hhx_byte_sink *s, hhx_byte_sink::Slab *slab, void *dev, int64_t n_bytes, hipEvent_t ev, bool spill) {
+    return files_submit("bytes -> " + s->path, s, [s, slab, dev, n_bytes, ev, spill]() -> int {
+        int rc = 0;
+        if (!s->failed) {
+            FileSink &f = spill ? s->spill : s->out;
+            bool &opened = spill ? s->spill_opened : s->opened;
+            if (!opened) { rc = spill ? f.open(s->spill_path.c_str()) : f.open_fd(f.fd); opened = true; }
+            if (!rc && hipStreamWaitEvent(g_stream, ev, 0) != hipSuccess) rc = fail("hipStreamWaitEvent failed");
+            if (!rc) rc = f.write_device((const unsigned char *)dev, (size_t)n_bytes);      // synchronises the stream piece by piece
+            if (rc) s->failed = true;                                // the first failure is the one reported; later ranges are dropped
+        }
+        (void)hipStreamSynchronize(g_stream);
+        (void)hipEventDestroy(ev);
+        void *give_back = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(s->mu);
+            if (--slab->outstanding == 0 && slab->sealed) {
+                if (s->stop_alloc || s->free_.size() >= 2 || slab->cap != s->slab_bytes) {   // the producer has finished (or is slower than the file, or
+                    give_back = slab->p;                             // the slab was one chunk's own): it leaves HBM for good — to the driver, not to the
+                    s->all.erase(std::find(s->all.begin(), s->all.end(), slab));        // pool's cache, where 4 GB blocks would starve what runs next
+                    s->allocated -= (i64)slab->cap;
+                    delete slab;
+                } else { slab->used = 0; slab->sealed = false; s->free_.push_back(slab); }
+            }
+        }
+        if (give_back) pool_free_to_driver(give_back);
+        s->cv.notify_all();
+        return rc;
+    }, 0);
+}
+
+// a deferred sink out of HBM budget: its parked ranges go to the part file (caller's thread, s->mu not held)
+static void spill_parked(hhx_byte_sink *s) {
+    std::vector<hhx_byte_sink::Range> todo;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->based) return;
+        todo.swap(s->parked);
+        for (auto &r : todo) s->spilled += r.n;
+    }
+    for (auto &r : todo) (void)submit_range(s, r.slab, r.dev, r.n, r.ev, true);
+}
+
 // room for n_bytes in the ring (16-byte aligned): waits for a slab when the current one is full
 extern "C" int hhx_byte_sink_reserve(hhx_byte_sink *s, int64_t n_bytes, void **dev) {
     if (!s || !dev || n_bytes < 0) return fail("hhx_byte_sink_reserve: bad argument");
@@ -305,13 +420,44 @@ extern "C" int hhx_byte_sink_reserve(hhx_byte_sink *s, int64_t n_bytes, void **d
     if (!s->cur || s->cur->used + (size_t)n_bytes > s->cur->cap) {
         if (s->cur) {                                                // full: goes back to the ring when its last range is written
             s->cur->sealed = true;
-            if (s->cur->outstanding == 0) { s->cur->used = 0; s->cur->sealed = false; s->free_.push_back(s->cur); }
+            if (s->cur->outstanding == 0 && s->cur->cap != s->slab_bytes) {                 // a chunk's own slab, written out: back to the driver
+                s->all.erase(std::find(s->all.begin(), s->all.end(), s->cur));
+                s->allocated -= (i64)s->cur->cap;
+                pool_free_to_driver(s->cur->p);
+                delete s->cur;
+            } else if (s->cur->outstanding == 0) { s->cur->used = 0; s->cur->sealed = false; s->free_.push_back(s->cur); }
             s->cur = nullptr;
         }
-        if ((size_t)n_bytes > s->slab_bytes) return fail("hhx_byte_sink_reserve: %lld bytes in one piece, slabs of %zu", (long long)n_bytes, s->slab_bytes);
+        if ((size_t)n_bytes > s->slab_bytes) {
+            // one chunk's BED outgrew the slabs (they are sized from a guess of the file's text): a slab of its own, freed when it is written
+            const size_t cap = ((size_t)n_bytes + 255) & ~(size_t)255;
+            lk.unlock();
+            void *p = pool_alloc(cap);
+            lk.lock();
+            if (!p) return fail("hhx_byte_sink: no device memory for a slab of %zu bytes: %s", cap, g_err.c_str());
+            auto *slab = new hhx_byte_sink::Slab();
+            slab->p = (unsigned char *)p; slab->cap = cap;
+            s->all.push_back(slab);
+            s->allocated += (i64)cap;
+            s->cur = slab;
+            *dev = slab->p;
+            return 0;
+        }
         if (s->allocated + (i64)s->slab_bytes <= s->budget) s->target = std::max<i64>(s->target, std::min<i64>(s->budget, s->allocated + 2 * (i64)s->slab_bytes));   // more than was expected
         s->cv.notify_all();
-        s->cv.wait(lk, [&] { return !s->free_.empty() || (s->alloc_failed && s->all.empty()); });
+        // a deferred sink whose parked ranges hold every slab, with no room for another (the budget is spent, or the device is out of memory):
+        // nothing would free a slab before the base is known — the parked ranges spill to the part file, which hands their slabs back
+        auto must_spill = [&] { return s->deferred && !s->based && s->free_.empty() && !s->parked.empty() &&
+                                       (s->alloc_failed || s->allocated + (i64)s->slab_bytes > s->budget); };
+        for (;;) {
+            if (must_spill()) {
+                lk.unlock();
+                spill_parked(s);
+                lk.lock();
+            }
+            s->cv.wait(lk, [&] { return !s->free_.empty() || (s->alloc_failed && s->all.empty()) || must_spill(); });
+            if (!must_spill()) break;
+        }
         if (s->free_.empty()) return fail("hhx_byte_sink: no device memory for a slab: %s", s->alloc_err.c_str());
         s->cur = s->free_.front();
         s->free_.pop_front();
@@ -337,44 +483,34 @@ extern "C" int hhx_byte_sink_commit(hhx_byte_sink *s, void *dev, int64_t n_bytes
         ++slab->outstanding;
         s->pushed += n_bytes;
     }
-    return files_submit("bytes -> " + s->path, s, [s, slab, dev, n_bytes, ev]() -> int {
-        int rc = 0;
-        if (!s->failed) {
-            if (!s->opened) { rc = s->out.open_fd(s->out.fd); s->opened = true; }
-            if (!rc && hipStreamWaitEvent(g_stream, ev, 0) != hipSuccess) rc = fail("hipStreamWaitEvent failed");
-            if (!rc) rc = s->out.write_device((const unsigned char *)dev, (size_t)n_bytes);      // synchronises the stream piece by piece
-            if (rc) s->failed = true;                                // the first failure is the one reported; later ranges are dropped
-        }
-        (void)hipStreamSynchronize(g_stream);
-        (void)hipEventDestroy(ev);
-        void *give_back = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(s->mu);
-            if (--slab->outstanding == 0 && slab->sealed) {
-                if (s->stop_alloc || s->free_.size() >= 2) {         // the producer has finished (or is slower than the file): the slab leaves HBM for good —
-                    give_back = slab->p;                             // to the driver, not to the pool's cache, where 4 GB blocks would starve what runs next
-                    s->all.erase(std::find(s->all.begin(), s->all.end(), slab));
-                    s->allocated -= (i64)slab->cap;
-                    delete slab;
-                } else { slab->used = 0; slab->sealed = false; s->free_.push_back(slab); }
-            }
-        }
-        if (give_back) pool_free_to_driver(give_back);
-        s->cv.notify_all();
-        return rc;
-    }, 0);
+    if (s->deferred && !s->based) {
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->parked.push_back({slab, dev, n_bytes, ev});
+        return 0;
+    }
+    return submit_range(s, slab, dev, n_bytes, ev, false);
 }
 
 extern "C" int hhx_byte_sink_close(hhx_byte_sink *s, int64_t *n_bytes_pushed) {
     if (!s) return 0;
     if (n_bytes_pushed) *n_bytes_pushed = s->pushed;
-    { std::lock_guard<std::mutex> lk(s->mu); s->stop_alloc = true; if (s->cur) s->cur->sealed = true; }
+    bool unplaced = false;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->stop_alloc = true;
+        if (s->cur) s->cur->sealed = true;
+        unplaced = s->deferred && !s->based;                          // closed before its base was known (a run that failed): nothing is written
+        for (auto &r : s->parked) { (void)hipEventDestroy(r.ev); --r.slab->outstanding; }
+        s->parked.clear();
+    }
     s->cv.notify_all();
     if (s->allocator.joinable()) s->allocator.join();
-    return files_submit("close " + s->path, s, [s]() -> int {
-        int rc = 0;
-        if (s->opened) rc = s->out.close();
-        else if (s->out.fd >= 0) { if (::close(s->out.fd) != 0) rc = fail("close failed: %s", strerror(errno)); s->out.fd = -1; }
+    return files_submit("close " + s->path, s, [s, unplaced]() -> int {
+        int rc = unplaced ? fail("%s: the byte sink was closed before its place in the file was set", s->path.c_str()) : 0;
+        if (s->spill_opened) { (void)s->spill.close(); s->spill_opened = false; }
+        if (s->deferred) ::unlink(s->spill_path.c_str());
+        if (s->opened) { const int c = s->out.close(); if (!rc) rc = c; }
+        else if (s->out.fd >= 0) { if (::close(s->out.fd) != 0 && !rc) rc = fail("close failed: %s", strerror(errno)); s->out.fd = -1; }
         (void)hipStreamSynchronize(g_stream);
         for (auto *slab : s->all) { pool_free_to_driver(slab->p); delete slab; }      // every range is on disk: idle on both streams
         const bool failed = s->failed;

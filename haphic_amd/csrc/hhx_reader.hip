@@ -24,6 +24,8 @@ struct hhx_text_reader {
     int state[2] = {0, 0};                // 0 free for the reader, 1 filled, 2 held by the caller
     std::vector<unsigned char> tail;      // the bytes after the last line break of the chunk read last: the front of the next chunk
     bool bgzf = false;                    // the file is BGZF: `at` / `size` count COMPRESSED bytes, the buffers hold inflated text
+    i64 skip = 0;                         // BGZF range: inflated bytes to drop in front of the first line (the range starts inside a block)
+    i64 limit = -1;                       // BGZF range: inflated bytes to hand out in all (-1: to the end of the file)
     std::vector<unsigned char> comp;      // compressed bytes read and not yet inflated (whole blocks + a partial tail)
     std::string emsg;                     // set with err == EBADMSG
     int fill = 0, take = 0;               // next buffer to fill / to hand out
@@ -81,6 +83,16 @@ struct hhx_text_reader {
                     if (!blocks.empty()) {
                         if (inflate_blocks(comp.data(), blocks, buf[b] + have, n_threads)) { std::lock_guard<std::mutex> lk(mu); err = EBADMSG; emsg = g_err; eof = true; cv.notify_all(); return; }
                         comp.erase(comp.begin(), comp.begin() + (long)used);
+                        if (skip) {                                  // a range: the text in front of its first line belongs to the rank before
+                            const size_t d = (size_t)std::min<i64>(skip, (i64)inflated);
+                            memmove(buf[b] + have, buf[b] + have + d, inflated - d);
+                            inflated -= d;
+                            skip -= (i64)d;
+                        }
+                        if (limit >= 0) {                            // ... and the text behind its last line to the rank after
+                            if ((i64)inflated >= limit) { inflated = (size_t)limit; at = size; comp.clear(); }
+                            limit -= (i64)inflated;
+                        }
                         have += inflated;
                     }
                     last = at >= size && comp.empty();
@@ -115,15 +127,100 @@ struct hhx_text_reader {
     }
 };
 
-static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, bool bgzf, hhx_text_reader **out);
+// The byte-range rule of a rank's share of a file (haphic_amd/ranks.py owned_range): a range [begin, end) owns the lines whose first byte lies in it.
+// A line starts at 0 and after every '\n'; a boundary x inside a line moves forward to the start of the next line (or the end of the text), so
+// the ranges of consecutive boundaries cover every line exactly once, in order.  Lines are cut on '\n' only: a "\r\n" stays whole.
+namespace {
+
+struct BgzfIndex {                        // every BGZF block of the file: compressed offset, compressed size, inflated size (its ISIZE trailer)
+    std::vector<i64> off, bsize, isize, text;                // text[k] = inflated bytes in front of block k (text.size() == n + 1)
+};
+
+int bgzf_index(int fd, i64 size, BgzfIndex &ix) {
+    ix = BgzfIndex();
+    ix.text.push_back(0);
+    unsigned char h[12 + 256], t[4];
+    for (i64 at = 0; at < size;) {
+        // the block header: gzip magic, FEXTRA, then the BC subfield (BSIZE) wherever it stands among the extra subfields (as scan_blocks reads it)
+        const ssize_t k = ::pread(fd, h, sizeof h, at);
+        if (k < 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return fail("not a BGZF block at compressed offset %lld", (long long)at);
+        const i64 xlen = (i64)(h[10] | (h[11] << 8));
+        i64 bs = 0;
+        for (i64 x = 0; x + 4 <= xlen && 12 + x + 6 <= (i64)k;) {
+            const unsigned char *f = h + 12 + x;
+            const i64 slen = (i64)(f[2] | (f[3] << 8));
+            if (f[0] == 'B' && f[1] == 'C' && slen == 2) { bs = (i64)(f[4] | (f[5] << 8)) + 1; break; }
+            x += 4 + slen;
+        }
+        if (!bs) return fail("not a BGZF block at compressed offset %lld: no BC subfield", (long long)at);
+        if (bs < 12 + xlen + 8 || at + bs > size || ::pread(fd, t, 4, at + bs - 4) != 4) return fail("truncated BGZF block at compressed offset %lld", (long long)at);
+        ix.off.push_back(at); ix.bsize.push_back(bs); ix.isize.push_back((i64)bgzf_rd32(t));
+        ix.text.push_back(ix.text.back() + ix.isize.back());
+        at += bs;
+    }
+    return 0;
+}
+
+int bgzf_inflate_block(int fd, const BgzfIndex &ix, size_t k, std::vector<unsigned char> &out) {
+    std::vector<unsigned char> comp((size_t)ix.bsize[k]);
+    if (::pread(fd, comp.data(), comp.size(), ix.off[k]) != (ssize_t)comp.size()) return fail("cannot read a BGZF block: %s", strerror(errno));
+    std::vector<Block> blocks;
+    size_t used = 0, inflated = 0;
+    if (scan_blocks(comp, (size_t)1 << 20, blocks, used, inflated) || blocks.size() != 1) return fail("not a BGZF block at compressed offset %lld", (long long)ix.off[k]);
+    out.assign(inflated, 0);
+    return inflated ? inflate_blocks(comp.data(), blocks, out.data(), 1) : 0;
+}
+
+// the text offset of the first line start at or after text offset x (x itself when a line starts there)
+int bgzf_line_start(int fd, const BgzfIndex &ix, i64 x, i64 &start) {
+    const i64 total = ix.text.back();
+    start = x;
+    if (x <= 0 || x >= total) return 0;
+    size_t k = (size_t)(std::upper_bound(ix.text.begin(), ix.text.end(), x - 1) - ix.text.begin()) - 1;     // the block holding byte x - 1
+    std::vector<unsigned char> t;
+    for (i64 from = x - 1; k < ix.off.size(); ++k) {
+        if (!ix.isize[k]) continue;
+        if (bgzf_inflate_block(fd, ix, k, t)) return -1;
+        for (i64 i = std::max<i64>(from, ix.text[k]) - ix.text[k]; i < (i64)t.size(); ++i)
+            if (t[(size_t)i] == '\n') { start = ix.text[k] + i + 1; return 0; }
+        from = ix.text[k + 1];
+    }
+    start = total;
+    return 0;
+}
+
+int plain_line_start(int fd, i64 size, i64 x, i64 &start) {
+    start = x;
+    if (x <= 0 || x >= size) return 0;
+    unsigned char b[1 << 16];
+    for (i64 at = x - 1; at < size;) {
+        const ssize_t k = ::pread(fd, b, (size_t)std::min<i64>((i64)sizeof b, size - at), at);
+        if (k <= 0) return fail("cannot read: %s", strerror(k < 0 ? errno : EIO));
+        const void *nl = memchr(b, '\n', (size_t)k);
+        if (nl) { start = at + ((const unsigned char *)nl - b) + 1; return 0; }
+        at += k;
+    }
+    start = size;
+    return 0;
+}
+
+}  // namespace
+
+static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, bool bgzf, int64_t begin, int64_t end, hhx_text_reader **out);
 extern "C" int hhx_text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, hhx_text_reader **out) {
-    return text_reader_open(path, chunk_bytes, n_threads, false, out);
+    return text_reader_open(path, chunk_bytes, n_threads, false, -1, -1, out);
 }
 // the same over a BGZF file (bgzip): the chunks are inflated text.  Fails with "not a BGZF file" on anything else (plain gzip included)
 extern "C" int hhx_text_reader_open_bgzf(const char *path, int64_t chunk_bytes, int n_threads, hhx_text_reader **out) {
-    return text_reader_open(path, chunk_bytes, n_threads, true, out);
+    return text_reader_open(path, chunk_bytes, n_threads, true, -1, -1, out);
 }
-static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, bool bgzf, hhx_text_reader **out) {
+// one rank's share of the file: the lines whose first byte lies in [begin, end) (BGZF: the blocks that start in [begin, end) of the COMPRESSED file,
+// the same line rule on their inflated text)
+extern "C" int hhx_text_reader_open_range(const char *path, int64_t begin, int64_t end, int64_t chunk_bytes, int n_threads, int bgzf, hhx_text_reader **out) {
+    if (begin < 0 || end < begin) return fail("hhx_text_reader_open_range: bad range [%lld, %lld)", (long long)begin, (long long)end);
+    return text_reader_open(path, chunk_bytes, n_threads, bgzf != 0, begin, end, out);
+}
+static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, bool bgzf, int64_t begin, int64_t end, hhx_text_reader **out) {
     if (!path || !out || chunk_bytes <= 0) return fail("hhx_text_reader_open: bad argument");
     const int fd = ::open(path, O_RDONLY);
     if (fd < 0) return fail("cannot open %s: %s", path, strerror(errno));
@@ -135,24 +232,57 @@ static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads
         const bool ok = k == (ssize_t)sizeof h && h[0] == 0x1f && h[1] == 0x8b && h[2] == 8 && (h[3] & 4) && h[12] == 'B' && h[13] == 'C';
         if (!ok && st.st_size != 0) { ::close(fd); return fail("%s is not a BGZF file (bgzip); a plain gzip stream cannot be inflated in parallel", path); }
     }
+    const bool ranged = begin >= 0;
+    i64 lo = 0, hi = (i64)st.st_size, skip = 0, limit = -1;
+    i64 text_bound = -1;                                               // BGZF: inflated bytes the reader can meet, from the ISIZE trailers
+    if (ranged) begin = std::min<i64>(begin, st.st_size), end = std::min<i64>(end, st.st_size);
+    if (bgzf && (ranged || st.st_size < 2 * chunk_bytes)) {           // (a large whole file needs no index: its buffers are two chunks whatever it inflates to)
+        BgzfIndex ix;
+        // a malformed block fails a range here.  The whole file goes on: its cap is bounded by the whole blocks in front of the bad one (+ 68 KB of
+        // room, more than one block inflates to), and the reader reports the bad block when it gets there, as it did without the index
+        if (bgzf_index(fd, (i64)st.st_size, ix) && ranged) { ::close(fd); return -1; }
+        if (ranged) {
+            // blocks [kb, ke) start in [begin, end); their text [text[kb], text[ke]), moved to line starts
+            const size_t kb = (size_t)(std::lower_bound(ix.off.begin(), ix.off.end(), (i64)begin) - ix.off.begin());
+            const size_t ke = (size_t)(std::lower_bound(ix.off.begin(), ix.off.end(), (i64)end) - ix.off.begin());
+            i64 t0 = 0, t1 = 0;
+            if (bgzf_line_start(fd, ix, ix.text[kb], t0) || bgzf_line_start(fd, ix, ix.text[ke], t1)) { ::close(fd); return -1; }
+            if (t0 < t1) {
+                const size_t k0 = (size_t)(std::upper_bound(ix.text.begin(), ix.text.end(), t0) - ix.text.begin()) - 1;       // the block holding text byte t0
+                const size_t k1 = (size_t)(std::upper_bound(ix.text.begin(), ix.text.end(), t1 - 1) - ix.text.begin()) - 1;   // ... and t1 - 1
+                lo = ix.off[k0];
+                hi = ix.off[k1] + ix.bsize[k1];
+                skip = t0 - ix.text[k0];
+                limit = t1 - t0;
+                text_bound = ix.text[k1 + 1] - ix.text[k0];
+            } else lo = hi = 0;
+        } else text_bound = ix.text.back();
+    } else if (ranged) {
+        if (plain_line_start(fd, (i64)st.st_size, begin, lo) || plain_line_start(fd, (i64)st.st_size, end, hi)) { ::close(fd); return -1; }
+        if (hi < lo) hi = lo;
+    }
     auto *r = new hhx_text_reader();
     r->fd = fd;
-    r->size = (i64)st.st_size;
+    r->at = lo;
+    r->size = hi;
+    r->skip = skip;
+    r->limit = limit;
     r->chunk = (size_t)chunk_bytes;
     r->cap = 2 * (size_t)chunk_bytes + 4096;                           // a carried tail is shorter than a chunk (or the file has a line longer than one)
     r->bgzf = bgzf;
-    if (!bgzf && (size_t)r->size + 4096 < r->cap) r->cap = (size_t)r->size + 4096;      // a small file: no more pinned memory than it has bytes (pinning costs ~0.5 ms per MB)
-    if (bgzf && (size_t)r->size * 12 + ((size_t)256 << 10) < r->cap) r->cap = (size_t)r->size * 12 + ((size_t)256 << 10);     // (text deflates 3-5 x; 12 x is the bound assumed)
+    if (!bgzf && (size_t)(hi - lo) + 4096 < r->cap) r->cap = (size_t)(hi - lo) + 4096;     // a small file: no more pinned memory than it has bytes (pinning costs ~0.5 ms per MB)
+    if (bgzf && text_bound >= 0 && (size_t)text_bound + ((size_t)68 << 10) < r->cap) r->cap = (size_t)text_bound + ((size_t)68 << 10);   // the ISIZE trailers bound the text (+ one block of room)
     r->n_threads = n_threads > 0 ? std::min(n_threads, 16) : 4;
     for (int k = 0; k < 2; ++k)
         if (hipHostMalloc((void **)&r->buf[k], r->cap, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
             for (int q = 0; q < k; ++q) (void)hipHostFree(r->buf[q]);
+            const size_t cap = r->cap;
             ::close(fd);
             delete r;
-            return fail("hhx_text_reader_open: no pinned memory for two buffers of %zu bytes", (size_t)(2 * chunk_bytes + 4096));
+            return fail("hhx_text_reader_open: no pinned memory for two buffers of %zu bytes", cap);
         }
-    if (r->size == 0) r->eof = true;
+    if (r->size <= r->at) r->eof = true;
     else r->th = std::thread([r] { r->loop(); });
     *out = r;
     return 0;

@@ -43,4 +43,10 @@ class HostStagedCollectives:
                                   group=self._g)
         out.copy_(h)
 
+    def send(self, t, dst):
+        self._d.send(t.cpu().contiguous(), dst, group=self._g)
 
+    def recv(self, t, src):
+        h = t.new_empty(t.shape, device='cpu')
+        self._d.recv(h, src, group=self._g)
+        t.copy_(h)

@@ -384,6 +384,10 @@ int hhx_text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, h
 /* the same over a bgzipped file (`bgzipped_pairs`: gzip.open in the reference :1541 / :1564): BGZF blocks inflated by n_threads threads straight into the
  * pinned buffer.  A file that is not BGZF (a plain gzip stream has no block boundaries to inflate in parallel) is refused: the caller keeps its gzip reader. */
 int hhx_text_reader_open_bgzf(const char *path, int64_t chunk_bytes, int n_threads, hhx_text_reader **out);
+/* one rank's share of the file (haphic_amd/ranks.py): the lines whose first byte lies in [begin, end) — a boundary inside a line moves forward past
+ * the next '\n', so the ranges [b_r, b_{r+1}) of consecutive boundaries hand out every line once, in order; a range may be empty.  bgzf != 0: begin /
+ * end are COMPRESSED offsets, the range owns the BGZF blocks that start in it and the same line rule applies to their inflated text. */
+int hhx_text_reader_open_range(const char *path, int64_t begin, int64_t end, int64_t chunk_bytes, int n_threads, int bgzf, hhx_text_reader **out);
 int hhx_text_reader_next(hhx_text_reader *r, const uint8_t **host, int64_t *n_bytes);
 int hhx_text_reader_close(hhx_text_reader *r);
 /* measurement only — the writer counterpart of hhx_pairs_parse for synthetic read pairs ("pairs written as .pairs text"): line k =
@@ -520,6 +524,11 @@ int hhx_byte_sink_open(const char *path, int64_t hbm_budget_bytes, int64_t expec
 int hhx_byte_sink_reserve(hhx_byte_sink *sink, int64_t n_bytes, void **dev);
 int hhx_byte_sink_commit(hhx_byte_sink *sink, void *dev, int64_t n_bytes);
 int hhx_byte_sink_close(hhx_byte_sink *sink, int64_t *n_bytes_pushed);
+/* a sink whose bytes start at a file offset known only later (one rank's share of alignments.bed, behind the ranks before it): the file is not
+ * truncated, committed ranges stay parked in their slabs until hhx_byte_sink_set_base(base) — when the HBM budget runs out before that, they spill
+ * in order to a part file beside the target, copied into place by the set_base job.  Closing it before set_base writes nothing and fails the close. */
+int hhx_byte_sink_open_deferred(const char *path, int64_t hbm_budget_bytes, int64_t expected_bytes, hhx_byte_sink **out);
+int hhx_byte_sink_set_base(hhx_byte_sink *sink, int64_t base);
 int hhx_pairs_parser_set_bed_sink(hhx_pairs_parser *p, hhx_byte_sink *sink);
 int hhx_files_pending(int64_t *n_pending, int64_t *n_done);
 int hhx_files_join(int64_t *n_failed);
