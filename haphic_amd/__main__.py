@@ -2,13 +2,15 @@
 its seams (SURVEY §8b "who calls it"): import the reference's HapHiC_cluster module, re-bind S1-S6 with
 haphic_amd.patch.patch_reference, call the reference's run(args, log_file) exactly as its main() does (:2962-2967).
 Argument parsing, logging, file formats and every stage outside the hot path are the reference's own code.
+`--correct_nrounds N` (assembly correction) runs on the device too: both passes over the alignment file, the break-point detection and the breaking
+(haphic_amd/correct.py); correct_assembly's round loop and its FASTA writer stay the reference's.
 `python -m haphic_amd plot <arguments of "haphic plot">` does the same for HapHiC_plot.py: parse_pairs / parse_bam (the read-pair
 binning into the scaffold-bin contact matrix) run on the device (haphic_amd.plot.patch_plot), main() is the reference's.
 
 The reference checkout is found through --reference DIR or $HAPHIC_REFERENCE (the repository root or its scripts/
 directory).  Extra flags of the wrapper (removed before the reference parses the command line):
   --device N                 HIP device ordinal (default 0)
-  --keep-reference-ingest    leave S5 / a1 (parse_alignments*, pairs_generator*) to the reference
+  --keep-reference-ingest    leave S5 / a1 (parse_alignments*, pairs_generator*) and the correction passes to the reference
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are

@@ -158,6 +158,20 @@ SIGNATURES = {
     'hhx_text_reader_close': (C.c_int, [C.c_void_p]),
     'hhx_files_pending': (C.c_int, [c_i64p, c_i64p]),
     'hhx_files_join': (C.c_int, [c_i64p]),
+    'hhx_correct_create': (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, c_vpp]),
+    'hhx_correct_push': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    'hhx_correct_finalize': (C.c_int, [C.c_void_p, c_i64p]),
+    'hhx_correct_shape': (C.c_int, [C.c_void_p, c_i32p, c_i64p, c_i64p]),
+    'hhx_correct_fetch_segments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_correct_fetch_coverage': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_correct_fetch_pairs': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_correct_detect': (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, c_i64p]),
+    'hhx_correct_fetch_break_points': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_correct_break': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_correct_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_remap_create': (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, c_vpp]),
+    'hhx_remap_apply': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'hhx_remap_destroy': (C.c_int, [C.c_void_p]),
 }
 
 _lib = None
@@ -1082,6 +1096,105 @@ class Ingest:
     def destroy(self):
         if self.h is not None and self.h.value:
             load().hhx_ingest_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class CorrectTable:
+    """hhx_correct: coverage bins and (lo, hi) position lists of the intra-contig read pairs (pass one of --correct_nrounds), the
+    break-point detection and the per-pair half of the breaking on them.  Segments = the contigs of the FASTA after finalize(), the
+    children of the broken contigs after break_()."""
+
+    def __init__(self, ctg_len, resolution):
+        lens = np.ascontiguousarray(ctg_len, np.int64)
+        self.resolution = int(resolution)
+        self.h = C.c_void_p()
+        check(load().hhx_correct_create(len(lens), ptr(lens), self.resolution, C.byref(self.h)))
+
+    def push(self, id1, pos1, id2, pos2):
+        arrs = [np.ascontiguousarray(a, np.int32) for a in (id1, pos1, id2, pos2)]
+        check(load().hhx_correct_push(self.h, arrs[0].size, *[ptr(a) for a in arrs], 0))
+
+    def push_device(self, n, id1_ptr, pos1_ptr, id2_ptr, pos2_ptr):
+        check(load().hhx_correct_push(self.h, int(n), C.c_void_p(id1_ptr), C.c_void_p(pos1_ptr), C.c_void_p(id2_ptr), C.c_void_p(pos2_ptr), 1))
+
+    def finalize(self):
+        n = C.c_int64(0)
+        check(load().hhx_correct_finalize(self.h, C.byref(n)))
+        return n.value
+
+    def shape(self):
+        """(segments, bins of the flat coverage array, pairs)"""
+        s, b, p = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        check(load().hhx_correct_shape(self.h, C.byref(s), C.byref(b), C.byref(p)))
+        return s.value, b.value, p.value
+
+    def segments(self):
+        """(bin_off, n_bins, length, pair_off[n_seg + 1]) of the table"""
+        n = self.shape()[0]
+        out = np.empty(n, np.int64), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n + 1, np.int64)
+        check(load().hhx_correct_fetch_segments(self.h, *[ptr(a) for a in out]))
+        return out
+
+    def coverage(self):
+        """the flat coverage array; segment s = [bin_off[s], bin_off[s] + n_bins[s])"""
+        out = np.empty(self.shape()[1], np.int32)
+        check(load().hhx_correct_fetch_coverage(self.h, ptr(out)))
+        return out
+
+    def pairs(self):
+        """lo, hi interleaved, int32 [2 * n_pairs], segment order (segment s = items [2 * pair_off[s], 2 * pair_off[s + 1]))"""
+        out = np.empty(2 * self.shape()[2], np.int32)
+        check(load().hhx_correct_fetch_pairs(self.h, ptr(out)))
+        return out
+
+    def detect(self, median_cov_ratio, region_len_ratio, min_region_cutoff):
+        """-> (n_bp[n_seg], bp_cov[n_seg], bp_bin[sum n_bp]): break points per segment, their coverage, their bins in segment order"""
+        n = self.shape()[0]
+        n_bp, cov, total = np.zeros(n, np.int32), np.zeros(n, np.int32), C.c_int64(0)
+        check(load().hhx_correct_detect(self.h, float(median_cov_ratio), float(region_len_ratio), int(min_region_cutoff), ptr(n_bp), ptr(cov),
+                                        C.byref(total)))
+        bins = np.empty(total.value, np.int32)
+        check(load().hhx_correct_fetch_break_points(self.h, ptr(bins) if bins.size else None))
+        return n_bp, cov, bins
+
+    def break_(self, seg, bp_off, bp_pos, zero):
+        seg, bp_pos = np.ascontiguousarray(seg, np.int32), np.ascontiguousarray(bp_pos, np.int32)
+        bp_off, zero = np.ascontiguousarray(bp_off, np.int64), np.ascontiguousarray(zero, np.uint8)
+        check(load().hhx_correct_break(self.h, len(seg), ptr(seg), ptr(bp_off), ptr(bp_pos), ptr(zero)))
+
+    def destroy(self):
+        if self.h is not None and self.h.value:
+            load().hhx_correct_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class ContigRemap:
+    """hhx_remap: (original contig id, position) -> (corrected contig id, position - break offset) in place on device arrays."""
+
+    def __init__(self, off, break_pos, new_id):
+        off, break_pos, new_id = (np.ascontiguousarray(a, np.int32) for a in (off, break_pos, new_id))
+        self.h = C.c_void_p()
+        check(load().hhx_remap_create(len(off) - 1, ptr(off), ptr(break_pos) if break_pos.size else None, ptr(new_id) if new_id.size else None,
+                                      C.byref(self.h)))
+
+    def apply(self, n, id_ptr, pos_ptr):
+        check(load().hhx_remap_apply(self.h, int(n), C.c_void_p(id_ptr), C.c_void_p(pos_ptr)))
+
+    def destroy(self):
+        if self.h is not None and self.h.value:
+            load().hhx_remap_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -1318,7 +1318,13 @@ def _ingest_handle(alignments, table, flank, bins, chunk=1 << 22, want_pairs=Fal
     text = isinstance(alignments, PairsText)
     bam = isinstance(alignments, BamRecords)
     ing = _lib.Ingest(table, flank, bins=bins, skip_intra=bool(getattr(alignments, 'inter_only', False)))      # :1582 / refid != mrefid
+    # the correction-aware front ends (correct.py, --correct_nrounds): the file names the ORIGINAL contigs, the table the corrected ones
+    src_names, remap = table.ctg_names, None
     try:
+        if (text or bam) and hasattr(alignments, 'remap_for'):
+            if table.wide:
+                raise RuntimeError('assembly correction keeps int32 positions: contigs of 2^31 bp and more are not supported')
+            src_names, remap = alignments.remap_for(table.ctg_names)
         if want_pairs:
             ing.keep_pairs()
         if want_frag_pairs:
@@ -1330,13 +1336,20 @@ def _ingest_handle(alignments, table, flank, bins, chunk=1 << 22, want_pairs=Fal
             if ranked:                       # the other ranks tokenise their byte ranges of the file meanwhile (ranks.py, phase `ingest`)
                 from . import ranks
                 ranks.announce('ingest', ranks.ingest_spec(alignments, table.ctg_names, table.wide))
-            for parser, k in alignments.batches(table.ctg_names, wide=table.wide):
+            for parser, k in alignments.batches(src_names, wide=table.wide):
                 if k:
-                    ing.push_device(k, *parser.device_arrays()[:4], wide=table.wide)
+                    ptrs = parser.device_arrays()[:4]
+                    if remap is not None:            # convert_ctg :1405-1411 on both ends; alignments.bed was formatted from the text before
+                        remap.apply(k, ptrs[0], ptrs[1])
+                        remap.apply(k, ptrs[2], ptrs[3])
+                    ing.push_device(k, *ptrs, wide=table.wide)
             if ranked:
                 ranks.gather_into(ing, table.wide)      # their pairs behind rank 0's, in rank order: the file's order
         elif bam:                            # f4: BGZF inflate on host threads, record decode on the device
-            for _reader, k, ptrs in alignments.batches(table.ctg_names):
+            for _reader, k, ptrs in alignments.batches(src_names):
+                if remap is not None:
+                    remap.apply(k, ptrs[0], ptrs[1])
+                    remap.apply(k, ptrs[2], ptrs[3])
                 ing.push_device(k, *ptrs)
         elif isinstance(alignments, IdArrays):
             if alignments.names != list(table.ctg_names):
@@ -1369,6 +1382,9 @@ def _ingest_handle(alignments, table, flank, bins, chunk=1 << 22, want_pairs=Fal
     except BaseException:
         ing.destroy()
         raise
+    finally:
+        if remap is not None:
+            remap.destroy()
 
 
 def ingest_links(alignments, table, flank, bins, chunk=1 << 22, want_pairs=False, max_read_pairs=0, want_frag_pairs=False):

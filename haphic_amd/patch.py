@@ -6,7 +6,7 @@
 
 Nothing under /root/reference is edited; the reference resolves these names at call time through its
 module globals, so `setattr` on the module is all that is needed."""
-from . import cluster
+from . import cluster, correct
 
 # seam -> (reference line, replacement)
 SEAMS = {
@@ -43,6 +43,20 @@ OPTIONAL = {
     'pairs_generator_inter_ctgs': ('HapHiC_cluster.py:1562-1583', cluster.pairs_generator_inter_ctgs),
     'bam_generator': ('HapHiC_cluster.py:1586-1593', cluster.bam_generator),                          # f4
 }
+# --correct_nrounds: what run() :2798-2851 and correct_assembly :1200-1297 (which stays the reference's code) call.  The mirrors return and
+# take containers backed by the device table (haphic_amd/correct.py) and feed the S5 mirrors, so they travel with `ingest`; detect / break are
+# handed the original function for containers that were thawed into plain dicts.
+CORRECTION_SEAMS = {
+    'parse_pairs_for_correction': ('HapHiC_cluster.py:1300-1344', correct.parse_pairs_for_correction),
+    'parse_bam_for_correction': ('HapHiC_cluster.py:1362-1398', correct.parse_bam_for_correction),
+    'detect_break_points': ('HapHiC_cluster.py:943-1014', correct.detect_break_points),
+    'break_and_update_ctgs': ('HapHiC_cluster.py:1017-1197', correct.break_and_update_ctgs),
+    'pairs_generator_for_correction_ctg': ('HapHiC_cluster.py:1401-1440', correct.pairs_generator_for_correction_ctg),
+    'bam_generator_for_correction_ctg': ('HapHiC_cluster.py:1443-1470', correct.bam_generator_for_correction_ctg),
+    'pairs_generator_for_correction': ('HapHiC_cluster.py:1473-1509', correct.pairs_generator_for_correction),
+    'bam_generator_for_correction': ('HapHiC_cluster.py:1512-1536', correct.bam_generator_for_correction),
+}
+_NEEDS_ORIGINAL = ('detect_break_points', 'break_and_update_ctgs')
 
 
 # position of `dense_matrix` in the reference signatures: --dense_matrix (:2723) is the reference's own numpy mode, which
@@ -110,9 +124,10 @@ def patch_reference(H, ingest=True, matrix_build=True):
         seams['pairs_generator_inter_ctgs'] = OPTIONAL['pairs_generator_inter_ctgs']
         seams['bam_generator'] = OPTIONAL['bam_generator']                    # f4: consumed by the same S5 mirrors
         seams.update(CONTAINER_SEAMS)
+        seams.update(CORRECTION_SEAMS)
     for name, (_cite, fn) in seams.items():
         saved[name] = getattr(H, name, None)
-        if name in CONTAINER_SEAMS:
+        if name in CONTAINER_SEAMS or name in _NEEDS_ORIGINAL:
             fn = _with_original(fn, saved[name])
         setattr(H, name, _dense_dispatch(fn, saved[name], DENSE_ARG[name]) if name in DENSE_ARG else fn)
     if ingest and getattr(H, 'run', None) is not None:

@@ -128,3 +128,48 @@ def add_allelic_pairs(genome, n_base, ploidy, id1, p1, id2, p2, frac, seed, jitt
     id2 = np.where(pick, mate, id2).astype(id2.dtype)
     p2 = np.where(pick, pos, p2).astype(p2.dtype)
     return id1, p1, id2, p2
+
+
+def join_chimeras(genome, id1, p1, id2, p2, n_chimeras, seed=12345):
+    """Plant chimeric contigs: n_chimeras disjoint pairs of contigs (a, b) from different chromosomes are joined end to end into one
+    contig `chimera_{a}_{b}` of length len_a + len_b that takes a's place in the FASTA order; b disappears and the pairs that lay on
+    it move to the chimera, shifted by len_a.  torch tensors (any device) in and out; returns (genome, id1, p1, id2, p2, joins) with
+    joins = [(id in the new genome, join position len_a)] — the truth an assembly correction should find."""
+    import torch
+    rng = np.random.default_rng(seed)
+    n = genome.n
+    pick = rng.permutation(n)
+    used, pairs_ab = np.zeros(n, bool), []
+    for a in pick.tolist():
+        if len(pairs_ab) == n_chimeras:
+            break
+        if used[a]:
+            continue
+        for _try in range(8):
+            b = int(rng.integers(0, n))
+            if b != a and not used[b] and genome.chrom[b] != genome.chrom[a]:
+                used[a] = used[b] = True
+                pairs_ab.append((a, b))
+                break
+    gone = np.zeros(n, bool)
+    shift = np.zeros(n, np.int64)
+    into = np.arange(n)
+    length = genome.length.copy()
+    names = list(genome.names)
+    for a, b in pairs_ab:
+        gone[b] = True
+        shift[b] = genome.length[a]
+        into[b] = a
+        length[a] = genome.length[a] + genome.length[b]
+        names[a] = 'chimera_{}_{}'.format(a, b)
+    new_of_kept = np.cumsum(~gone) - 1
+    new_id = new_of_kept[into].astype(np.int32)
+    keep = np.flatnonzero(~gone)
+    out = Genome([names[k] for k in keep], length[keep], genome.chrom[keep], genome.start[keep], genome.rev[keep], length[keep] // 256 + 1,
+                 genome.chr_len, genome.nchrs)
+    dev = id1.device
+    t_id, t_shift = torch.as_tensor(new_id, device=dev), torch.as_tensor(shift, device=dev)
+    q1 = (p1.long() + t_shift[id1.long()]).int()
+    q2 = (p2.long() + t_shift[id2.long()]).int()
+    joins = [(int(new_id[a]), int(genome.length[a])) for a, _b in pairs_ab]
+    return out, t_id[id1.long()], q1, t_id[id2.long()], q2, joins

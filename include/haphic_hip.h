@@ -64,7 +64,8 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * shapes and window count of the window kernel); "block_tiles" 0 = iterations >= 1 of the window class walk the stream in tiles
  * of one (B row, window) segment each instead of 64-entry blocks (default 15; 1, 2, 5, 11, 31: other block-tile shapes /
  * addressings); "row_order" 0 = the window-class rows as listed instead of in min-hash order; "reuse" 4 / 2 = the grouped kernel;
- * "dense_seed_hint" (the sweep's first pool sizes).  value INT64_MIN: back to the default.  Unset knobs fall back to the
+ * "dense_seed_hint" (the sweep's first pool sizes); "correct_agg" 1 = hhx_correct_push merges the atomic adds of the lanes of a wave that hit the
+ * same word before they leave the wave (default 0: one atomic per lane; tools/correct_bench.py times both).  value INT64_MIN: back to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
 int hhx_profile_enable(int on);
@@ -532,6 +533,50 @@ int hhx_byte_sink_set_base(hhx_byte_sink *sink, int64_t base);
 int hhx_pairs_parser_set_bed_sink(hhx_pairs_parser *p, hhx_byte_sink *sink);
 int hhx_files_pending(int64_t *n_pending, int64_t *n_done);
 int hhx_files_join(int64_t *n_failed);
+
+/* ---------------------------------------------------------------- assembly correction (--correct_nrounds), haphic_amd/csrc/hhx_correct.hip
+ * Pass one — parse_pairs_for_correction :1300-1344 / parse_bam_for_correction :1362-1398.  hhx_correct_create: contig c (fa_dict order, ctg_len
+ * host) owns ctg_len[c] // resolution + 1 bins (:1311) of one flat int32 coverage array.  Positions and coverage are int32 as in the reference
+ * (array('i') :1308, ndarray int32 :1311): a contig of 2^31 - 1 bp or more is refused.  hhx_correct_push takes the four arrays the tokeniser
+ * (hhx_pairs_parser_arrays) and the BAM decoder (hhx_bam_next) leave on the device (or host arrays, on_device = 0): a record is kept iff
+ * id1 == id2 >= 0 (:1327-1332; BAM records that fail `flag.read1 && refid == mrefid` :1376 carry id -2 or two different ids); lo, hi = sorted(pos, mpos)
+ * :1337; coverage of bins lo // res .. hi // res += 1, clipped at the contig's last bin as the numpy slice :1341 is; (lo, hi) joins the contig's
+ * position list :1342 in file order.  A negative position fails the push.  hhx_correct_finalize: the position lists grouped by contig (stable),
+ * the coverage summed; *n_kept = kept records.
+ * The table: segment s = (first bin in the flat array, bins, length, pairs [pair_off[s], pair_off[s + 1])) — the contigs of the FASTA after
+ * finalize, the children of the broken contigs after hhx_correct_break.  hhx_correct_fetch_*: host copies (any pointer of _segments may be null);
+ * coverage = the whole flat array [n_bins of hhx_correct_shape], pairs = lo, hi interleaved [2 * n_pairs] in segment order.
+ * hhx_correct_detect — detect_break_points :943-1014 over every segment, arithmetic as the kernel's comment spells it out (numpy median, float64
+ * cut-offs): n_bp[s] break points in segment s (0: none) at coverage bp_cov[s] (0: the zero-coverage case, possibly several points; else one point),
+ * *n_total their sum; hhx_correct_fetch_break_points: their BINS (position = bin * resolution), segment order, ascending inside a segment.
+ * hhx_correct_break — the per-pair half of break_and_update_ctgs :1063-1113 and the coverage slices :1153 :1178 for the n_broken segments seg[]
+ * (ascending) with break POSITIONS bp_pos[bp_off[b] .. bp_off[b + 1]) (ascending multiples of the resolution inside the contig) and zero[b] bit 0 =
+ * the zero-coverage case (:1068), bit 1 = the contig is a piece that does not start its original contig (pos_shift :1050 then files the pairs of every child
+ * but the last under a name nothing reads again: they are dropped, as the reference loses them): pairs meeting [bp, bp + res] are dropped and their coverage taken back (non-zero case), the others move to the
+ * child holding both ends or are dropped when the ends part; child k of a contig is a view [start // res, point // res) of its parent's bins, the
+ * last child runs to the parent's last bin; the new table holds the children alone, in (parent, child) order (:1192-1197). */
+typedef struct hhx_correct hhx_correct;
+int hhx_correct_create(int32_t n_ctg, const int64_t *ctg_len, int32_t resolution, hhx_correct **out);
+int hhx_correct_push(hhx_correct *c, int64_t n, const int32_t *id1, const int32_t *pos1, const int32_t *id2, const int32_t *pos2, int on_device);
+int hhx_correct_finalize(hhx_correct *c, int64_t *n_kept);
+int hhx_correct_shape(hhx_correct *c, int32_t *n_seg, int64_t *n_bins, int64_t *n_pairs);
+int hhx_correct_fetch_segments(hhx_correct *c, int64_t *bin_off, int32_t *n_bins, int32_t *len, int64_t *pair_off);
+int hhx_correct_fetch_coverage(hhx_correct *c, int32_t *cov);
+int hhx_correct_fetch_pairs(hhx_correct *c, int32_t *lo_hi);
+int hhx_correct_detect(hhx_correct *c, double median_cov_ratio, double region_len_ratio, int64_t min_region_cutoff, int32_t *n_bp, int32_t *bp_cov,
+                       int64_t *n_total);
+int hhx_correct_fetch_break_points(hhx_correct *c, int32_t *bp_bin);
+int hhx_correct_break(hhx_correct *c, int32_t n_broken, const int32_t *seg, const int64_t *bp_off, const int32_t *bp_pos, const uint8_t *zero);
+int hhx_correct_destroy(hhx_correct *c);
+/* Pass two — convert_ctg :1405-1411 (and its copies :1447-1453 :1477-1483 :1516-1522) between a front end and hhx_ingest_push: source contig s
+ * (the names the tokeniser / BAM decoder was given) owns entries [off[s], off[s + 1]) of (break_pos ascending, new_id): (s, x) becomes
+ * (new_id, x - break_pos) of the entry with the largest break_pos <= x; an unbroken contig has the one entry (0, its id in the corrected FASTA); a
+ * source without entries, or x below its first entry, becomes id -1 (dropped by the ingest like any name outside fa_dict).  Negative ids pass
+ * through.  hhx_remap_apply works in place on one (id, position) column pair on the device, on the library's stream. */
+typedef struct hhx_remap hhx_remap;
+int hhx_remap_create(int32_t n_src, const int32_t *off, const int32_t *break_pos, const int32_t *new_id, hhx_remap **out);
+int hhx_remap_apply(hhx_remap *r, int64_t n, int32_t *dev_id, int32_t *dev_pos);
+int hhx_remap_destroy(hhx_remap *r);
 
 #ifdef __cplusplus
 }
