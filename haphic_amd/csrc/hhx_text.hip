@@ -18,7 +18,9 @@
 //      records at its offset (k_bed_write).
 // Whitespace is the ASCII subset of str.split()'s (\t \n \v \f \r \x1c-\x1f and space); int() takes an optional
 // sign, digits and single underscores between digits.  A line with fewer than five columns or a malformed integer
-// fails the call (the reference raises IndexError / ValueError there); positions must fit int32.
+// fails the call with what :1556 raises, evaluated left to right: IndexError without a second column, ValueError for a
+// malformed third, IndexError without a fourth or fifth, ValueError for a malformed fifth; the first such line of the
+// chunk is the one reported.  Positions must fit int32 (wide mode: literals up to 2^40).
 #include "hhx_common.h"
 
 using namespace hhx;
@@ -280,6 +282,7 @@ __device__ __forceinline__ bool parse_int(const RD &rd, const Tok &k, i64 *val, 
         }
     }
     if (!prev_digit) return false;
+    if (v > (1ll << 40)) big = true;
     v = neg ? -v : v;
     *range = big ? 2 : ((v - 1 > 2147483647ll || v - 1 < -2147483648ll) ? 1 : 0);
     *val = v;
@@ -324,7 +327,9 @@ __device__ __forceinline__ void parse_one(const RD &rd, i64 k, i64 a, i64 e, con
         i64 v1 = 0, v2 = 0;
         int r1 = 0, r2 = 0;
         const int limit = O.pos1w ? 1 : 0;                       // wide mode accepts what does not fit int32
-        if (nt < 5) atomicMin(O.err, ((unsigned long long)k << 8) | ERR_COLUMNS);
+        // in the order :1556 evaluates cols[1], int(cols[2]), cols[3], int(cols[4]): a malformed third column is a ValueError even when
+        // the fourth or fifth is missing; the range refusals are this path's own and come last
+        if (nt < 5) atomicMin(O.err, ((unsigned long long)k << 8) | (nt >= 3 && !parse_int(rd, tok[2], &v1, &r1) ? ERR_INT : ERR_COLUMNS));
         else if (!parse_int(rd, tok[2], &v1, &r1) || !parse_int(rd, tok[4], &v2, &r2)) atomicMin(O.err, ((unsigned long long)k << 8) | ERR_INT);
         else if (r1 > limit || r2 > limit) atomicMin(O.err, ((unsigned long long)k << 8) | ERR_RANGE);
         else {
@@ -372,7 +377,7 @@ __device__ __forceinline__ bool stage_lines(const unsigned char *__restrict__ t,
 }
 
 // STAGED = true: the blocks of 128 lines whose text fits the LDS window; the others (lines of kilobytes, or an
-// unaligned device buffer) only raise O.err[1] and are taken by a second launch with STAGED = false, which reads HBM
+// unaligned device buffer) are only counted in O.err[1] and are taken by a second launch with STAGED = false, which reads HBM
 // directly — so that the common kernel carries one reader, not two (registers, instruction cache).
 template <bool STAGED>
 __global__ __launch_bounds__(LN_BLOCK) void k_parse_lines(const unsigned char *__restrict__ t, i64 n, const i64 *__restrict__ starts, i64 n_lines,
@@ -385,7 +390,7 @@ __global__ __launch_bounds__(LN_BLOCK) void k_parse_lines(const unsigned char *_
         const bool fits = aligned && e0 - (a0 & ~(i64)15) <= IN_CAP;
         const i64 k = k0 + threadIdx.x;
         if (STAGED) {
-            if (!fits) { if (threadIdx.x == 0) atomicOr(&O.err[1], 1ull); continue; }
+            if (!fits) { if (threadIdx.x == 0) atomicAdd(&O.err[1], 1ull); continue; }
             i64 bias;
             (void)stage_lines(t, n, a0, e0, s_in, &bias);
             __syncthreads();
@@ -399,10 +404,12 @@ __global__ __launch_bounds__(LN_BLOCK) void k_parse_lines(const unsigned char *_
 }
 
 // BED records of a block of lines are formatted into LDS at (offset - out_bias), out_bias chosen so that LDS and
-// HBM addresses agree mod 16, then leave with 16-byte stores (bytes at the two ragged ends)
+// HBM addresses agree mod 16, then leave with 16-byte stores (bytes at the two ragged ends).  path_count (profiling
+// only, else nullptr): [0] blocks that took the LDS output path, [1] blocks that wrote HBM directly
 __global__ __launch_bounds__(LN_BLOCK) void k_bed_write(const unsigned char *__restrict__ t, i64 n, const i64 *__restrict__ starts, i64 n_lines,
                                                         const i32 *__restrict__ pos1, const i32 *__restrict__ pos2, const i64 *__restrict__ pos1w,
-                                                        const i64 *__restrict__ pos2w, const i64 *__restrict__ bed_off, unsigned char *__restrict__ bed) {
+                                                        const i64 *__restrict__ pos2w, const i64 *__restrict__ bed_off, unsigned char *__restrict__ bed,
+                                                        unsigned long long *__restrict__ path_count) {
     __shared__ __attribute__((aligned(16))) unsigned char s_in[IN_CAP + 16];
     __shared__ __attribute__((aligned(16))) unsigned char s_out[OUT_CAP];
     for (i64 k0 = (i64)blockIdx.x * LN_BLOCK; k0 < n_lines; k0 += (i64)gridDim.x * LN_BLOCK) {
@@ -414,6 +421,7 @@ __global__ __launch_bounds__(LN_BLOCK) void k_bed_write(const unsigned char *__r
         const bool staged = stage_lines(t, n, a0, e0, s_in, &bias);
         const i64 out_bias = b0 & ~(i64)15;                      // bed is 16-byte aligned (pool allocation)
         const bool out_staged = b1 - out_bias <= OUT_CAP;
+        if (path_count && threadIdx.x == 0) atomicAdd(&path_count[out_staged ? 0 : 1], 1ull);
         __syncthreads();
         const i64 k = k0 + threadIdx.x;
         if (k < k1 && bed_off[k + 1] > bed_off[k]) {
@@ -461,7 +469,7 @@ extern "C" int hhx_pairs_parser_create(i32 n_names, const uint8_t *names, const 
         sh[s] = h;
     }
     if (p->names.alloc(words.size()) || p->name_off.alloc(off.size()) || p->name_len.alloc(len.size()) || p->slot_hash.alloc(cap) ||
-        p->slot_id.alloc(cap) || p->err.alloc(2)) { delete p; return 1; }
+        p->slot_id.alloc(cap) || p->err.alloc(4)) { delete p; return 1; }
     hipError_t e = hipMemcpyAsync(p->names.p, words.data(), sizeof(u64) * words.size(), hipMemcpyHostToDevice, g_stream);
     if (e == hipSuccess) e = hipMemcpyAsync(p->name_off.p, off.data(), sizeof(i64) * off.size(), hipMemcpyHostToDevice, g_stream);
     if (e == hipSuccess) e = hipMemcpyAsync(p->name_len.p, len.data(), sizeof(i32) * len.size(), hipMemcpyHostToDevice, g_stream);
@@ -513,7 +521,7 @@ extern "C" int hhx_pairs_parse(hhx_pairs_parser *p, const uint8_t *text, i64 n_b
     if (p->wide && std::min(p->pos1w.n, p->pos2w.n) < (size_t)nl && (p->pos1w.alloc((size_t)nl) || p->pos2w.alloc((size_t)nl))) return 1;
     DevBuf<i64> bed_len;
     if (want_bed && bed_len.alloc((size_t)nl)) return 1;
-    HHX_HIP(hipMemsetAsync(p->err.p, 0xff, sizeof(unsigned long long), g_stream));      // [0] first error (min), [1] unstaged blocks seen
+    HHX_HIP(hipMemsetAsync(p->err.p, 0xff, sizeof(unsigned long long), g_stream));      // [0] first error (min), [1] blocks that did not stage, [2] [3] BED blocks by output path (profiling)
     HHX_HIP(hipMemsetAsync(p->err.p + 1, 0, sizeof(unsigned long long), g_stream));
     const NameTable T{p->names.p, p->name_off.p, p->name_len.p, p->slot_hash.p, p->slot_id.p, p->mask};
     const LineOut O{p->id1.p, p->pos1.p, p->id2.p, p->pos2.p, want_bed ? bed_len.p : nullptr, p->err.p, p->wide ? p->pos1w.p : nullptr,
@@ -529,6 +537,10 @@ extern "C" int hhx_pairs_parse(hhx_pairs_parser *p, const uint8_t *text, i64 n_b
         HHX_LAUNCH_CHECK();
         HHX_HIP(hipMemcpyAsync(errw, p->err.p, sizeof errw, hipMemcpyDeviceToHost, g_stream));
         HHX_HIP(hipStreamSynchronize(g_stream));
+    }
+    if (prof_enabled()) {
+        prof_count("text_blocks_direct", (i64)errw[1]);
+        prof_count("text_blocks_staged", (nl + LN_BLOCK - 1) / LN_BLOCK - (i64)errw[1]);
     }
     const unsigned long long err = errw[0];
     if (err != ~0ull) {
@@ -548,10 +560,19 @@ extern "C" int hhx_pairs_parse(hhx_pairs_parser *p, const uint8_t *text, i64 n_b
         unsigned char *dst = nullptr;
         if (p->sink) { void *room = nullptr; HHX_TRY(hhx_byte_sink_reserve(p->sink, total + 16, &room)); dst = (unsigned char *)room; }
         else { if (p->bed.n < (size_t)total + 16 && p->bed.alloc((size_t)total + 16)) return 1; dst = p->bed.p; }
+        const bool counted = prof_enabled();                     // which output path the blocks take: counted on the device, read back only here
+        if (counted) HHX_HIP(hipMemsetAsync(p->err.p + 2, 0, 2 * sizeof(unsigned long long), g_stream));
         { KTimer kt("text_bed");
         k_bed_write<<<grid_for(nl, LN_BLOCK), LN_BLOCK, 0, g_stream>>>(t, n_bytes, p->starts.p, nl, p->pos1.p, p->pos2.p, p->wide ? p->pos1w.p : nullptr,
-                                                                          p->wide ? p->pos2w.p : nullptr, p->bed_off.p, dst); }
+                                                                          p->wide ? p->pos2w.p : nullptr, p->bed_off.p, dst, counted ? p->err.p + 2 : nullptr); }
         HHX_LAUNCH_CHECK();
+        if (counted) {
+            unsigned long long paths[2] = {0, 0};
+            HHX_HIP(hipMemcpyAsync(paths, p->err.p + 2, sizeof paths, hipMemcpyDeviceToHost, g_stream));
+            HHX_HIP(hipStreamSynchronize(g_stream));
+            prof_count("bed_blocks_lds", (i64)paths[0]);
+            prof_count("bed_blocks_direct", (i64)paths[1]);
+        }
         if (p->sink) HHX_TRY(hhx_byte_sink_commit(p->sink, dst, total));
         p->bed_bytes = total;
         if (bed_bytes) *bed_bytes = total;

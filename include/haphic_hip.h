@@ -76,7 +76,10 @@ int hhx_profile_get(const char *kernel, double *total_ms, int64_t *launches);
  * "ingest_records" (read pairs that survive the map stage); per fused expansion, the rows k_classify puts in each class —
  * "expand_rows_window", "expand_rows_compact", "expand_rows_tiny", "expand_rows_hash" — the hash-class rows the hash kernel hands
  * back ("expand_rows_hash_to_window", "expand_rows_hash_to_compact"), the column windows of the window-class launch
- * ("expand_window_n_win") and the survivor-pool retries ("expand_pool_retries") */
+ * ("expand_window_n_win") and the survivor-pool retries ("expand_pool_retries"); per hhx_pairs_parse, the blocks of 128 lines whose
+ * text was staged in LDS / read from HBM directly ("text_blocks_staged", "text_blocks_direct": a span beyond the LDS window, or a
+ * device buffer that is not 16-byte aligned) and, of the blocks that write alignments.bed bytes, those formatted in LDS / straight
+ * into HBM ("bed_blocks_lds", "bed_blocks_direct") */
 int hhx_profile_counter(const char *name, int64_t *value);
 
 /* ---------------------------------------------------------------- matrices */
@@ -360,7 +363,10 @@ int hhx_shard_destroy(hhx_shard *s);
  * (n_names strings, concatenated, name_off[n_names + 1]); a name that is not among them, and every skipped
  * line, yields id -1 — which hhx_ingest_push drops (:1610 / :1702) — so line k of the chunk is element k of
  * the arrays.  A chunk must hold whole lines.  A line with fewer than 5 columns or a malformed integer fails
- * the call with "IndexError: ..." / "ValueError: ..." in hhx_last_error(), as the reference raises.  The
+ * the call with "IndexError: ..." / "ValueError: ..." in hhx_last_error(), as the reference raises, :1556 evaluated
+ * left to right (no second column: IndexError; malformed third: ValueError; no fourth or fifth: IndexError;
+ * malformed fifth: ValueError), for the first such line of the chunk.  This path's own refusals come after those: a
+ * position outside int32 (wide mode: a literal beyond 2^40 in magnitude) is a "ValueError: ...".  The
  * arrays (device pointers, int32) stay valid until the next parse on the same parser. */
 typedef struct hhx_pairs_parser hhx_pairs_parser;
 int hhx_pairs_parser_create(int32_t n_names, const uint8_t *names, const int64_t *name_off, hhx_pairs_parser **out);
