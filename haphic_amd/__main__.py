@@ -14,7 +14,8 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
-                             byte-identical to the one-rank run.  Under torchrun (RANK / WORLD_SIZE set) its ranks are used instead.
+                             byte-identical to the one-rank run; with --correct_nrounds both correction passes over a .pairs file are shared
+                             across the ranks too.  Under torchrun (RANK / WORLD_SIZE set) its ranks are used instead.
   --host-transport           with --gpus: gloo through host memory instead of RCCL, for ranks that share a device (the default when N
                              exceeds the number of devices)
 """

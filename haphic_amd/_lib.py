@@ -161,6 +161,8 @@ SIGNATURES = {
     'hhx_correct_create': (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, c_vpp]),
     'hhx_correct_push': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     'hhx_correct_finalize': (C.c_int, [C.c_void_p, c_i64p]),
+    'hhx_correct_export': (C.c_int, [C.c_void_p, c_i32p, c_i64p, c_i64p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
+    'hhx_correct_absorb': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]),
     'hhx_correct_shape': (C.c_int, [C.c_void_p, c_i32p, c_i64p, c_i64p]),
     'hhx_correct_fetch_segments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_correct_fetch_coverage': (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1127,6 +1129,50 @@ class CorrectTable:
         n = C.c_int64(0)
         check(load().hhx_correct_finalize(self.h, C.byref(n)))
         return n.value
+
+    def export_shape(self):
+        """(resolution, bins, kept records) of a table that is not finalized"""
+        r, b, p = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        check(load().hhx_correct_export(self.h, C.byref(r), C.byref(b), C.byref(p), None, 0, 0, None, None, 0))
+        return r.value, b.value, p.value
+
+    def export_diff(self):
+        """host copy of the coverage difference array of a table that is not finalized"""
+        diff = np.empty(self.export_shape()[1], np.int32)
+        check(load().hhx_correct_export(self.h, None, None, None, ptr(diff) if diff.size else None, 0, 0, None, None, 0))
+        return diff
+
+    def export_pairs(self, first, count):
+        """-> (pair_ctg int32 [count], pair_lo_hi int32 [2 count]): host copies of the kept records [first, first + count) in push order"""
+        ctg, lo_hi = np.empty(count, np.int32), np.empty(2 * count, np.int32)
+        if count:
+            check(load().hhx_correct_export(self.h, None, None, None, None, int(first), int(count), ptr(ctg), ptr(lo_hi), 0))
+        return ctg, lo_hi
+
+    def export(self):
+        """-> (resolution, cov_diff, pair_ctg, pair_lo_hi) of the whole table; absorb(*other.export()) adds them to another table"""
+        res, _bins, n = self.export_shape()
+        return (res, self.export_diff()) + self.export_pairs(0, n)
+
+    def export_device(self, diff_ptr, first, count, ctg_ptr, lo_hi_ptr):
+        """the same into device arrays (a null pointer: that part is left out)"""
+        check(load().hhx_correct_export(self.h, None, None, None, C.c_void_p(diff_ptr), int(first), int(count), C.c_void_p(ctg_ptr),
+                                        C.c_void_p(lo_hi_ptr), 1))
+
+    def absorb(self, resolution, cov_diff, pair_ctg, pair_lo_hi):
+        """add a piece of a partial table (host arrays) to this one, its records behind those kept so far.  cov_diff None: records alone (the
+        difference array came with an earlier piece)"""
+        n_bins = self.export_shape()[1] if cov_diff is None else len(cov_diff)
+        diff = None if cov_diff is None else np.ascontiguousarray(cov_diff, np.int32)
+        ctg, lo_hi = (np.ascontiguousarray(a, np.int32) for a in (pair_ctg, pair_lo_hi))
+        if lo_hi.size != 2 * ctg.size:
+            raise ValueError('CorrectTable.absorb: {} contig ids, {} positions'.format(ctg.size, lo_hi.size))
+        check(load().hhx_correct_absorb(self.h, int(resolution), n_bins, ptr(diff) if diff is not None and diff.size else None, ctg.size,
+                                        ptr(ctg) if ctg.size else None, ptr(lo_hi) if ctg.size else None, 0))
+
+    def absorb_device(self, resolution, n_bins, diff_ptr, n_pairs, ctg_ptr, lo_hi_ptr):
+        check(load().hhx_correct_absorb(self.h, int(resolution), int(n_bins), C.c_void_p(diff_ptr), int(n_pairs), C.c_void_p(ctg_ptr),
+                                        C.c_void_p(lo_hi_ptr), 1))
 
     def shape(self):
         """(segments, bins of the flat coverage array, pairs)"""

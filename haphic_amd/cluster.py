@@ -1335,8 +1335,11 @@ def _ingest_handle(alignments, table, flank, bins, chunk=1 << 22, want_pairs=Fal
             ranked = alignments.multi_rank()
             if ranked:                       # the other ranks tokenise their byte ranges of the file meanwhile (ranks.py, phase `ingest`)
                 from . import ranks
-                ranks.announce('ingest', ranks.ingest_spec(alignments, table.ctg_names, table.wide))
+                ranks.announce('ingest', ranks.ingest_spec(alignments, src_names, table.wide))
+                t_ranked = time.perf_counter()
+            n_lines = 0
             for parser, k in alignments.batches(src_names, wide=table.wide):
+                n_lines += k
                 if k:
                     ptrs = parser.device_arrays()[:4]
                     if remap is not None:            # convert_ctg :1405-1411 on both ends; alignments.bed was formatted from the text before
@@ -1345,6 +1348,7 @@ def _ingest_handle(alignments, table, flank, bins, chunk=1 << 22, want_pairs=Fal
                     ing.push_device(k, *ptrs, wide=table.wide)
             if ranked:
                 ranks.gather_into(ing, table.wide)      # their pairs behind rank 0's, in rank order: the file's order
+                ranks.record('ingest', n_lines, None, time.perf_counter() - t_ranked)
         elif bam:                            # f4: BGZF inflate on host threads, record decode on the device
             for _reader, k, ptrs in alignments.batches(src_names):
                 if remap is not None:

@@ -131,28 +131,34 @@ def _frozen_session(*containers):
 
 
 # ------------------------------------------------------------------ pass one
-class _WholeFileText(cluster.PairsText):
-    """a .pairs file read whole by the calling rank: the correction passes are not shared out across the ranks of a --gpus N job"""
-
-    def multi_rank(self):
-        return False
-
-
 def _new_table(fa_dict, args):
     names = list(fa_dict)
     return names, _lib.CorrectTable([fa_dict[c][1] for c in names], args.correct_resolution)
 
 
 def parse_pairs_for_correction(fa_dict, args):
-    """parse_pairs_for_correction() :1300-1344"""
+    """parse_pairs_for_correction() :1300-1344.  In a --gpus N job over a plain or BGZF file every rank fills a table from the lines of its
+    own byte range (ranks.py, phase `correct_pass1`); this rank absorbs them in rank order — file order — before it finalizes.  A plain gzip
+    stream is read whole by this rank, as for the ingest."""
+    import time
     logger.info('Parsing input pairs file for contig correction...')
     assert args.aln_format in ('pairs', 'bgzipped_pairs')
     names, table = _new_table(fa_dict, args)
     try:
-        text = _WholeFileText(args.alignments, args.aln_format, inter_only=False, bed_path=None)
-        for parser, k in text.batches(names):
-            if k:
-                table.push_device(k, *parser.device_arrays()[:4])
+        text = cluster.PairsText(args.alignments, args.aln_format, inter_only=False, bed_path=None)
+        ranked = text.multi_rank()
+        if ranked:
+            from . import ranks
+            ranks.announce('correct_pass1', ranks.correct_spec(text, names, [fa_dict[c][1] for c in names], args.correct_resolution))
+            t0 = time.perf_counter()
+            lines = ranks.fill_table(table, text, names)
+            kept = table.export_shape()[2]
+            ranks.gather_tables(table)
+            ranks.record('correct_pass1', lines, kept, time.perf_counter() - t0)
+        else:
+            for parser, k in text.batches(names):
+                if k:
+                    table.push_device(k, *parser.device_arrays()[:4])
         table.finalize()
     except BaseException:
         table.destroy()
@@ -308,13 +314,14 @@ class _Remapped:
 
     def remap_for(self, corrected_names):
         sources, off, pos, new = _remap_tables(corrected_names, self._break_pos, self._break_frag)
+        self.remap_tables = (off, pos, new)                      # what a multi-rank ingest broadcasts (ranks.ingest_spec)
         return sources, _lib.ContigRemap(off, pos, new)
-
-    def multi_rank(self):
-        return False
 
 
 class CorrectedPairsText(_Remapped, cluster.PairsText):
+    """multi_rank() is PairsText's: in a --gpus N job every rank tokenises the ORIGINAL names of its byte range, converts on its own device and
+    sends its pairs in rank order; each writes its share of alignments.bed with the original names"""
+
     def __init__(self, pairs, aln_format, inter_only, final_break_pos_dict, final_break_frag_dict):
         cluster.PairsText.__init__(self, pairs, aln_format, inter_only)
         self._set_remap(final_break_pos_dict, final_break_frag_dict)
@@ -327,6 +334,9 @@ class CorrectedBamRecords(_Remapped, cluster.BamRecords):
             raise NotImplementedError('refid != mrefid is tested after the contig conversion (:1467), not by the BAM filter')
         self.inter_only = inter_only
         self._set_remap(final_break_pos_dict, final_break_frag_dict)
+
+    def multi_rank(self):
+        return False                                             # BAM input is read by rank 0 alone
 
 
 def pairs_generator_for_correction(pairs, aln_format, final_break_pos_dict, final_break_frag_dict):

@@ -140,6 +140,38 @@ __global__ __launch_bounds__(CR_T) void k_cov_compact(i64 n, const i32 *__restri
         }
 }
 
+// A table that is not finalized yet, handed to another one (the ranks of a --gpus N job each fill a table from their byte range of the file):
+// k_export_pairs narrows the kept records of one push to (contig, lo, hi) int32 columns; k_absorb_diff adds a partial difference array
+// (difference arrays of disjoint record sets add); k_absorb_pairs appends records behind those already kept, counted per contig as k_cov_push
+// counts them.  A record no push could have kept (contig outside the table, lo < 0, lo > hi) raises `bad` and is not counted; the caller then
+// drops the whole chunk.
+__global__ __launch_bounds__(CR_T) void k_export_pairs(i64 n, const u64 *__restrict__ key, const u64 *__restrict__ val, i32 *__restrict__ ctg,
+                                                       i32 *__restrict__ lo_hi) {
+    for (i64 k = (i64)blockIdx.x * CR_T + threadIdx.x; k < n; k += (i64)gridDim.x * CR_T) {
+        const u64 v = val[k];
+        ctg[k] = (i32)(u32)key[k];
+        lo_hi[2 * k] = (i32)(u32)v;
+        lo_hi[2 * k + 1] = (i32)(u32)(v >> 32);
+    }
+}
+
+__global__ __launch_bounds__(CR_T) void k_absorb_diff(i64 n, const i32 *__restrict__ part, i32 *__restrict__ diff) {
+    for (i64 k = (i64)blockIdx.x * CR_T + threadIdx.x; k < n; k += (i64)gridDim.x * CR_T) diff[k] += part[k];
+}
+
+__global__ __launch_bounds__(CR_T) void k_absorb_pairs(i64 n, const i32 *__restrict__ ctg, const i32 *__restrict__ lo_hi, i32 n_ctg,
+                                                       u64 *__restrict__ key, u64 *__restrict__ val, unsigned long long *__restrict__ cnt,
+                                                       i32 *__restrict__ bad) {
+    for (i64 k = (i64)blockIdx.x * CR_T + threadIdx.x; k < n; k += (i64)gridDim.x * CR_T) {
+        const i32 a = ctg[k], lo = lo_hi[2 * k], hi = lo_hi[2 * k + 1];
+        const bool ok = a >= 0 && a < n_ctg && lo >= 0 && lo <= hi;
+        key[k] = (u64)(u32)(ok ? a : 0);
+        val[k] = ((u64)(u32)hi << 32) | (u64)(u32)lo;
+        if (ok) atomicAdd(&cnt[a], 1ull);
+        else *bad = 1;                                            // same value from every writer
+    }
+}
+
 // cov[seg] += inclusive scan of diff[seg]; diff[seg] = 0.  One wave per segment (the typical contig has a few dozen bins).
 __global__ __launch_bounds__(HHX_WAVE) void k_apply_diff(i32 n, const i64 *__restrict__ off_of, const i32 *__restrict__ nb_of, i32 *__restrict__ diff,
                                                          i32 *__restrict__ cov) {
@@ -414,6 +446,95 @@ extern "C" int hhx_correct_push(hhx_correct *c, i64 n, const i32 *id1, const i32
     }
     HHX_HIP(hipStreamSynchronize(g_stream));                       // the staging buffers of a host push go back to the pool here
     prof_count("correct_records", n);
+    return 0;
+}
+
+extern "C" int hhx_correct_export(hhx_correct *c, i32 *resolution, i64 *n_bins, i64 *n_pairs, i32 *cov_diff, i64 pair_first, i64 pair_count,
+                                  i32 *pair_ctg, i32 *pair_lo_hi, int on_device) {
+    if (!c) return fail("null handle");
+    if (c->finalized) return fail("hhx_correct_export: the table is finalized (its difference array is spent)");
+    i64 total = 0;
+    for (i64 k : c->chunk_n) total += k;
+    if (resolution) *resolution = c->res;
+    if (n_bins) *n_bins = c->total_bins;
+    if (n_pairs) *n_pairs = total;
+    if ((pair_ctg == nullptr) != (pair_lo_hi == nullptr)) return fail("hhx_correct_export: the pair columns come together");
+    if (pair_ctg && (pair_first < 0 || pair_count < 0 || pair_first > total || pair_count > total - pair_first))
+        return fail("hhx_correct_export: records [%lld, %lld + %lld) of %lld", (long long)pair_first, (long long)pair_first, (long long)pair_count,
+                    (long long)total);
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (cov_diff && c->total_bins) HHX_HIP(hipMemcpyAsync(cov_diff, c->diff.p, sizeof(i32) * (size_t)c->total_bins, kind, g_stream));
+    DevBuf<i32> d_ctg, d_lh;                                       // staging of a host call: back to the pool behind the copies
+    if (pair_ctg && pair_count) {
+        i32 *ctg = pair_ctg, *lh = pair_lo_hi;
+        if (!on_device) {
+            if (d_ctg.alloc((size_t)pair_count) || d_lh.alloc(2 * (size_t)pair_count)) return 1;
+            ctg = d_ctg.p; lh = d_lh.p;
+        }
+        const i64 end = pair_first + pair_count;
+        i64 begin = 0, at = 0;                                     // begin: first record of chunk k in push order; at: records written
+        for (size_t k = 0; k < c->chunk_n.size() && begin < end; begin += c->chunk_n[k], ++k) {
+            const i64 lo = std::max(begin, pair_first), hi = std::min(begin + c->chunk_n[k], end);
+            if (hi <= lo) continue;
+            k_export_pairs<<<grid_for(hi - lo, CR_T), CR_T, 0, g_stream>>>(hi - lo, c->chunk_key[k].p + (lo - begin), c->chunk_val[k].p + (lo - begin),
+                                                                          ctg + at, lh + 2 * at);
+            HHX_LAUNCH_CHECK();
+            at += hi - lo;
+        }
+        if (!on_device) {
+            HHX_HIP(hipMemcpyAsync(pair_ctg, ctg, sizeof(i32) * (size_t)pair_count, hipMemcpyDeviceToHost, g_stream));
+            HHX_HIP(hipMemcpyAsync(pair_lo_hi, lh, sizeof(i32) * 2 * (size_t)pair_count, hipMemcpyDeviceToHost, g_stream));
+        }
+    }
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+extern "C" int hhx_correct_absorb(hhx_correct *c, i32 resolution, i64 n_bins, const i32 *cov_diff, i64 n_pairs, const i32 *pair_ctg,
+                                  const i32 *pair_lo_hi, int on_device) {
+    if (!c) return fail("null handle");
+    if (c->finalized) return fail("hhx_correct_absorb: the table is finalized");
+    if (resolution != c->res) return fail("hhx_correct_absorb: a table of resolution %d into one of resolution %d", resolution, c->res);
+    if (n_bins != c->total_bins) return fail("hhx_correct_absorb: a table of %lld bins into one of %lld", (long long)n_bins, (long long)c->total_bins);
+    if (n_pairs < 0 || n_pairs > (i64)INT32_MAX) return fail("hhx_correct_absorb: %lld pair records", (long long)n_pairs);
+    if (n_pairs && (!pair_ctg || !pair_lo_hi)) return fail("null pointer");
+    const bool with_diff = cov_diff != nullptr && n_bins > 0;      // null: a further piece of a table whose difference array came with an earlier one
+    DevBuf<i32> d_diff, d_ctg, d_lh;
+    if (!on_device) {
+        if (with_diff) {
+            HHX_TRY(upload(d_diff, cov_diff, (size_t)n_bins));
+            cov_diff = d_diff.p;
+        }
+        if (n_pairs) {
+            HHX_TRY(upload(d_ctg, pair_ctg, (size_t)n_pairs));
+            HHX_TRY(upload(d_lh, pair_lo_hi, 2 * (size_t)n_pairs));
+            pair_ctg = d_ctg.p; pair_lo_hi = d_lh.p;
+        }
+    }
+    if (n_pairs) {                                                 // the same growth as a push: one more chunk behind those kept so far
+        DevBuf<u64> key, val;
+        if (key.alloc((size_t)n_pairs) || val.alloc((size_t)n_pairs)) return 1;
+        {
+            KTimer kt("correct_absorb");
+            k_absorb_pairs<<<grid_for(n_pairs, CR_T), CR_T, 0, g_stream>>>(n_pairs, pair_ctg, pair_lo_hi, (i32)c->seg_off.size(), key.p, val.p,
+                                                                          c->cnt.p, c->bad.p);
+        }
+        HHX_LAUNCH_CHECK();
+        i32 bad = 0;
+        HHX_HIP(hipMemcpyAsync(&bad, c->bad.p, sizeof bad, hipMemcpyDeviceToHost, g_stream));
+        HHX_HIP(hipStreamSynchronize(g_stream));
+        if (bad) return fail("hhx_correct_absorb: a record no push keeps (contig outside the table, or not 0 <= lo <= hi); the table cannot be finalized any more");
+        c->chunk_key.push_back(std::move(key));
+        c->chunk_val.push_back(std::move(val));
+        c->chunk_n.push_back(n_pairs);
+    }
+    if (with_diff) {
+        KTimer kt("correct_absorb");
+        k_absorb_diff<<<grid_for(n_bins, CR_T), CR_T, 0, g_stream>>>(n_bins, cov_diff, c->diff.p);
+        HHX_LAUNCH_CHECK();
+    }
+    HHX_HIP(hipStreamSynchronize(g_stream));                       // the caller's arrays (and the staging buffers of a host call) are free again
+    prof_count("correct_absorbed_pairs", n_pairs);
     return 0;
 }
 

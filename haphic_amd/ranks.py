@@ -3,18 +3,29 @@
 Rank 0 drives: it runs the reference's run() with the seams patched, exactly as a one-rank job does, and writes every file and log line.
 Ranks > 0 serve: serve() joins the collective phases rank 0 announces with a small broadcast —
 
+  correct_pass1  (from correct.parse_pairs_for_correction, --correct_nrounds): every rank tokenises the lines of its own byte range into a
+          correction table of its own (_lib.CorrectTable: coverage difference array + kept intra-contig pairs in file order, no BED output);
+          ranks > 0 export theirs and send it, rank 0 absorbs them IN RANK ORDER (hhx_correct_absorb) and finalizes: the table of one pass over
+          the whole file, bit for bit.  Detection, breaking and the bookkeeping stay on rank 0 (O(contigs), on its device).
   ingest  (from the .pairs mirrors, cluster._ingest_handle): every rank reads the lines of its own byte range of the file (owned_range) and
           tokenises them on its device; rank 0 pushes its own chunks into its ingest handle as it parses them, then the other ranks' id /
           position arrays IN RANK ORDER.  The handle so sees the file's pairs in file order, as the one-rank run does: HT order, CLM lists,
           coordinates and ctg_pair_to_frag come out the same, and the writers run unchanged on rank 0.  Every rank writes its own BED records
           into alignments.bed at the offset of the ranks before it (a deferred byte sink, placed once the BED sizes are all-gathered).
+          After a correction (correct.CorrectedPairsText) the spec carries the contig remap tables as well: every rank tokenises the ORIGINAL
+          names, builds its own _lib.ContigRemap and converts both ends of every batch on its device (convert_ctg :1405-1411) before it sends;
+          the intra-contig drop after the conversion (:1437) is the one of rank 0's ingest handle, applied once to the whole stream.
   sweep   (from run_mcl_clustering): rank 0 broadcasts the link matrix and the sweep parameters, every rank runs sharded.sweep_sharded, rank 0
           writes inflation_*/.
   done / abort
 
+BAM and plain-gzip input have no byte ranges to share out: rank 0 reads them alone in every phase.  HAPHIC_RANKS_RECORD=DIR makes every rank
+write DIR/rank<r>.json when it ends: per phase the lines it parsed, the pairs it kept, its seconds and the bytes it sent to rank 0.
+
 The transport is RCCL (device to device) with one device per rank, or gloo with HostStagedCollectives (host_transport.py) when ranks share a
 device (--host-transport; the default when there are more ranks than devices)."""
 import datetime
+import json
 import os
 import subprocess
 import time
@@ -33,6 +44,33 @@ class Context:
 
 def current():
     return _CTX
+
+
+# ------------------------------------------------------------------ the per-rank record
+RECORD = []                              # this rank's share of every phase it took part in, in order
+
+
+def record(phase, lines, pairs, seconds, bytes_sent=0):
+    RECORD.append({'phase': phase, 'lines': int(lines), 'pairs': None if pairs is None else int(pairs), 'seconds': float(seconds),
+                   'bytes_sent': int(bytes_sent)})
+
+
+def write_record(rank):
+    where = os.environ.get('HAPHIC_RANKS_RECORD')
+    if where:
+        with open(os.path.join(where, 'rank{}.json'.format(rank)), 'w') as f:
+            json.dump({'rank': rank, 'world': _CTX.world if _CTX is not None else 1, 'phases': RECORD}, f)
+
+
+def _dev():
+    """the torch device of this rank's tensors (a context without a device, as the host-side tests make one, keeps them in host memory)"""
+    return 'cpu' if _CTX.device is None else 'cuda:%d' % _CTX.device
+
+
+def _torch_sync():
+    if _CTX.device is not None:
+        import torch
+        torch.cuda.synchronize()
 
 
 def active():
@@ -197,6 +235,8 @@ def serve():
         phase, payload = _broadcast(None)
         if phase == 'ingest':
             _ingest_worker(payload)
+        elif phase == 'correct_pass1':
+            _correct_pass1_worker(payload)
         elif phase == 'sweep':
             _sweep_worker(payload)
         elif phase == 'done':
@@ -212,11 +252,111 @@ def serve():
             raise RuntimeError('haphic_amd.ranks: unknown phase {!r}'.format(phase))
 
 
+# ---- correct_pass1
+def correct_spec(text, names, lens, resolution):
+    """what rank 0 broadcasts for pass one of the assembly correction over a PairsText"""
+    return {'path': os.path.abspath(text.path), 'format': text.aln_format, 'names': list(names), 'lens': [int(x) for x in lens],
+            'resolution': int(resolution), 'chunk_bytes': int(text.chunk_bytes)}
+
+
+def fill_table(table, text, names):
+    """this rank's lines of `text` pushed into `table`; returns the number of lines"""
+    lines = 0
+    for parser, k in text.batches(names):
+        lines += k
+        if k:
+            table.push_device(k, *parser.device_arrays()[:4])
+    return lines
+
+
+TABLE_PIECE = int(os.environ.get('HAPHIC_TABLE_PIECE', str(1 << 26)))     # kept pairs per message of a correction table (12 bytes each)
+
+
+def _pieces(n):
+    return [(lo, min(TABLE_PIECE, n - lo)) for lo in range(0, n, max(TABLE_PIECE, 1))]
+
+
+def _send_table(table):
+    """ranks > 0: the shapes all-gathered, then this rank's table in int32 messages — the difference array, then the kept pairs TABLE_PIECE at a
+    time as [contig ids | lo, hi interleaved], so that neither a message nor rank 0's staging grows with the table; returns (kept pairs, bytes sent)"""
+    import numpy as np
+    import torch
+    res, n_bins, n = table.export_shape()
+    shapes = [None] * _CTX.world
+    _CTX.dist.all_gather_object(shapes, (res, n_bins, n))
+    host = _CTX.host_transport               # the wire is host memory anyway: host copies straight from the library
+    if n_bins:
+        if host:
+            _CTX.raw.send(torch.from_numpy(table.export_diff()), 0)
+        else:
+            blob = torch.empty(n_bins, dtype=torch.int32, device=_dev())
+            table.export_device(blob.data_ptr(), 0, 0, 0, 0)
+            _CTX.dist.send(blob, 0)
+    for first, m in _pieces(n):
+        if host:
+            _CTX.raw.send(torch.from_numpy(np.concatenate(table.export_pairs(first, m))), 0)
+        else:
+            blob = torch.empty(3 * m, dtype=torch.int32, device=_dev())
+            table.export_device(0, first, m, blob.data_ptr(), blob.data_ptr() + 4 * m)
+            _CTX.dist.send(blob, 0)
+    return n, 4 * (n_bins + 3 * n)
+
+
+def gather_tables(table):
+    """rank 0, after its own lines: the other ranks' tables absorbed in rank order, which is file order, piece by piece as _send_table sends them"""
+    import torch
+    res, n_bins, _n = table.export_shape()
+    shapes = [None] * _CTX.world
+    _CTX.dist.all_gather_object(shapes, (res, n_bins, 0))
+    host = _CTX.host_transport
+
+    def receive(count, r):
+        blob = torch.empty(count, dtype=torch.int32, device='cpu' if host else _dev())
+        (_CTX.raw if host else _CTX.dist).recv(blob, r)
+        if not host:
+            _torch_sync()
+        return blob
+
+    for r in range(1, _CTX.world):
+        res_r, nb_r, n_r = shapes[r]
+        if nb_r:
+            blob = receive(nb_r, r)
+            if host:
+                table.absorb(res_r, blob.numpy(), [], [])
+            else:
+                table.absorb_device(res_r, nb_r, blob.data_ptr(), 0, 0, 0)          # returns once it has read the tensor
+        elif (res_r, nb_r) != (res, n_bins):
+            raise RuntimeError('haphic_amd.ranks: rank {} built a correction table of another shape'.format(r))
+        for _first, m in _pieces(n_r):
+            blob = receive(3 * m, r)
+            if host:
+                a = blob.numpy()
+                table.absorb(res_r, None, a[:m], a[m:])
+            else:
+                table.absorb_device(res_r, nb_r, 0, m, blob.data_ptr(), blob.data_ptr() + 4 * m)
+
+
+def _correct_pass1_worker(spec):
+    from . import _lib, cluster
+    t0 = time.perf_counter()
+    table = _lib.CorrectTable(spec['lens'], spec['resolution'])
+    try:
+        text = cluster.PairsText(spec['path'], spec['format'], False, chunk_bytes=spec['chunk_bytes'], bed_path=None)
+        lines = fill_table(table, text, spec['names'])
+        kept, sent = _send_table(table)
+    finally:
+        table.destroy()
+    record('correct_pass1', lines, kept, time.perf_counter() - t0, sent)
+
+
 # ---- ingest
 def ingest_spec(text, names, wide):
-    """what rank 0 broadcasts for the ingest phase of a PairsText"""
+    """what rank 0 broadcasts for the ingest phase of a PairsText: `names` are the names to tokenise — after a correction the ORIGINAL contigs
+    (the sources of correct._remap_tables), with the remap tables (off, break_pos, new_id) every rank builds its _lib.ContigRemap from"""
+    remap = getattr(text, 'remap_tables', None)
     return {'path': os.path.abspath(text.path), 'format': text.aln_format, 'inter_only': bool(text.inter_only), 'names': list(names),
-            'wide': bool(wide), 'bed_path': os.path.abspath(text.bed_path) if text.bed_path else None, 'chunk_bytes': int(text.chunk_bytes)}
+            'wide': bool(wide), 'bed_path': os.path.abspath(text.bed_path) if text.bed_path else None, 'chunk_bytes': int(text.chunk_bytes),
+            'remap': None if remap is None else tuple(a.tolist() for a in remap)}
 
 
 def bed_bases(my_bytes):
@@ -245,15 +385,30 @@ def _take(parser, k, wide):
 
 def _ingest_worker(spec):
     import torch
-    from . import cluster
+    from . import _lib, cluster
+    t0 = time.perf_counter()
     text = cluster.PairsText(spec['path'], spec['format'], spec['inter_only'], chunk_bytes=spec['chunk_bytes'], bed_path=spec['bed_path'])
-    parts = [_take(parser, k, spec['wide']) for parser, k in text.batches(spec['names'], wide=spec['wide']) if k]
-    mine = torch.cat(parts, 1) if parts else torch.empty((4, 0), dtype=torch.int64 if spec['wide'] else torch.int32, device='cuda:%d' % _CTX.device)
+    remap = _lib.ContigRemap(*spec['remap']) if spec.get('remap') else None
+    parts, lines = [], 0
+    try:
+        for parser, k in text.batches(spec['names'], wide=spec['wide']):
+            lines += k
+            if k:
+                if remap is not None:        # convert_ctg :1405-1411 on both ends, on this rank's device; the BED bytes were formatted before
+                    ptrs = parser.device_arrays()
+                    remap.apply(k, ptrs[0], ptrs[1])
+                    remap.apply(k, ptrs[2], ptrs[3])
+                parts.append(_take(parser, k, spec['wide']))
+    finally:
+        if remap is not None:
+            remap.destroy()
+    mine = torch.cat(parts, 1) if parts else torch.empty((4, 0), dtype=torch.int64 if spec['wide'] else torch.int32, device=_dev())
     del parts
     counts = [None] * _CTX.world
     _CTX.dist.all_gather_object(counts, int(mine.shape[1]))
     if counts[_CTX.rank]:
         _CTX.dist.send(mine.contiguous(), 0)
+    record('ingest', lines, mine.shape[1], time.perf_counter() - t0, mine.numel() * mine.element_size())
 
 
 def gather_into(ing, wide):
@@ -264,11 +419,11 @@ def gather_into(ing, wide):
     for r in range(1, _CTX.world):
         if not counts[r]:
             continue
-        buf = torch.empty((4, counts[r]), dtype=torch.int64 if wide else torch.int32, device='cuda:%d' % _CTX.device)
+        buf = torch.empty((4, counts[r]), dtype=torch.int64 if wide else torch.int32, device=_dev())
         _CTX.dist.recv(buf, r)
         id1, id2 = buf[0].to(torch.int32).contiguous(), buf[2].to(torch.int32).contiguous()
         p1, p2 = buf[1].contiguous(), buf[3].contiguous()
-        torch.cuda.synchronize()
+        _torch_sync()
         ing.push_device(counts[r], id1.data_ptr(), p1.data_ptr(), id2.data_ptr(), p2.data_ptr(), wide=wide)
         from . import _lib
         _lib.check(_lib.load().hhx_synchronize())            # the push has read the tensors before they go
@@ -300,13 +455,20 @@ def run_rank(drive):
             drive()
             ok = True
         finally:
-            if ctx is not None:
-                try:
-                    finish(ok)
-                finally:
-                    shutdown()
+            try:
+                if ok:
+                    write_record(0)
+            finally:
+                if ctx is not None:
+                    try:
+                        finish(ok)
+                    finally:
+                        shutdown()
         return 0
     try:
-        return serve()
+        status = serve()
+        if status == 0:
+            write_record(ctx.rank)
+        return status
     finally:
         shutdown()

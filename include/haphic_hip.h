@@ -565,6 +565,21 @@ typedef struct hhx_correct hhx_correct;
 int hhx_correct_create(int32_t n_ctg, const int64_t *ctg_len, int32_t resolution, hhx_correct **out);
 int hhx_correct_push(hhx_correct *c, int64_t n, const int32_t *id1, const int32_t *pos1, const int32_t *id2, const int32_t *pos2, int on_device);
 int hhx_correct_finalize(hhx_correct *c, int64_t *n_kept);
+/* Partial tables (the ranks of a --gpus N job fill one each from their byte range of the file, haphic_amd/ranks.py phase `correct_pass1`).  Until
+ * hhx_correct_finalize a table is a coverage difference array [n_bins] (+1 at the first bin of a kept record :1341, -1 behind its last) and the
+ * kept records (contig, lo, hi) in push order: difference arrays of disjoint record sets add, record lists concatenate, so absorbing the tables of
+ * consecutive pieces of a stream IN ORDER and finalizing gives the table of one pass over the whole stream, bit for bit (coverage, segments, the
+ * position lists :1342 in file order).  hhx_correct_export: *resolution, *n_bins, *n_pairs of a table that is not finalized (any may be null), and
+ * — where the pointers are not null — its difference array [n_bins] and its records [pair_first, pair_first + pair_count) in push order as
+ * pair_ctg [pair_count], pair_lo_hi [2 * pair_count] (lo, hi interleaved), into host arrays or (on_device) device arrays; the table is left as it
+ * was.  A large table goes out in pieces: the difference array once, the records a range at a time.  hhx_correct_absorb adds such a piece to c
+ * (cov_diff null: records alone; n_pairs 0: the difference array alone; at most 2^31 - 1 records a call): a resolution or bin count other than
+ * c's, or a finalized c, is refused before anything is touched; a record no push keeps (contig outside the table, not 0 <= lo <= hi) fails the
+ * call and leaves c unfit for hhx_correct_finalize. */
+int hhx_correct_export(hhx_correct *c, int32_t *resolution, int64_t *n_bins, int64_t *n_pairs, int32_t *cov_diff, int64_t pair_first,
+                       int64_t pair_count, int32_t *pair_ctg, int32_t *pair_lo_hi, int on_device);
+int hhx_correct_absorb(hhx_correct *c, int32_t resolution, int64_t n_bins, const int32_t *cov_diff, int64_t n_pairs, const int32_t *pair_ctg,
+                       const int32_t *pair_lo_hi, int on_device);
 int hhx_correct_shape(hhx_correct *c, int32_t *n_seg, int64_t *n_bins, int64_t *n_pairs);
 int hhx_correct_fetch_segments(hhx_correct *c, int64_t *bin_off, int32_t *n_bins, int32_t *len, int64_t *pair_off);
 int hhx_correct_fetch_coverage(hhx_correct *c, int32_t *cov);

@@ -11,6 +11,10 @@
 (b) and (c) read the same bytes through the same tokeniser as (d): what they cost beyond it is the extra kernels.
 
     python tools/correct_bench.py [--contigs 100000] [--pairs 500000000] [--chimeras 2000] [--out profiles/correction_bench.json]
+    python tools/correct_bench.py --gpus N [--host-transport] [--pairs 20000000] [--out FILE.json]
+                                                                                   both passes as N ranks over one .pairs file (haphic_amd/ranks.py):
+                                                                                   per rank and per pass the lines parsed, the pairs kept, the seconds
+                                                                                   and the bytes sent to rank 0.  Ranks that share a device: functional only
     python tools/correct_bench.py --cpu-reference DIR [--prefix-pairs 200000]     the reference's own parse_pairs_for_correction (CPU, no GPU needed)
                                                                                    on a labelled prefix of such a file; merged into --out
 """
@@ -174,6 +178,108 @@ def gpu_legs(a):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def _planted_correction(names, lens, joins):
+    """the final_break_* dicts and the corrected contig table of an assembly cut at the planted joins, in the shape break_and_update_ctgs leaves them"""
+    truth = dict(joins)
+    fpos, ffrag, cnames, clens = {}, {}, [], []
+    for k, (nm, ln) in enumerate(zip(names, lens)):
+        if k in truth:
+            cut = truth[k]
+            fpos[nm], ffrag[nm] = [cut, 0], ['{}:{}-{}'.format(nm, cut + 1, ln), '{}:1-{}'.format(nm, cut)]
+        else:
+            cnames.append(nm)
+            clens.append(ln)
+    for k, (nm, ln) in enumerate(zip(names, lens)):
+        if k in truth:
+            cnames += ffrag[nm][::-1]
+            clens += [truth[k], ln - truth[k]]
+    return fpos, ffrag, cnames, clens
+
+
+def ranks_job(meta_path):
+    """one rank of the --gpus N mode (started by ranks.launch): rank 0 drives pass one and pass two, the others serve"""
+    from haphic_amd import _lib, cluster, correct, ranks
+    with open(meta_path) as f:
+        meta = json.load(f)
+    ctx = ranks.init(True if meta['host_transport'] else None)
+    if ctx is None:
+        _lib.check(_lib.load().hhx_set_device(0))
+
+    def drive():
+        names, lens = meta['names'], meta['lens']
+        fa_dict = {nm: [None, int(ln), int(ln) // 256 + 1] for nm, ln in zip(names, lens)}
+        args = types.SimpleNamespace(alignments=meta['pairs'], aln_format='pairs', correct_resolution=500, median_cov_ratio=0.2, region_len_ratio=0.1,
+                                     min_region_cutoff=5000, threads=8, flank=500, remove_allelic_links=0, remove_concentrated_links=False,
+                                     max_read_pairs=200, nwindows=50, skip_clustering=True)
+        os.chdir(meta['workdir'])
+        cov_d, pos_d = correct.parse_pairs_for_correction(fa_dict, args)
+        found = len(correct.detect_break_points(cov_d, fa_dict, args))
+        del cov_d, pos_d
+        fpos, ffrag, cnames, clens = _planted_correction(names, lens, meta['joins'])
+        fixed = {nm: [None, int(ln), int(ln) // 256 + 1] for nm, ln in zip(cnames, clens)}
+        _s, _b, _bs, frag_len_dict, nx, _re, split = cluster.stat_fragments(fixed, 'GATC', {}, set(), nchrs=meta['nchrs'], flank=500, Nx=100, bin_size=-1)
+        assert not split
+        aln = correct.pairs_generator_for_correction_ctg(meta['pairs'], 'pairs', fpos, ffrag)
+        out = cluster.parse_alignments_for_ctgs(aln, fixed, args, frag_len_dict, nx, 'int32', 'int32')
+        _lib.check(_lib.load().hhx_synchronize())
+        n_full = len(out[0])
+        del out
+        _lib.files_join()
+        with open(os.path.join(meta['workdir'], 'rank0_result.json'), 'w') as f:
+            json.dump({'contigs_with_break_points': found, 'full_link_keys': n_full}, f)
+    return ranks.run_rank(drive)
+
+
+def ranks_mode(a):
+    """the file made here (one process), then N fresh rank processes over it; their records collected"""
+    import torch
+    import c3_run
+    from haphic_amd import _lib, ranks, synth
+    _lib.check(_lib.load().hhx_set_device(0))
+    per_chr = max(1, a.contigs // a.nchrs)
+    base = synth.make_genome(a.nchrs, per_chr * a.mean_len, a.mean_len, seed=12345)
+    arrays = synth.sample_pairs(base, a.pairs, seed=12346, device='cuda:0')
+    gen, id1, p1, id2, p2, joins = synth.join_chimeras(base, *arrays, a.chimeras, seed=777)
+    d = tempfile.mkdtemp(prefix='hhx_correct_ranks_', dir=a.dir or ('/dev/shm' if os.path.isdir('/dev/shm') else None))
+    try:
+        path = os.path.join(d, 'hic.pairs')
+        size, lines = c3_run.write_pairs_file(path, gen, id1.contiguous(), p1.contiguous(), id2.contiguous(), p2.contiguous())
+        del arrays, id1, p1, id2, p2
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        _lib.check(_lib.load().hhx_pool_trim())
+        rec = os.path.join(d, 'record')
+        os.makedirs(rec)
+        os.makedirs(os.path.join(d, 'work'))
+        meta = os.path.join(d, 'meta.json')
+        with open(meta, 'w') as f:
+            json.dump({'pairs': path, 'workdir': os.path.join(d, 'work'), 'names': list(gen.names), 'lens': [int(x) for x in gen.length.tolist()],
+                       'joins': [[int(k), int(v)] for k, v in joins], 'nchrs': a.nchrs, 'host_transport': bool(a.host_transport)}, f)
+        env = dict(os.environ, HAPHIC_RANKS_RECORD=rec)
+        env.pop('MASTER_PORT', None)
+        t0 = time.perf_counter()
+        rc = ranks.launch(['timeout', '-k', '10', str(a.rank_timeout), sys.executable, os.path.abspath(__file__), '--rank-job', meta], a.gpus,
+                          host_transport=a.host_transport, env=env)
+        wall = time.perf_counter() - t0
+        if rc:
+            raise SystemExit('the {}-rank job failed with status {}'.format(a.gpus, rc))
+        per_rank = []
+        for r in range(a.gpus):
+            with open(os.path.join(rec, 'rank%d.json' % r)) as f:
+                per_rank.append(json.load(f))
+        with open(os.path.join(d, 'work', 'rank0_result.json')) as f:
+            result = json.load(f)
+        shared = a.gpus > _lib.device_count()
+        return {'what': 'both correction passes as %d ranks over one .pairs file (pass one = phase correct_pass1, pass two = phase ingest with the remap)' % a.gpus,
+                'label': 'functional: %d ranks SHARE %d device(s) over the host transport — content and order, not speed' % (a.gpus, _lib.device_count())
+                if shared or a.host_transport else 'one device per rank',
+                'device': torch.cuda.get_device_name(0), 'ranks': a.gpus, 'host_transport': bool(a.host_transport or shared),
+                'contigs': int(gen.n), 'pairs': int(a.pairs), 'chimeras_planted': len(joins), 'pairs_file_bytes': int(size), 'pairs_file_lines': int(lines),
+                'job_wall_s_with_process_start': wall, 'per_rank': per_rank, **result}
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
 def cpu_reference(a):
     """the reference's parse_pairs_for_correction :1300-1344, as it is, on the first --prefix-pairs lines of a file of the same model"""
     from haphic_amd import synth
@@ -207,7 +313,7 @@ def cpu_reference(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--contigs', type=int, default=100000)
-    ap.add_argument('--pairs', type=int, default=500_000_000)
+    ap.add_argument('--pairs', type=int, default=None, help='read pairs (default 500 M; 20 M with --gpus)')
     ap.add_argument('--nchrs', type=int, default=24)
     ap.add_argument('--mean-len', type=int, default=30_000)
     ap.add_argument('--chimeras', type=int, default=2000)
@@ -215,12 +321,24 @@ def main():
     ap.add_argument('--out', default=None, help='JSON file to write / merge into')
     ap.add_argument('--cpu-reference', default=None, help="the reference's scripts directory: time its pass one on a prefix instead of the GPU legs")
     ap.add_argument('--prefix-pairs', type=int, default=200_000)
+    ap.add_argument('--gpus', type=int, default=0, help='run both passes as this many ranks and report the per-rank record')
+    ap.add_argument('--host-transport', action='store_true')
+    ap.add_argument('--rank-timeout', type=int, default=600, help='seconds each rank process may run')
+    ap.add_argument('--rank-job', default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.rank_job:
+        sys.exit(ranks_job(a.rank_job))
+    if a.gpus > 8:
+        ap.error('--gpus: at most 8 ranks (this process keeps its device open beside them)')
+    if a.pairs is None:
+        a.pairs = 20_000_000 if a.gpus else 500_000_000
     out = {}
     if a.out and os.path.exists(a.out):
         with open(a.out) as f:
             out = json.load(f)
-    if a.cpu_reference:
+    if a.gpus:
+        out['ranks_%d' % a.gpus] = ranks_mode(a)
+    elif a.cpu_reference:
         out['cpu_reference_prefix'] = cpu_reference(a)
     else:
         out.update(gpu_legs(a))
