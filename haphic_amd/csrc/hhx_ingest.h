@@ -25,6 +25,10 @@ struct LinkRun {
     DevBuf<u64> key, ord_full, ord_flank;
     DevBuf<u32> ht;     // [n][4]
     DevBuf<u32> fl;     // [n]
+    // what hhx_ingest_finalize asks of a run, taken by the kernel that wrote it (k_aggregate) where it is one:
+    // [0] rows with a full ordinal, [1] rows with a flank ordinal, [2] 1 + largest ordinal
+    bool has_stats = false;
+    unsigned long long stats[3] = {0, 0, 0};
     int alloc(i64 rows) {
         n = rows;
         return key.alloc((size_t)rows) || ord_full.alloc((size_t)rows) || ord_flank.alloc((size_t)rows) ||

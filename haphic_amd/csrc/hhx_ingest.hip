@@ -42,6 +42,7 @@ template <bool COMBINED, class POS = i32>
 struct SrcPairs {
     typedef u32 w1_t;
     static constexpr bool MARK = false;
+    static constexpr bool BATCHED = false;
     const i32 *id1; const POS *pos1; const i32 *id2; const POS *pos2;
     DevTables t;
     int stream;
@@ -126,7 +127,17 @@ void launch_map(const SrcPairs<COMBINED, POS> &src, i64 n, u64 *rec, const MapHi
 struct SrcMapped {
     typedef u32 w1_t;
     static constexpr bool MARK = false;
+    static constexpr bool BATCHED = true;      // hhx_partition.h: the loads of a whole tile are issued before the first is consumed
+    static constexpr int CHUNK = 16, CHUNK_SCATTER = 16;
     const u64 *rec;
+    struct Raw { u64 a; };
+    __device__ __forceinline__ void load1(i64 idx, Raw &r) const { r.a = rec[idx]; }
+    __device__ __forceinline__ void load2(Raw &) const {}
+    __device__ __forceinline__ bool decode(i64 idx, const Raw &r, u64 &w0, u32 &ord) const {
+        w0 = r.a;
+        ord = (u32)idx;
+        return w0 != EMPTY_KEY;
+    }
     __device__ __forceinline__ bool get(i64 idx, u64 &w0, u32 &ord) const {
         w0 = rec[idx];
         ord = (u32)idx;
@@ -136,7 +147,17 @@ struct SrcMapped {
 struct SrcRows {            // table rows to be merged: the record is the bare key, the "ordinal" the row index
     typedef u32 w1_t;
     static constexpr bool MARK = false;
+    static constexpr bool BATCHED = true;
+    static constexpr int CHUNK = 16, CHUNK_SCATTER = 16;
     const u64 *key;
+    struct Raw { u64 a; };
+    __device__ __forceinline__ void load1(i64 idx, Raw &r) const { r.a = key[idx]; }
+    __device__ __forceinline__ void load2(Raw &) const {}
+    __device__ __forceinline__ bool decode(i64 idx, const Raw &r, u64 &rec, u32 &ord) const {
+        rec = r.a & KEY_MASK;
+        ord = (u32)idx;
+        return true;
+    }
     __device__ __forceinline__ bool get(i64 idx, u64 &rec, u32 &ord) const {
         rec = key[idx] & KEY_MASK;
         ord = (u32)idx;
@@ -165,6 +186,7 @@ struct AggParams {
     u32 *o_ht, *o_fl;                        // (a run is unordered by definition, so the reservation order does not matter)
     unsigned long long *out_cursor;       // [1] rows written so far
     unsigned int *overflow;
+    unsigned long long *stats;            // [3] of the rows written: with a full ordinal, with a flank ordinal, 1 + largest ordinal (LinkRun::stats)
 };
 
 // MODE 0: pair records (flags inside rec, 32-bit batch ordinals).  MODE 1: table rows (64-bit ordinals + counts gathered by row).
@@ -199,6 +221,8 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
     unsigned long long rbn = b + 1 < b1 ? A.base[b + 1] : 0ull, ren = b + 1 < b1 ? A.base[b + 2] : 0ull;      // bounds run two buckets ahead
     u64 rec_r[AG_R];
     u32 ord_r[AG_R];
+    u32 st_full = 0, st_flank = 0;                 // this thread's share of A.stats: the rows pass through its registers on their way out
+    u64 st_max = 0;
 #pragma unroll
     for (int u = 0; u < AG_R; ++u) {
         const unsigned long long i = rb + tid + (unsigned long long)u * AG_T;
@@ -313,13 +337,18 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
             const u64 key = s_key[s];
             if (key == EMPTY_KEY) continue;
             A.o_key[o] = key;
+            u64 of, ok;
             if constexpr (MODE == 0) {
-                A.o_ord_full[o] = s_of[s] == ORD_NONE ? NO_ORD : A.ord_base + (u64)s_of[s];
-                A.o_ord_flank[o] = s_ok[s] == ORD_NONE ? NO_ORD : A.ord_base + (u64)s_ok[s];
+                of = s_of[s] == ORD_NONE ? NO_ORD : A.ord_base + (u64)s_of[s];
+                ok = s_ok[s] == ORD_NONE ? NO_ORD : A.ord_base + (u64)s_ok[s];
             } else {
-                A.o_ord_full[o] = (u64)s_of[s];
-                A.o_ord_flank[o] = (u64)s_ok[s];
+                of = (u64)s_of[s];
+                ok = (u64)s_ok[s];
             }
+            A.o_ord_full[o] = of;
+            A.o_ord_flank[o] = ok;
+            if (of != NO_ORD) { ++st_full; st_max = max(st_max, of + 1); }
+            if (ok != NO_ORD) { ++st_flank; st_max = max(st_max, ok + 1); }
             *reinterpret_cast<uint4 *>(A.o_ht + o * 4) = make_uint4(s_cnt[s], s_cnt[AG_CAP + s], s_cnt[2 * AG_CAP + s], s_cnt[3 * AG_CAP + s]);   // one 16-byte store
             A.o_fl[o] = s_cnt[4 * AG_CAP + s];
             ++o;
@@ -335,6 +364,14 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
         b = bn; rb = rbn; re = ren; rbn = rbn2; ren = ren2;
 #pragma unroll
         for (int u = 0; u < AG_R; ++u) { rec_r[u] = rec_n[u]; ord_r[u] = ord_n[u]; }
+    }
+    const u64 w_full = (u64)wave_sum_i64((i64)st_full), w_flank = (u64)wave_sum_i64((i64)st_flank);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) st_max = max(st_max, (u64)__shfl_down((long long)st_max, o, HHX_WAVE));
+    if (lane == 0) {
+        if (w_full) atomicAdd(&A.stats[0], (unsigned long long)w_full);
+        if (w_flank) atomicAdd(&A.stats[1], (unsigned long long)w_flank);
+        if (st_max) atomicMax(&A.stats[2], (unsigned long long)st_max);
     }
 }
 
@@ -406,23 +443,23 @@ int build_run(const Src &src, i64 n_items, const Payload &pl, u64 ord_base, Link
         A.in_ord_full = pl.ord_full; A.in_ord_flank = pl.ord_flank; A.in_ht = pl.ht; A.in_fl = pl.fl;
         // The run is written once: its arrays are sized for the worst case (every record a new key) and n is set to the
         // rows actually reserved.  (Round 1 wrote gapped segments and compacted them: 3.9 ms and 15 GB of traffic per 500 M pairs.)
-        DevBuf<unsigned long long> out_cursor;
-        DevBuf<unsigned int> overflow;
-        if (run->alloc(n_valid) || out_cursor.alloc(1) || overflow.alloc(1)) { delete run; return 1; }
-        HHX_HIP(hipMemsetAsync(overflow.p, 0, sizeof(unsigned int), g_stream));
-        HHX_HIP(hipMemsetAsync(out_cursor.p, 0, sizeof(unsigned long long), g_stream));
+        // one block of control words, cleared by one memset and read back by one copy: [0] rows reserved, [1] overflow flag, [2..4] LinkRun::stats
+        // (hhx_ingest_finalize no longer walks the 16 B of ordinals per key with a kernel and a synchronisation of its own)
+        DevBuf<unsigned long long> ctl;
+        unsigned long long ctl_host[5] = {0, 0, 0, 0, 0};
+        if (run->alloc(n_valid) || ctl.alloc(5)) { delete run; return 1; }
+        HHX_HIP(hipMemsetAsync(ctl.p, 0, sizeof ctl_host, g_stream));
         A.o_key = run->key.p; A.o_ord_full = run->ord_full.p; A.o_ord_flank = run->ord_flank.p; A.o_ht = run->ht.p; A.o_fl = run->fl.p;
-        A.out_cursor = out_cursor.p; A.overflow = overflow.p;
+        A.out_cursor = ctl.p; A.overflow = reinterpret_cast<unsigned int *>(ctl.p + 1); A.stats = ctl.p + 2;
         { KTimer kt("aggregate");
         k_aggregate<MODE><<<n_wg, AG_T, agg_lds_bytes<MODE>(), g_stream>>>(A); }
         HHX_LAUNCH_CHECK();
-        unsigned long long n_keys = 0;
-        unsigned int ov = 0;
-        HHX_HIP(hipMemcpyAsync(&n_keys, out_cursor.p, sizeof n_keys, hipMemcpyDeviceToHost, g_stream));
-        HHX_HIP(hipMemcpyAsync(&ov, overflow.p, sizeof ov, hipMemcpyDeviceToHost, g_stream));
+        HHX_HIP(hipMemcpyAsync(ctl_host, ctl.p, sizeof ctl_host, hipMemcpyDeviceToHost, g_stream));
         HHX_HIP(hipStreamSynchronize(g_stream));
-        if (ov) continue;                                       // a sub-pass held more distinct keys than LDS: more buckets
-        run->n = (i64)n_keys;
+        if (ctl_host[1]) continue;                              // a sub-pass held more distinct keys than LDS: more buckets
+        run->n = (i64)ctl_host[0];
+        run->has_stats = true;
+        for (int k = 0; k < 3; ++k) run->stats[k] = ctl_host[2 + k];
         *out = run;
         return 0;
     }
@@ -495,7 +532,9 @@ int upload(DevBuf<T> &d, const T *h, size_t n) {
 
 int run_stats(const LinkRun *r, i64 *n_full, i64 *n_flank, u64 *ord_limit) {
     unsigned long long h[3] = {0, 0, 0};
-    if (r && r->n) {
+    if (r && r->n && r->has_stats) {
+        for (int k = 0; k < 3; ++k) h[k] = r->stats[k];
+    } else if (r && r->n) {                                      // a table that was pushed as it is (hhx_ingest_push_table) and needed no merge
         DevBuf<unsigned long long> d;
         if (d.alloc(3)) return 1;
         HHX_HIP(hipMemsetAsync(d.p, 0, sizeof h, g_stream));

@@ -275,6 +275,7 @@ namespace {
 struct SrcDirected {
     typedef u64 w1_t;
     static constexpr bool MARK = false;
+    static constexpr bool BATCHED = false;
     const u64 *key, *ord_flank;
     const u32 *fl;
     const unsigned char *in_set;
@@ -313,30 +314,44 @@ __device__ __forceinline__ u32 xcc_id() {            // the XCD this wave runs o
 struct SrcDirectedPacked {
     typedef NoPayload w1_t;
     static constexpr bool MARK = true;      // k_part_count calls mark_load / mark_apply once per record (level 1 only)
+    static constexpr bool BATCHED = true;
+    // records whose raw words are in flight together: half a tile in the count pass; fewer in the scatter pass, which keeps the whole
+    // tile in registers besides (more would cost either kernel its second workgroup per CU)
+    static constexpr int CHUNK = 7, CHUNK_SCATTER = 4;
     const u64 *key, *ord_flank;
     const u32 *fl;
     const unsigned char *in_set;
     unsigned long long *first_pos;          // [N_XCC][n_frag]; set in the object the level-1 count pass reads through, null otherwise
     unsigned int *too_big;
     i32 n_frag;
-    // extra: the entry's position in the insertion order, 2 * ordinal + side (all ones: its count does not fit PK_CNT_BITS)
-    __device__ __forceinline__ bool get_marked(i64 idx, u64 &w0, u64 &extra) const {
+    // the loads of a record without a branch between them (hhx_partition.h: BATCHED): the three words of the table row, then the
+    // two membership bytes its key points at — every load of a chunk of records is in flight before the first is consumed
+    struct Raw { u64 ord, ky; u32 c; unsigned char si, sj; };
+    __device__ __forceinline__ u32 frag_i(const Raw &r) const { return min((u32)(r.ky >> ID_BITS), (u32)n_frag - 1u); }     // (clamped: the gathers are
+    __device__ __forceinline__ u32 frag_j(const Raw &r) const { return min((u32)(r.ky & ID_MASK), (u32)n_frag - 1u); }      //  unconditional)
+    __device__ __forceinline__ void load1(i64 idx, Raw &r) const {
         const i64 k = idx >> 1;
-        const u64 ord = ord_flank[k];
-        if (ord == NO_ORD) return false;
-        const u64 ky = key[k];
-        const u32 i = (u32)(ky >> ID_BITS), j = (u32)(ky & ID_MASK);
-        if (!in_set[i] || !in_set[j]) return false;
+        r.ord = ord_flank[k]; r.ky = key[k]; r.c = fl[k];
+    }
+    __device__ __forceinline__ void load2(Raw &r) const { r.si = in_set[frag_i(r)]; r.sj = in_set[frag_j(r)]; }
+    // extra: the entry's position in the insertion order, 2 * ordinal + side (all ones: its count does not fit PK_CNT_BITS)
+    __device__ __forceinline__ bool decode_marked(i64 idx, const Raw &r, u64 &w0, u64 &extra) const {
+        const u32 i = (u32)(r.ky >> ID_BITS), j = (u32)(r.ky & ID_MASK);
         const u32 side = (u32)(idx & 1);
         const u32 a = side ? j : i, b = side ? i : j;
-        const u32 c = fl[k];
-        w0 = ((u64)a << (PK_ID_BITS + PK_CNT_BITS)) | ((u64)b << PK_CNT_BITS) | (u64)(c & PK_CNT_MASK);
-        extra = c > PK_CNT_MASK ? ~0ull : 2 * ord + side;
-        return true;
+        w0 = ((u64)a << (PK_ID_BITS + PK_CNT_BITS)) | ((u64)b << PK_CNT_BITS) | (u64)(r.c & PK_CNT_MASK);
+        extra = r.c > PK_CNT_MASK ? ~0ull : 2 * r.ord + side;
+        return r.ord != NO_ORD && r.si && r.sj;
     }
-    __device__ __forceinline__ bool get(i64 idx, u64 &w0, NoPayload &) const {
+    __device__ __forceinline__ bool decode(i64 idx, const Raw &r, u64 &w0, NoPayload &) const {
         u64 extra;
-        return get_marked(idx, w0, extra);
+        return decode_marked(idx, r, w0, extra);
+    }
+    __device__ __forceinline__ bool get(i64 idx, u64 &w0, NoPayload &w1) const {
+        Raw r;
+        load1(idx, r);
+        load2(r);
+        return decode(idx, r, w0, w1);
     }
     // First position of the row fragment: an atomic min that almost never fires, because the current minimum is read first
     // and the table is walked in hash order (a minimum settles after ~ln(entries) updates).  For that read to see the
@@ -344,12 +359,13 @@ struct SrcDirectedPacked {
     // every XCD keeps ITS OWN copy of the table (first_pos[xcc][n_frag], merged by k_min_over_xcc afterwards) — an atomic
     // drops the line from the issuing XCD's L2, the next L2-served (sc1: past the CU's L1) load fetches the new value.
     // With one shared table each XCD's L2 kept the initial ~0 and every lane fired: 3 ms of fabric atomics per 330 M entries.
+    // The read is issued beside the membership gathers (it needs the key alone), for records that turn out to be dropped too.
     __device__ __forceinline__ unsigned long long *my_table() const {
         return first_pos + (size_t)xcc_id() * (size_t)n_frag;
     }
-    __device__ __forceinline__ u64 mark_load(u64 w0) const {
+    __device__ __forceinline__ u64 mark_load(i64 idx, const Raw &r) const {
         if (!first_pos) return 0;
-        return __hip_atomic_load(&my_table()[(u32)(w0 >> (PK_ID_BITS + PK_CNT_BITS)) & PK_ID_MASK], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return __hip_atomic_load(&my_table()[(idx & 1) ? frag_j(r) : frag_i(r)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __device__ __forceinline__ void mark_apply(u64 w0, u64 pos, u64 seen) const {
         if (!first_pos) return;
@@ -557,10 +573,7 @@ int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const
         HHX_TRY(partition_records(src, DigRowPacked(), 2 * run->n, row_bits, level_bits, &part, "d2m", &marking));
         k_min_over_xcc<<<grid_for((u64)n_frag), 256, 0, g_stream>>>(n_frag, per_xcc.p, first_pos.p);
         HHX_LAUNCH_CHECK();
-        unsigned int too_big = 0;
-        HHX_HIP(hipMemcpyAsync(&too_big, nl.p + 1, sizeof too_big, hipMemcpyDeviceToHost, g_stream));
-        HHX_HIP(hipStreamSynchronize(g_stream));
-        if (too_big) return -2;
+        // (whether a count was too big for the packed entry is read back together with n_linked, below)
     } else {
         const SrcDirected src{run->key.p, run->ord_flank.p, run->fl.p, in_set.p};
         HHX_TRY(partition_records(src, DigRow(), 2 * run->n, row_bits, level_bits, &part, "d2m"));
@@ -576,14 +589,15 @@ int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const
     }
     { KTimer kt("d2m_rank");
     HHX_TRY(rank_first_positions(n_frag, first_pos.p, 2 * ord_limit + 1, frag_index.p, nl.p)); }
-    unsigned int n_linked = 0;
-    HHX_HIP(hipMemcpyAsync(&n_linked, nl.p, sizeof n_linked, hipMemcpyDeviceToHost, g_stream));
-    HHX_HIP(hipStreamSynchronize(g_stream));
-    if (n_rest < 0) {
-        i64 members = 0;
+    unsigned int nl_host[2] = {0, 0};                             // n_linked, "a count does not fit the packed entry"
+    HHX_HIP(hipMemcpyAsync(nl_host, nl.p, sizeof nl_host, hipMemcpyDeviceToHost, g_stream));
+    i64 members = 0;                                             // counted while the device works
+    if (n_rest < 0)
         for (i32 f = 0; f < n_frag; ++f) members += in_set_host[f] != 0;
-        n_rest = (i32)(members - (i64)n_linked);
-    }
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    if (PACKED && nl_host[1]) return -2;
+    const unsigned int n_linked = nl_host[0];
+    if (n_rest < 0) n_rest = (i32)(members - (i64)n_linked);
     const i64 shape64 = (i64)n_linked + n_rest;
     if (shape64 > INT32_MAX) return fail("matrix order exceeds int32");
     const i32 shape = (i32)shape64;

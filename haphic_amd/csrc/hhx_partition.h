@@ -28,12 +28,31 @@ struct PartLevel {
                         // within a tile except where a tile straddles two buckets of the previous level
 };
 
+// A record source is read through get(idx, w0, w1) -> "the record exists".  A BATCHED source also hands its loads out one step at a
+// time, without a branch between them: load1(idx, raw) (idx valid: the caller clamps it), load2(raw) (the gathers that depend on
+// load1's words) and decode(idx, raw, w0, w1), which touches no memory.  The kernels issue load1 for a CHUNK of records, then load2
+// for all of them, then decode: with get() in the per-record loop every load sat in a basic block of its own behind the LDS atomic of
+// the record before it, each followed by s_waitcnt vmcnt(0) — one round trip per load and record (read off the ISA), which is why
+// these passes ran at a third of the stream rate.
 template <class W1>
 struct SrcRecs {
     typedef W1 w1_t;
     static constexpr bool MARK = false;
+    static constexpr bool BATCHED = true;
+    static constexpr int CHUNK = 16, CHUNK_SCATTER = 16;
     const u64 *w0;
     const W1 *w1;
+    struct Raw { u64 a; W1 b; };
+    __device__ __forceinline__ void load1(i64 idx, Raw &r) const {
+        r.a = w0[idx];
+        if constexpr (PartW1<W1>::HAS) r.b = w1[idx];
+    }
+    __device__ __forceinline__ void load2(Raw &) const {}
+    __device__ __forceinline__ bool decode(i64, const Raw &r, u64 &a, W1 &b) const {
+        a = r.a;
+        if constexpr (PartW1<W1>::HAS) b = r.b;
+        return true;
+    }
     __device__ __forceinline__ bool get(i64 idx, u64 &a, W1 &b) const {
         a = w0[idx];
         if constexpr (PartW1<W1>::HAS) b = w1[idx];
@@ -72,33 +91,45 @@ __global__ __launch_bounds__(PT) void k_part_count(Src src, Dig dig, i64 n, Part
             cur = tg;
             lds_barrier();
         }
-        if constexpr (Src::MARK) {
-            // a source with a side effect per record (get_marked / mark_load / mark_apply): the record loads of half a tile
-            // first, then the loads the side effect needs, then its (rare) atomics — an atomic inside the per-record loop
-            // would pin the loads of the following records behind it and serialise a dozen round trips per thread; halves,
-            // because three 64-bit words per record in flight for the whole tile cost the kernel half its occupancy
-            constexpr int HALF = (P_ITEMS + 1) / 2;
+        if constexpr (Src::BATCHED) {
+            // the loads of a chunk of records, then the gathers that depend on them — for a source with a side effect per record
+            // (MARK: mark_load / mark_apply) the load the side effect needs rides with those gathers — then the histogram and the
+            // side effect's (rare) atomics: an atomic inside the load loop would pin the loads of the following records behind it
+            constexpr int CH = Src::CHUNK < P_ITEMS ? Src::CHUNK : P_ITEMS;
 #pragma unroll
-            for (int h = 0; h < P_ITEMS; h += HALF) {
-                u64 w0[HALF], extra[HALF], seen[HALF];
-                bool ok[HALF];
+            for (int h = 0; h < P_ITEMS; h += CH) {
+                typename Src::Raw raw[CH];
+                u64 seen[CH];
 #pragma unroll
-                for (int k = 0; k < HALF; ++k) {
-                    const i64 idx = base + (i64)(h + k) * PT + tid;
-                    ok[k] = h + k < P_ITEMS && idx < n && src.get_marked(idx, w0[k], extra[k]);
-                }
+                for (int k = 0; k < CH; ++k)
+                    if (h + k < P_ITEMS) {
+                        const i64 idx = base + (i64)(h + k) * PT + tid;
+                        src.load1(idx < n ? idx : n - 1, raw[k]);
+                    }
 #pragma unroll
-                for (int k = 0; k < HALF; ++k) seen[k] = ok[k] ? src.mark_load(w0[k]) : 0;
+                for (int k = 0; k < CH; ++k)
+                    if (h + k < P_ITEMS) {
+                        src.load2(raw[k]);
+                        if constexpr (Src::MARK) seen[k] = src.mark_load(base + (i64)(h + k) * PT + tid, raw[k]);
+                    }
 #pragma unroll
-                for (int k = 0; k < HALF; ++k)
-                    if (ok[k]) {
-                        src.mark_apply(w0[k], extra[k], seen[k]);
-                        const u32 d = dig(w0[k]) >> L.shift;
-                        if ((d >> L.lds_bits) == tg) atomicAdd(&hist[d & (u32)(nb - 1)], 1u);
-                        else atomicAdd(&ghist[d], 1ull);
+                for (int k = 0; k < CH; ++k)
+                    if (h + k < P_ITEMS) {
+                        const i64 idx = base + (i64)(h + k) * PT + tid;
+                        u64 w0, extra = 0;
+                        bool ok;
+                        if constexpr (Src::MARK) ok = src.decode_marked(idx, raw[k], w0, extra);
+                        else { typename Src::w1_t w1; ok = src.decode(idx, raw[k], w0, w1); }
+                        if (idx < n && ok) {
+                            if constexpr (Src::MARK) src.mark_apply(w0, extra, seen[k]);
+                            const u32 d = dig(w0) >> L.shift;
+                            if ((d >> L.lds_bits) == tg) atomicAdd(&hist[d & (u32)(nb - 1)], 1u);
+                            else atomicAdd(&ghist[d], 1ull);
+                        }
                     }
             }
         } else {
+            static_assert(!Src::MARK, "a source with a side effect per record is a BATCHED one");
 #pragma unroll
         for (int k = 0; k < P_ITEMS; ++k) {
             const i64 idx = base + (i64)k * PT + tid;
@@ -147,11 +178,36 @@ __global__ __launch_bounds__(PT) void k_part_scatter(Src src, Dig dig, i64 n, Pa
         u64 w0[P_ITEMS];
         W1 w1[P_ITEMS];
         u32 loc[P_ITEMS], rank[P_ITEMS];
+        bool have[P_ITEMS];
+        if constexpr (Src::BATCHED) {                                // every load of a chunk in flight before the first is consumed (see SrcRecs)
+            constexpr int CH = Src::CHUNK_SCATTER < P_ITEMS ? Src::CHUNK_SCATTER : P_ITEMS;
+#pragma unroll
+            for (int h = 0; h < P_ITEMS; h += CH) {
+                typename Src::Raw raw[CH];
+#pragma unroll
+                for (int k = 0; k < CH; ++k)
+                    if (h + k < P_ITEMS) {
+                        const i64 idx = base + (i64)(h + k) * PT + tid;
+                        src.load1(idx < n ? idx : n - 1, raw[k]);
+                    }
+#pragma unroll
+                for (int k = 0; k < CH; ++k)
+                    if (h + k < P_ITEMS) src.load2(raw[k]);
+#pragma unroll
+                for (int k = 0; k < CH; ++k)
+                    if (h + k < P_ITEMS) {
+                        const i64 idx = base + (i64)(h + k) * PT + tid;
+                        const bool ok = src.decode(idx, raw[k], w0[h + k], w1[h + k]);
+                        have[h + k] = idx < n && ok;
+                    }
+            }
+        }
 #pragma unroll
         for (int k = 0; k < P_ITEMS; ++k) {
             const i64 idx = base + (i64)k * PT + tid;
             loc[k] = 0xffffffffu;
-            if (idx < n && src.get(idx, w0[k], w1[k])) {
+            if constexpr (!Src::BATCHED) have[k] = idx < n && src.get(idx, w0[k], w1[k]);
+            if (have[k]) {
                 const u32 d = dig(w0[k]) >> L.shift;
                 if ((d >> L.lds_bits) == tg) {
                     loc[k] = d & (u32)(nb - 1);
