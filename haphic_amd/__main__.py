@@ -5,7 +5,8 @@ Argument parsing, logging, file formats and every stage outside the hot path are
 `--correct_nrounds N` (assembly correction) runs on the device too: both passes over the alignment file, the break-point detection and the breaking
 (haphic_amd/correct.py); correct_assembly's round loop and its FASTA writer stay the reference's.
 `python -m haphic_amd plot <arguments of "haphic plot">` does the same for HapHiC_plot.py: parse_pairs / parse_bam (the read-pair
-binning into the scaffold-bin contact matrix) run on the device (haphic_amd.plot.patch_plot), main() is the reference's.
+binning into the scaffold-bin contact matrix) and normalize_matrix (the Knight-Ruiz balancing of `--normalization KR`, the scaled
+matrix and the median behind vmax; `log10` / `none`: the median alone) run on the device (haphic_amd.plot.patch_plot), main() is the reference's.
 
 The reference checkout is found through --reference DIR or $HAPHIC_REFERENCE (the repository root or its scripts/
 directory).  Extra flags of the wrapper (removed before the reference parses the command line):

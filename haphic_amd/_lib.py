@@ -129,6 +129,15 @@ SIGNATURES = {
     'hhx_contact_map_fetch': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_contact_map_device': (C.c_int, [C.c_void_p, c_vpp, c_i32p]),
     'hhx_contact_map_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_plotnorm_create': (C.c_int, [C.c_void_p, C.c_int32, c_vpp, c_i64p, c_i64p, c_i32p]),
+    'hhx_plotnorm_set_blocks': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'hhx_plotnorm_balance': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_plotnorm_fetch_x': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_plotnorm_apply': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_plotnorm_median': (C.c_int, [C.c_void_p, C.c_int32, c_i64p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    'hhx_plotnorm_matvec': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'hhx_plotnorm_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_select_middle_u64': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     'hhx_ingest_fetch_ht_order': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_ingest_keep_frag_pairs': (C.c_int, [C.c_void_p, C.c_int]),
     'hhx_ingest_fetch_frag_pairs': (C.c_int, [C.c_void_p, c_i64p, C.c_void_p, C.c_void_p]),
@@ -803,6 +812,70 @@ class ContactMap:
         if self.h:
             load().hhx_contact_map_destroy(self.h)
             self.h = None
+
+
+class PlotNorm:
+    """hhx_plotnorm: the scaffold-bin matrix of `haphic plot` in HBM as int32 counts, for the Knight-Ruiz balancing, the scaled matrix and the
+    off-diagonal median of HapHiC_plot.py normalize_matrix :407-504 (include/haphic_hip.h).  .max / .min / .symmetric describe the upload."""
+
+    def __init__(self, matrix):
+        matrix = np.ascontiguousarray(matrix, np.int64)
+        assert matrix.ndim == 2 and matrix.shape[0] == matrix.shape[1]
+        self.n = matrix.shape[0]
+        self.h = C.c_void_p()
+        mx, mn, sym = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        check(load().hhx_plotnorm_create(ptr(matrix), self.n, C.byref(self.h), C.byref(mx), C.byref(mn), C.byref(sym)))
+        self.max, self.min, self.symmetric = mx.value, mn.value, bool(sym.value)
+        self.n_blocks = 0
+
+    def set_blocks(self, lo, hi):
+        lo, hi = np.ascontiguousarray(lo, np.int32), np.ascontiguousarray(hi, np.int32)
+        check(load().hhx_plotnorm_set_blocks(self.h, len(lo), ptr(lo), ptr(hi)))
+        self.n_blocks = len(lo)
+
+    def balance(self):
+        """-> (outer steps, mat-vec counts, status) per block, the whole matrix last; status 1: a cap of bnewt was reached"""
+        outer, mvp, status = np.zeros(self.n_blocks + 1, np.int32), np.zeros(self.n_blocks + 1, np.int64), np.zeros(self.n_blocks + 1, np.int32)
+        check(load().hhx_plotnorm_balance(self.h, ptr(outer), ptr(mvp), ptr(status)))
+        return outer, mvp, status
+
+    def x(self):
+        """-> (x of the whole matrix, the blocks' x at their bins)"""
+        x_all, x_blk = np.empty(self.n), np.empty(self.n)
+        check(load().hhx_plotnorm_fetch_x(self.h, ptr(x_all), ptr(x_blk)))
+        return x_all, x_blk
+
+    def apply(self):
+        out = np.empty((self.n, self.n), np.float64)
+        check(load().hhx_plotnorm_apply(self.h, ptr(out)))
+        return out
+
+    def middle(self, kr):
+        """-> (count, lo, hi): the two middle off-diagonal block cells, float64 (kr) or int64 counts"""
+        count, lo, hi = C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+        check(load().hhx_plotnorm_median(self.h, int(bool(kr)), C.byref(count), C.byref(lo), C.byref(hi)))
+        pair = np.array([lo.value, hi.value], np.uint64)
+        return count.value, pair.view(np.float64) if kr else pair.astype(np.int64)
+
+    def matvec(self, lo, hi, v):
+        v = np.ascontiguousarray(v, np.float64)
+        assert len(v) == hi - lo
+        out = np.empty(hi - lo)
+        check(load().hhx_plotnorm_matvec(self.h, int(lo), int(hi), ptr(v), ptr(out)))
+        return out
+
+    def destroy(self):
+        if self.h:
+            load().hhx_plotnorm_destroy(self.h)
+            self.h = None
+
+
+def select_middle(values):
+    """the two middle values of a non-negative float64 array (radix select over the bit patterns on the device); None when it is empty"""
+    values = np.ascontiguousarray(values, np.float64)
+    lo, hi = C.c_uint64(0), C.c_uint64(0)
+    check(load().hhx_select_middle_u64(ptr(values), len(values), C.byref(lo), C.byref(hi)))
+    return np.array([lo.value, hi.value], np.uint64).view(np.float64) if len(values) else None
 
 
 class PairsParser:

@@ -1,6 +1,7 @@
 """`haphic plot` read-pair binning on the MI355X (second half): mirrors of HapHiC_plot.py
-parse_pairs :153-202 and parse_bam :205-245 with the reference's signatures.  parse_agp / generate_contact_matrix /
-normalisation / drawing stay the reference's code; the per-read-pair loop runs on the device (hhx_contact_map_*):
+parse_pairs :153-202, parse_bam :205-245 and normalize_matrix :407-504 (with bnewt :291-404) with the reference's signatures.  parse_agp /
+generate_contact_matrix / drawing stay the reference's code; the per-read-pair loop (hhx_contact_map_*) and the Knight-Ruiz balancing,
+scaling and vmax median (hhx_plotnorm_*) run on the device:
 
     import HapHiC_plot as P
     import haphic_amd.plot
@@ -114,9 +115,114 @@ def parse_bam(bam, ctg_dict, ctg_aln_dict, bin_size, contact_matrix, group_to_to
     return _bin_batches(batches(), table, contact_matrix, 1, 'BAM', lambda: state['reader'].fetch())
 
 
+KR_FAILURE = ('Unable to converge. Maybe the matrix is too sparse (too few Hi-C links). '
+              'You can try another normalization method.')            # bnewt :325-327
+
+
+def block_bounds(n, group_list, group_size_dict, bin_size):
+    """the diagonal blocks normalize_matrix slices (:422-426): ceil(size / bin_size) consecutive bins per scaffold from bin 0, although
+    generate_contact_matrix :127 allotted size // bin_size + 1 — a scaffold whose length is a multiple of bin_size shifts every later block
+    by one bin and the trailing bins belong to no block.  Clipped to n as numpy clips a slice."""
+    from math import ceil
+    lo, hi, at = [], [], 0
+    for group in group_list:
+        m = ceil(group_size_dict[group] / bin_size)
+        lo.append(min(at, n))
+        hi.append(min(at + m, n))
+        at += m
+    return np.array(lo, np.int32), np.array(hi, np.int32)
+
+
+def _device_ok(contact_matrix):
+    """what hhx_plotnorm holds: a non-empty square integer ndarray (its counts are checked on the device during the upload)"""
+    return (isinstance(contact_matrix, np.ndarray) and contact_matrix.ndim == 2 and contact_matrix.shape[0] == contact_matrix.shape[1]
+            and contact_matrix.shape[0] > 0 and contact_matrix.dtype.kind in 'iu')
+
+
+def _normalize_matrix(contact_matrix, group_list, group_size_dict, bin_size, normalization, vmax_coef, manual_vmax, _original=None):
+    def hand_back():
+        if _original is None:
+            raise RuntimeError('this contact matrix needs the reference normalize_matrix (not a square matrix of counts below 2^31): '
+                               'call it through haphic_amd.plot.patch_plot(HapHiC_plot)')
+        return _original(contact_matrix, group_list, group_size_dict, bin_size, normalization, vmax_coef, manual_vmax)
+
+    kr = normalization == 'KR'
+    if not kr and manual_vmax >= 0:
+        pn = None                                           # :488-491: the list is never used, nothing to select
+    else:
+        if not _device_ok(contact_matrix):
+            return hand_back()
+        pn = _lib.PlotNorm(contact_matrix)
+    try:
+        if pn is not None:
+            if pn.min < 0 or pn.max >= 2 ** 31:
+                return hand_back()
+            pn.set_blocks(*block_bounds(pn.n, group_list, group_size_dict, bin_size))
+        if kr:
+            logger.info('Normalizing contact mattrix using the Knight-Ruiz (KR) balancing algorithm')
+            status = pn.balance()[2]
+            if (status == 1).any():
+                logger.info(KR_FAILURE)
+                raise RuntimeError(KR_FAILURE)
+            if status.any():
+                raise ValueError('min() arg is an empty sequence')          # :369 / :374 with no entry to step to the bound
+            if manual_vmax < 0:
+                count, pair = pn.middle(True)
+                vmax = np.median(pair if count else []) * vmax_coef
+            normalized_matrix = pn.apply()
+            if manual_vmax < 0:
+                logger.info('The vmax for the KR-normalized matrix is calculated to be {} ({} * median)'.format(vmax, vmax_coef))
+            else:
+                vmax = manual_vmax
+                logger.info('The vmax for the KR-normalized matrix is manually designated as {})'.format(vmax))
+            return normalized_matrix, vmax
+        if normalization == 'log10':
+            logger.info('Normalizing contact matrix using log10...')
+            normalized_matrix = np.log10(contact_matrix + 1)
+        else:
+            logger.info('Normalization is disabled')
+            normalized_matrix = contact_matrix
+        if manual_vmax < 0:
+            count, pair = pn.middle(False)
+            pair = pair.astype(contact_matrix.dtype)
+            # log10 is monotone: the middle values of log10(c + 1) are log10 of the middle counts + 1
+            middle = (np.log10(pair + 1) if normalization == 'log10' else pair) if count else []
+            vmax = np.median(middle) * vmax_coef
+        else:
+            vmax = manual_vmax
+        what = 'log-normalized' if normalization == 'log10' else 'raw'
+        if manual_vmax < 0:
+            logger.info('The vmax for the {} matrix is calculated to be {} ({} * median)'.format(what, vmax, vmax_coef))
+        else:
+            logger.info('The vmax for the {} matrix is manually designated as {}'.format(what, vmax))
+        return normalized_matrix, vmax
+    finally:
+        if pn is not None:
+            pn.destroy()
+
+
+def normalize_matrix(contact_matrix, group_list, group_size_dict, bin_size, normalization, vmax_coef, manual_vmax):
+    """normalize_matrix() :407-504 with bnewt :291-404 on the device (csrc/hhx_plotnorm.hip): the Knight-Ruiz balancing of every scaffold block
+    and of the whole matrix, the scaled matrix with its zeros kept, and the median of the off-diagonal block cells behind vmax.  Same log
+    lines, same return types.  `log10` / `none` keep the matrix a numpy expression on the host; only the median goes to the device."""
+    return _normalize_matrix(contact_matrix, group_list, group_size_dict, bin_size, normalization, vmax_coef, manual_vmax)
+
+
+def _with_original(original):
+    """the seam patch_plot installs: input the device matrix cannot hold (floats, negative counts, counts >= 2^31, not square, empty) goes to the
+    reference's own function"""
+    def seam(contact_matrix, group_list, group_size_dict, bin_size, normalization, vmax_coef, manual_vmax):
+        return _normalize_matrix(contact_matrix, group_list, group_size_dict, bin_size, normalization, vmax_coef, manual_vmax, _original=original)
+    seam.__wrapped__ = normalize_matrix
+    seam.__name__ = normalize_matrix.__name__
+    seam.__doc__ = normalize_matrix.__doc__
+    return seam
+
+
 def patch_plot(P):
     """P: the imported HapHiC_plot module.  Returns {name: original}."""
     _lib.load()
-    saved = {'parse_pairs': P.parse_pairs, 'parse_bam': P.parse_bam}
+    saved = {'parse_pairs': P.parse_pairs, 'parse_bam': P.parse_bam, 'normalize_matrix': P.normalize_matrix}
     P.parse_pairs, P.parse_bam = parse_pairs, parse_bam
+    P.normalize_matrix = _with_original(saved['normalize_matrix'])
     return saved

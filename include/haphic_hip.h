@@ -446,6 +446,35 @@ int hhx_contact_map_fetch(hhx_contact_map *m, int64_t *cells_host);
 int hhx_contact_map_device(hhx_contact_map *m, void **cells_dev_i64, int32_t *n_total_bins);
 int hhx_contact_map_destroy(hhx_contact_map *m);
 
+/* ------------------------------------------------------------------ f4: `haphic plot` normalisation and vmax
+ * HapHiC_plot.py bnewt :291-404 (Knight-Ruiz balancing, float64, tol 1e-6, delta 0.1, Delta 3, g 0.9, etamax 0.1, at most 1000
+ * outer / 10000 inner steps) and normalize_matrix :407-504, on the n x n scaffold-bin matrix (haphic_amd/csrc/hhx_plotnorm.hip).
+ * hhx_plotnorm_create takes the host matrix (int64, row major) into HBM as int32 counts and reports its max, min and whether it
+ *   is symmetric; a negative count or one >= 2^31 leaves a handle every later call refuses.  A[i][j] = (double)count + 0.00001 (:420).
+ * hhx_plotnorm_set_blocks: the scaffold blocks [lo[g], hi[g]) — ascending, disjoint, the bins outside belong to no block.
+ * hhx_plotnorm_balance: bnewt on every block, then on the whole matrix; entry g < n_blocks of outer / mvp / status is block g,
+ *   entry n_blocks the whole matrix: outer steps, matrix-vector products (MVP :388), status 0 = converged, 1 = a cap was reached
+ *   (the reference raises 'Unable to converge'), 2 = no step to the bound exists (the reference's min() of an empty list).  The
+ *   call returns at the first status != 0.  Same bits on every run: all reductions have a fixed order.
+ * hhx_plotnorm_fetch_x: x of the whole matrix and the blocks' x, each at its bins (0.0 outside the blocks); either may be null.
+ * hhx_plotnorm_apply: the float64 n x n result to the host: (x[i] * A[i][j]) * x[j] with the block's x inside a block and the
+ *   whole matrix's x elsewhere (:431 :437 :446), exactly 0.0 where the count is 0 (:418 :454).
+ * hhx_plotnorm_median: the two middle values (as 64-bit patterns; equal when the count is odd) of the off-diagonal cells of
+ *   all blocks (:447-450 / :482-485) and their number; kr != 0: the doubles (x[i] * A[i][j]) * x[j] BEFORE the zeros are restored,
+ *   kr == 0: the integer counts.  np.median is the mean of the two.
+ * hhx_plotnorm_matvec: out = A[lo:hi, lo:hi] @ v with host vectors (the mat-vec kernel alone).
+ * hhx_select_middle_u64: the same selection over `count` host values (unsigned order; non-negative doubles order like their bits). */
+typedef struct hhx_plotnorm hhx_plotnorm;
+int hhx_plotnorm_create(const int64_t *matrix, int32_t n, hhx_plotnorm **out, int64_t *max, int64_t *min, int32_t *symmetric);
+int hhx_plotnorm_set_blocks(hhx_plotnorm *h, int32_t n_blocks, const int32_t *lo, const int32_t *hi);
+int hhx_plotnorm_balance(hhx_plotnorm *h, int32_t *outer, int64_t *mvp, int32_t *status);
+int hhx_plotnorm_fetch_x(hhx_plotnorm *h, double *x_all, double *x_blocks);
+int hhx_plotnorm_apply(hhx_plotnorm *h, double *out_host);
+int hhx_plotnorm_median(hhx_plotnorm *h, int32_t kr, int64_t *count, uint64_t *lo, uint64_t *hi);
+int hhx_plotnorm_matvec(hhx_plotnorm *h, int32_t lo, int32_t hi, const double *v, double *out);
+int hhx_plotnorm_destroy(hhx_plotnorm *h);
+int hhx_select_middle_u64(const uint64_t *vals, int64_t count, uint64_t *lo, uint64_t *hi);
+
 /* HT_link_dict's insertion order (update_HT_link_dict :404-416): first[4 * k + q] = stream position (among the pairs that
  * entered full_link_dict) of the first read pair of contig pair k (dict order of hhx_ingest_fetch) in quadrant
  * q = [HH, HT, TH, TT], INT64_MAX if the quadrant is empty.  Needs hhx_ingest_keep_pairs. */
