@@ -406,6 +406,10 @@ int select_middle(const u64 *vals, i64 count, u64 *lo, u64 *hi) {
     return 0;
 }
 
+// measurement knobs (hhx_tune): the largest block of the one-workgroup path, the cells of an upload / apply chunk.  Defaults: the constants above.
+i32 small_limit() { return (i32)std::max<i64>(0, std::min<i64>(PN_SMALL, tune_get("plotnorm_small", PN_SMALL))); }
+i64 chunk_cells() { return std::max<i64>(1, tune_get("plotnorm_chunk_cells", PN_CHUNK_CELLS)); }
+
 PnVec vecs_of(hhx_plotnorm *h, double *x, i32 lo) {
     double *w = h->vec.p + lo;
     const i64 n = h->n;
@@ -496,7 +500,7 @@ extern "C" int hhx_plotnorm_create(const i64 *matrix, i32 n, hhx_plotnorm **out,
     if (n <= 0 || !matrix) return fail("hhx_plotnorm_create: bad arguments");
     hhx_plotnorm *h = new hhx_plotnorm();
     h->n = n;
-    const i64 cells = (i64)n * n, rows_per = std::max<i64>(1, PN_CHUNK_CELLS / n);
+    const i64 cells = (i64)n * n, rows_per = std::max<i64>(1, chunk_cells() / n);
     DevBuf<i64> stage;
     DevBuf<long long> mnmx;
     DevBuf<int> flag;
@@ -569,9 +573,10 @@ extern "C" int hhx_plotnorm_balance(hhx_plotnorm *h, i32 *outer, i64 *mvp, i32 *
     const i32 nb = h->n_blocks;
     for (i32 g = 0; g <= nb; ++g) { outer[g] = 0; mvp[g] = 0; status[g] = 0; }
     HHX_HIP(hipMemsetAsync(h->x_blk.p, 0, sizeof(double) * h->n, g_stream));
+    const i32 small_max = small_limit();
     std::vector<i32> small;
     for (i32 g = 0; g < nb; ++g)
-        if (h->hi[g] > h->lo[g] && h->hi[g] - h->lo[g] <= PN_SMALL) small.push_back(g);
+        if (h->hi[g] > h->lo[g] && h->hi[g] - h->lo[g] <= small_max) small.push_back(g);
     if (!small.empty()) {
         DevBuf<i32> list, d_outer, d_status;
         DevBuf<i64> d_mvp;
@@ -594,7 +599,7 @@ extern "C" int hhx_plotnorm_balance(hhx_plotnorm *h, i32 *outer, i64 *mvp, i32 *
         if (bad) return 0;
     }
     for (i32 g = 0; g < nb; ++g)
-        if (h->hi[g] - h->lo[g] > PN_SMALL) {
+        if (h->hi[g] - h->lo[g] > small_max) {
             HHX_TRY(bnewt_grid(h, h->x_blk.p, h->lo[g], h->hi[g] - h->lo[g], &outer[g], &mvp[g], &status[g]));
             if (status[g]) return 0;
         }
@@ -615,7 +620,7 @@ extern "C" int hhx_plotnorm_apply(hhx_plotnorm *h, double *out_host) {
     if (!h) return fail("null handle");
     if (!out_host) return fail("null pointer");
     if (!h->balanced) return fail("hhx_plotnorm_apply: no balancing has converged on this handle");
-    const i64 n = h->n, rows_per = std::max<i64>(1, PN_CHUNK_CELLS / n);
+    const i64 n = h->n, rows_per = std::max<i64>(1, chunk_cells() / n);
     DevBuf<double> stage;
     if (stage.alloc((size_t)(rows_per * n))) return 1;
     for (i64 r = 0; r < n; r += rows_per) {

@@ -65,7 +65,11 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * of one (B row, window) segment each instead of 64-entry blocks (default 15; 1, 2, 5, 11, 31: other block-tile shapes /
  * addressings); "row_order" 0 = the window-class rows as listed instead of in min-hash order; "reuse" 4 / 2 = the grouped kernel;
  * "dense_seed_hint" (the sweep's first pool sizes); "correct_agg" 1 = hhx_correct_push merges the atomic adds of the lanes of a wave that hit the
- * same word before they leave the wave (default 0: one atomic per lane; tools/correct_bench.py times both).  value INT64_MIN: back to the default.  Unset knobs fall back to the
+ * same word before they leave the wave (default 0: one atomic per lane; tools/correct_bench.py times both); "plotnorm_small" = the largest
+ * block (bins) hhx_plotnorm_balance runs inside one workgroup, clamped to [0, 512] (default 512; 0: every block is steered from the host;
+ * the two implementations sum in another order, so the blocks' x agrees within the spread the reference's bnewt shows under a permutation,
+ * step counts equal); "plotnorm_chunk_cells" = cells per upload / apply chunk of hhx_plotnorm (default 2^24, at least 1: one row per chunk;
+ * same bits).  value INT64_MIN: back to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
 int hhx_profile_enable(int on);

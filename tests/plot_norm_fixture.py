@@ -85,6 +85,24 @@ def expected_matrix(counts, sizes, x_all, x_blocks):
     return out
 
 
+def kr_block_cells(counts, sizes, x_blocks):
+    """the list behind the KR vmax (:447-450): the off-diagonal cells (x_i * A_ij) * x_j of every block, taken BEFORE the zeros are restored (:454)"""
+    A = counts + 0.00001
+    cells = [((x_blocks[lo:hi, None] * A[lo:hi, lo:hi]) * x_blocks[None, lo:hi])[~np.eye(hi - lo, dtype=bool)] for lo, hi in blocks_of(sizes)]
+    return np.concatenate(cells)
+
+
+def load_cases(golden):
+    """name -> (sizes, read-only int64 counts) of the stored cases"""
+    out = {}
+    for name in CASES:
+        sizes = golden[name + '__sizes'].tolist()
+        counts = unpack_upper(golden[name + '__upper'], n_bins(sizes))
+        counts.setflags(write=False)
+        out[name] = (sizes, counts)
+    return out
+
+
 def tolerance(perm_spread):
     """1000 x the spread the reference's own bnewt shows under a permutation of the rows and columns, at least 1e-12"""
     return max(1000.0 * float(perm_spread), 1e-12)
@@ -94,6 +112,58 @@ def rel_diff(got, want):
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
     scale = np.maximum(np.abs(want), np.finfo(np.float64).tiny)
     return float(np.max(np.abs(got - want) / scale)) if got.size else 0.0
+
+
+def bnewt(A, tol=1e-6, delta=0.1, Delta=3, g=0.9, etamax=0.1):
+    """numpy restatement of bnewt :291-404 in the precision of A -> (x, outer steps, mat-vec count MVP, lower exits, upper exits): how often an
+    inner loop left through the `delta` bound (:367-371) and through the `Delta` bound (:372-376).  MVP is the reference's own counter: its first
+    product v = x * (A @ x) is not in it."""
+    n = A.shape[0]
+    x, eta, rt, MVP, nn, lower, upper = np.ones(n, A.dtype), etamax, tol ** 2, 0, 0, 0, 0
+    v = x * (A @ x)
+    rk = 1 - v
+    rho_km1 = rout = rold = rk @ rk
+    while rout > rt:
+        nn += 1
+        assert nn <= 1000
+        k, y, innertol = 0, np.ones(n, A.dtype), max(eta ** 2 * rout, rt)
+        while rho_km1 > innertol:
+            k += 1
+            assert k <= 10000
+            if k == 1:
+                Z = rk / v
+                p = Z
+                rho_km1 = rk @ Z
+            else:
+                p = Z + (rho_km1 / rho_km2) * p
+            w = x * (A @ (x * p)) + v * p
+            alpha = rho_km1 / (p @ w)
+            ap = alpha * p
+            ynew = y + ap
+            if ynew.min() <= delta:
+                ind = ap < 0
+                y = y + ((delta - y[ind]) / ap[ind]).min() * ap
+                lower += 1
+                break
+            if ynew.max() >= Delta:
+                ind = ynew > Delta
+                y = y + ((Delta - y[ind]) / ap[ind]).min() * ap
+                upper += 1
+                break
+            y, rk, rho_km2 = ynew, rk - alpha * w, rho_km1
+            Z = rk / v
+            rho_km1 = rk @ Z
+        x = x * y
+        v = x * (A @ x)
+        rk = 1 - v
+        rho_km1 = rout = rk @ rk
+        MVP += k + 1
+        rat, rold, eta_o = rout / rold, rout, eta
+        eta = g * rat
+        if g * eta_o ** 2 > 0.1:
+            eta = max(eta, g * eta_o ** 2)
+        eta = max(min(eta, etamax), tol * 0.5 / np.sqrt(rout))
+    return x, nn, MVP, lower, upper
 
 
 def load_reference_plot(scripts=REFERENCE_SCRIPTS, name='_haphic_plot_reference_private'):

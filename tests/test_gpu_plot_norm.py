@@ -21,13 +21,12 @@ def golden():
 
 @pytest.fixture(scope='module')
 def cases(golden):
-    out = {}
-    for name in nf.CASES:
-        sizes = golden[name + '__sizes'].tolist()
-        counts = nf.unpack_upper(golden[name + '__upper'], nf.n_bins(sizes))
-        counts.setflags(write=False)
-        out[name] = (sizes, counts)
-    return out
+    return nf.load_cases(golden)
+
+
+# (case, block index) -> evidence: a block whose step counts may differ from the reference's because a loop comparison of the restatement sits
+# within a few ulp of its threshold at the step where the counts part (at most one of the 25 blocks).  None is needed.
+STEP_COUNT_EXEMPT = {}
 
 
 def _run(counts, sizes, mode, manual_vmax=-1):
@@ -51,6 +50,13 @@ def test_kr_against_the_reference(golden, cases, name):
         outer, mvp, status = pn.balance()
         assert not status.any()
         print(name, 'outer', outer.tolist(), 'reference', golden[name + '__outer'].tolist(), 'MVP', mvp.tolist(), 'reference A @ v', golden[name + '__mvp'].tolist())
+        # the route, not only its fixed point: a wrong beta, step to the bound or rk update converges to the same x by other steps.  The
+        # reference's counts do not move under a permutation of the matrix (tests/test_plot_norm.py pins the restatement to them); its
+        # generator counts the very first product too, the device counts bnewt's own MVP.
+        assert len(STEP_COUNT_EXEMPT) <= 1
+        for k in range(len(outer)):
+            if (name, k) not in STEP_COUNT_EXEMPT:
+                assert outer[k] == golden[name + '__outer'][k] and mvp[k] == golden[name + '__mvp'][k] - 1, (name, k)
         x_all, x_blocks = pn.x()
     finally:
         pn.destroy()
@@ -70,10 +76,13 @@ def test_kr_against_the_reference(golden, cases, name):
     # the device's own x through the host formula: the same bits (multiplication order of d @ A @ d)
     assert got.tobytes() == nf.expected_matrix(counts, sizes, x_all, x_blocks).tobytes()
     want_vmax = golden[name + '__vmax_KR']
+    # the host's median of the cells the host formula gives from the device's own x_blocks, before the zeros are restored: the same bits
+    cells = nf.kr_block_cells(counts, sizes, x_blocks)
     if np.isnan(want_vmax):
-        assert np.isnan(vmax)
+        assert np.isnan(vmax) and not len(cells)
     else:
         assert abs(vmax - want_vmax) <= tol * want_vmax
+        assert vmax.tobytes() == (np.median(cells) * nf.VMAX_COEF).tobytes()
     manual = _run(counts, sizes, 'KR', manual_vmax=3)
     assert manual[1] == 3 and type(manual[1]) is int and manual[0].tobytes() == got.tobytes()
 

@@ -20,54 +20,6 @@ def golden():
     return load_golden('plot_norm.npz')
 
 
-def bnewt(A, tol=1e-6, delta=0.1, Delta=3, g=0.9, etamax=0.1):
-    """numpy restatement of bnewt :291-404 -> (x, outer steps, mat-vec count MVP)"""
-    n = A.shape[0]
-    x, eta, rt, MVP, nn = np.ones(n), etamax, tol ** 2, 0, 0
-    v = x * (A @ x)
-    rk = 1 - v
-    rho_km1 = rout = rold = rk @ rk
-    while rout > rt:
-        nn += 1
-        assert nn <= 1000
-        k, y, innertol = 0, np.ones(n), max(eta ** 2 * rout, rt)
-        while rho_km1 > innertol:
-            k += 1
-            assert k <= 10000
-            if k == 1:
-                Z = rk / v
-                p = Z
-                rho_km1 = rk @ Z
-            else:
-                p = Z + (rho_km1 / rho_km2) * p
-            w = x * (A @ (x * p)) + v * p
-            alpha = rho_km1 / (p @ w)
-            ap = alpha * p
-            ynew = y + ap
-            if ynew.min() <= delta:
-                ind = ap < 0
-                y = y + ((delta - y[ind]) / ap[ind]).min() * ap
-                break
-            if ynew.max() >= Delta:
-                ind = ynew > Delta
-                y = y + ((Delta - y[ind]) / ap[ind]).min() * ap
-                break
-            y, rk, rho_km2 = ynew, rk - alpha * w, rho_km1
-            Z = rk / v
-            rho_km1 = rk @ Z
-        x = x * y
-        v = x * (A @ x)
-        rk = 1 - v
-        rho_km1 = rout = rk @ rk
-        MVP += k + 1
-        rat, rold, eta_o = rout / rold, rout, eta
-        eta = g * rat
-        if g * eta_o ** 2 > 0.1:
-            eta = max(eta, g * eta_o ** 2)
-        eta = max(min(eta, etamax), tol * 0.5 / np.sqrt(rout))
-    return x, nn, MVP
-
-
 def test_header_bindings_and_exports_carry_plotnorm():
     from haphic_amd import _lib
     header = open(os.path.join(ROOT, 'include', 'haphic_hip.h')).read()
@@ -220,7 +172,7 @@ def test_block_bounds_are_the_reference_ones():
 
 @pytest.mark.parametrize('name', list(nf.CASES))
 def test_fixture_self_check(golden, name):
-    """the stored x against the restatement of bnewt above, within the case's tolerance; the expected-matrix helper the GPU tests use against
+    """the stored x against the restatement of bnewt (plot_norm_fixture.bnewt), within the case's tolerance; the expected-matrix helper the GPU tests use against
     the reference's own matrix, bit for bit, where it is stored"""
     sizes = golden[name + '__sizes'].tolist()
     assert sizes == nf.CASES[name][0] and int(golden['bin_size']) == nf.BIN_SIZE and float(golden['vmax_coef']) == nf.VMAX_COEF
@@ -231,11 +183,11 @@ def test_fixture_self_check(golden, name):
     assert 1e-12 <= tol < 1e-9
     A = counts + 0.00001
     x_all, x_blocks = golden[name + '__x_all'], golden[name + '__x_blocks']
-    x, outer, mvp = bnewt(A)
+    x, outer, mvp, _, _ = nf.bnewt(A)
     assert nf.rel_diff(x, x_all) <= tol
     steps = [(outer, mvp)]
     for lo, hi in nf.blocks_of(sizes):
-        xg, o, m = bnewt(A[lo:hi, lo:hi])
+        xg, o, m, _, _ = nf.bnewt(A[lo:hi, lo:hi])
         assert nf.rel_diff(xg, x_blocks[lo:hi]) <= tol
         steps.insert(-1, (o, m))
     print(name, 'outer / MVP (restatement):', steps, ' reference outer:', golden[name + '__outer'].tolist())
@@ -250,10 +202,39 @@ def test_fixture_self_check(golden, name):
         assert name + '__matrix_KR' not in golden
     assert ((want == 0) == (counts == 0)).all()
     # vmax of the KR mode: the median is taken BEFORE the zeros are restored (:447-450 runs before :454)
-    cells = [((x_blocks[lo:hi, None] * A[lo:hi, lo:hi]) * x_blocks[None, lo:hi])[~np.eye(hi - lo, dtype=bool)] for lo, hi in nf.blocks_of(sizes)]
-    cells = np.concatenate(cells)
+    cells = nf.kr_block_cells(counts, sizes, x_blocks)
     want_vmax = golden[name + '__vmax_KR']
     if len(cells):
         assert (np.median(cells) * nf.VMAX_COEF).tobytes() == want_vmax.tobytes()
     else:
         assert np.isnan(want_vmax)
+
+
+# the blocks whose restated bnewt leaves an inner loop through the lower bound (ynew.min() <= delta :367); (lo, hi) of the whole matrix is (0, n)
+LOWER_EXIT_BLOCKS = {('n753', (500, 750)), ('n2055', (0, 300)), ('n2055', (300, 500)), ('n2055', (500, 750)), ('n2055', (750, 2052)), ('n2055', (0, 2055))}
+SMALL_PATH_MAX = 512            # PN_SMALL of csrc/hhx_plotnorm.hip: larger blocks, and every whole matrix, take the host-steered loop
+
+
+def test_fixture_reaches_both_exits_on_both_paths(golden):
+    """what the GPU tests rely on: the restatement's step counts are the stored ones for every block (outer == __outer, MVP == __mvp - 1: the
+    generator's counter sees the very first product too), and both early exits of the inner loop are taken by a block of the one-workgroup
+    path and by one of the host-steered path"""
+    lower, upper, n_blocks = set(), set(), 0
+    for name, (sizes, counts) in nf.load_cases(golden).items():
+        A = counts + 0.00001
+        spans = nf.blocks_of(sizes) + [(0, len(A))]
+        for k, (lo, hi) in enumerate(spans):
+            _, outer, mvp, n_lower, n_upper = nf.bnewt(A[lo:hi, lo:hi])
+            assert outer == golden[name + '__outer'][k] and mvp == golden[name + '__mvp'][k] - 1, (name, lo, hi)
+            grid = hi - lo > SMALL_PATH_MAX or k == len(spans) - 1
+            if n_lower:
+                lower.add((name, (lo, hi)))
+            if n_upper:
+                upper.add((name, (lo, hi), grid))
+            n_blocks += 1
+    assert n_blocks == 25 and lower == LOWER_EXIT_BLOCKS
+    both = {(name, span, grid) for name, span, grid in upper if (name, span) in lower}
+    assert ('n753', (500, 750), False) in both                                  # a block of at most 512 bins
+    assert ('n2055', (750, 2052), True) in both and ('n2055', (0, 2055), True) in both           # a large block and a whole matrix
+    for name in ('n110', 'n753'):                                               # the cases the path tests run through both implementations
+        assert any(u[0] == name and not u[2] for u in upper) and any(u[0] == name and u[2] for u in upper)
