@@ -116,13 +116,15 @@ __global__ __launch_bounds__(256) void k_map_records(SrcPairs<COMBINED, POS> src
             if (lh[t]) atomicAdd(&H.hist[t], (unsigned long long)lh[t]);
     }
 }
+// workgroups of the map at most (HHX_MAP_GRID, read at every launch: a test walks the grid-stride loop with a few thousand pairs)
+inline i64 map_grid_cap() { const char *e = getenv("HHX_MAP_GRID"); return e && atoll(e) > 0 ? atoll(e) : 256 * 16; }
 template <bool COMBINED, class POS>
 void launch_map(const SrcPairs<COMBINED, POS> &src, i64 n, u64 *rec, const MapHist &H) {
     // (64-bit positions — contigs beyond 2^31 bp, rare — take the scalar kernel: one pair per lane)
     const bool aligned = sizeof(POS) == 4 && ((((uintptr_t)src.id1) | ((uintptr_t)src.id2) | ((uintptr_t)src.pos1) | ((uintptr_t)src.pos2) | ((uintptr_t)rec)) & 15) == 0;
     const i64 bulk = aligned && src.t.n_ctg > 0 ? (n & ~(i64)3) : 0;
-    if (bulk) k_map_records<COMBINED, true, POS><<<(unsigned)std::max<i64>(1, std::min<i64>((bulk / 4 + 255) / 256, 256 * 16)), 256, 0, g_stream>>>(src, 0, bulk, rec, H);
-    if (bulk < n) k_map_records<COMBINED, false, POS><<<(unsigned)std::max<i64>(1, std::min<i64>((n - bulk + 255) / 256, 256 * 16)), 256, 0, g_stream>>>(src, bulk, n, rec, H);
+    if (bulk) k_map_records<COMBINED, true, POS><<<(unsigned)std::max<i64>(1, std::min<i64>((bulk / 4 + 255) / 256, map_grid_cap())), 256, 0, g_stream>>>(src, 0, bulk, rec, H);
+    if (bulk < n) k_map_records<COMBINED, false, POS><<<(unsigned)std::max<i64>(1, std::min<i64>((n - bulk + 255) / 256, map_grid_cap())), 256, 0, g_stream>>>(src, bulk, n, rec, H);
 }
 struct SrcMapped {
     typedef u32 w1_t;
@@ -212,6 +214,7 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
     const u32 b1 = min(A.n_buckets, b0 + A.buckets_per_wg);
     if (b0 >= A.n_buckets) return;
     unsigned long long &s_base = *reinterpret_cast<unsigned long long *>(s_scan + 16);   // dynamic LDS only: the 160 KB attribute needs it all
+    u32 &s_nkeys = s_scan[AG_T / HHX_WAVE + 1];      // first insertions of a single-pass attempt (s_scan has 16 words, the scan uses 8)
     // A bucket is ~1k records (two per thread): a chain of dependent round trips — bounds, records, the output
     // reservation, the stores — so the kernel is latency bound.  The first AG_R records per thread of the NEXT bucket are
     // loaded into registers before the current bucket's insert / scan / store phases begin.
@@ -221,6 +224,7 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
     unsigned long long rbn = b + 1 < b1 ? A.base[b + 1] : 0ull, ren = b + 1 < b1 ? A.base[b + 2] : 0ull;      // bounds run two buckets ahead
     u64 rec_r[AG_R];
     u32 ord_r[AG_R];
+    bool single = true;                            // the previous bucket's distinct keys fitted one table pass (see below)
     u32 st_full = 0, st_flank = 0;                 // this thread's share of A.stats: the rows pass through its registers on their way out
     u64 st_max = 0;
 #pragma unroll
@@ -255,20 +259,30 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
         // every record through HBM again instead.)
         int sbits = 0;
         while ((n >> sbits) > 1024 && sbits < 4) ++sbits;
-        const u64 per_sub = (n >> sbits) + 1;
+        // The table is full when it holds too many distinct KEYS, not too many records: a bucket whose records are all in
+        // registers (n <= AG_R * AG_T) is first taken in ONE pass over the whole table, the first insertions counted as they
+        // happen.  More than AG_CAP / 2 of them: the attempt is abandoned after its insert phase (nothing reserved, nothing
+        // stored) and the bucket goes through the sub-passes.  `single` carries the outcome to the workgroup's next bucket,
+        // so that a stream of keys seen once (low coverage) pays one abandoned attempt per workgroup, not one per bucket.
+        bool attempt = sbits && n <= (u64)AG_R * AG_T && single;
+        int sb = attempt ? 0 : sbits;                  // hash bits that pick the sub-pass, as in effect
+        u32 held = 0;                                  // distinct keys of this bucket's completed sub-passes
+        for (u32 sub = 0; sub < (1u << sb); ++sub) {
+        const u64 per_sub = (n >> sb) + 1;
         u32 tsize = AG_CAP;
         if (2 * per_sub <= AG_CAP) { tsize = 64; while (tsize < 2 * per_sub) tsize <<= 1; }
-        for (u32 sub = 0; sub < (1u << sbits); ++sub) {
         for (u32 s = tid; s < tsize; s += AG_T) {
             s_key[s] = EMPTY_KEY; s_of[s] = ORD_NONE; s_ok[s] = ORD_NONE;
 #pragma unroll
             for (int c = 0; c < 5; ++c) s_cnt[c * AG_CAP + s] = 0;
         }
+        if (tid == 0) s_nkeys = 0;
         lds_barrier();
+        u32 wins = 0;                                  // first insertions by this thread
         auto insert = [&](const u64 rec, const u32 ord) {
             const u64 key = rec & KEY_MASK;
             const u64 h = mix64(key);
-            if (sbits && (u32)((h << A.total_bits) >> (64 - sbits)) != sub) return;
+            if (sb && (u32)((h << A.total_bits) >> (64 - sb)) != sub) return;
             u32 slot = (u32)h & (tsize - 1);
             u32 probe = 0;
             for (; probe < tsize; ++probe) {
@@ -277,6 +291,7 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
                 if (cur == key) break;
                 if (cur == EMPTY_KEY) {
                     const u64 old = atomicCAS((unsigned long long *)&s_key[slot], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
+                    wins += old == EMPTY_KEY;
                     if (old == EMPTY_KEY || old == key) break;
                 }
                 slot = (slot + 1) & (tsize - 1);
@@ -307,6 +322,10 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
         for (int u = 0; u < AG_R; ++u)
             if (rec_r[u] != EMPTY_KEY) insert(rec_r[u], ord_r[u]);
         for (unsigned long long i = rb + tid + (unsigned long long)AG_R * AG_T; i < re; i += AG_T) insert(A.rec[i], A.ord[i]);
+        if (attempt) {
+            const u32 w = (u32)wave_sum_i32((i32)wins);
+            if (lane == 0 && w) atomicAdd(&s_nkeys, w);
+        }
         lds_barrier();
         // The prefetched registers are pinned HERE, before this bucket's reservation atomic and output stores are issued:
         // vmcnt completes in order, so a wait for the prefetch placed after the stores (at the loop latch, where the compiler
@@ -314,6 +333,17 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
 #pragma unroll
         for (int u = 0; u < AG_R; ++u) { asm volatile("" : "+v"(rec_n[u])); asm volatile("" : "+v"(ord_n[u])); }
         asm volatile("" : "+v"(rbn2)); asm volatile("" : "+v"(ren2));
+        if (attempt) {
+            // every thread reads the same count behind the barrier that ended the insert phase: one decision per workgroup
+            attempt = false;
+            if (s_nkeys > AG_CAP / 2) {
+                single = false;
+                sb = sbits;
+                sub = ~0u;                             // the sub-passes start at 0
+                lds_barrier();                         // s_nkeys has been read by every wave before the next clear resets it
+                continue;
+            }
+        }
         // compaction: contiguous chunk of slots per thread, block exclusive scan of the occupied counts
         const u32 per = tsize >= AG_T ? tsize / AG_T : 1;
         const u32 s0 = min(tsize, (u32)tid * per), s1 = min(tsize, s0 + per);
@@ -330,6 +360,7 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
         u32 woff = 0, total = 0;
 #pragma unroll
         for (int w = 0; w < AG_T / HHX_WAVE; ++w) { if (w < wave) woff += s_scan[w]; total += s_scan[w]; }
+        held += total;
         if (tid == 0) s_base = total ? atomicAdd(A.out_cursor, (unsigned long long)total) : 0ull;
         lds_barrier();
         unsigned long long o = s_base + woff + incl - mine;
@@ -355,6 +386,7 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
         }
         lds_barrier();
         }   // sub-passes
+        if (sbits) single = held <= AG_CAP / 2;        // (sub-passes that held few keys: the next bucket tries the single pass again)
         } else {   // empty bucket: same pins, so that no path reaches the latch with loads pending (see above)
 #pragma unroll
             for (int u = 0; u < AG_R; ++u) { asm volatile("" : "+v"(rec_n[u])); asm volatile("" : "+v"(ord_n[u])); }
@@ -394,7 +426,7 @@ struct Payload {            // MODE 1 only
 };
 
 // bucket bits of the group-by of n_items records (attempt: after an LDS overflow, more buckets) and the radix bits per level.
-// Up to 2048 records a bucket (k_aggregate takes such a bucket in two sub-passes over the L2-resident records) and up to 9 bits a level: 500 M
+// Up to 2048 records a bucket (k_aggregate takes such a bucket in one table pass while its distinct keys fit half the table, else in two sub-passes over the register-resident records) and up to 9 bits a level: 500 M
 // pairs are 2^18 buckets = TWO radix levels of 9 bits instead of 2^19 = three of 6 + 6 + 7 — one pass of the 6 GB of records through HBM less.
 // Measured at C3 (tools/ingest_probe.py, profiles/r06_ingest_levels_probe.json): 1024 / 7 (rounds 1-6) 39.5 ms, 2048 / 9 37.1 ms, 4096 / 9 38.5 ms
 // (four sub-passes: the aggregation 7.6 -> 9.1 ms), 1024 / 9 40.1 ms (still three levels).
@@ -405,6 +437,10 @@ inline int ingest_total_bits(i64 n_items, int attempt) {
     while ((n_items >> total_bits) > ingest_per_bucket() && total_bits < 24) ++total_bits;
     return std::min(24, total_bits + 2 * attempt);
 }
+
+// workgroups of the aggregation at most (HHX_AGG_WGS, read at every launch: a test gives one workgroup several of a few dozen buckets,
+// which is what carries k_aggregate's single-pass choice from one bucket to the next)
+inline u32 agg_wg_cap() { const char *e = getenv("HHX_AGG_WGS"); return e && atoi(e) > 0 ? (u32)atoi(e) : 1024u; }
 
 // hist0: the level-1 histogram of the records counted by their producer for attempt 0's bucket bits (or null)
 template <class Src, int MODE>
@@ -434,7 +470,7 @@ int build_run(const Src &src, i64 n_items, const Payload &pl, u64 ord_base, Link
         if (MODE == 0 && attempt == 0) prof_count("ingest_records", n_valid);
         const u32 n_buckets = part.n_buckets;
         // ---- aggregate
-        const u32 n_wg = std::min<u32>(n_buckets, 1024);
+        const u32 n_wg = std::min<u32>(n_buckets, agg_wg_cap());
         AggParams A{};
         A.rec = part.w0.p; A.ord = part.w1.p; A.base = (const unsigned long long *)part.base.p;
         A.n_buckets = n_buckets; A.buckets_per_wg = (n_buckets + n_wg - 1) / n_wg;
