@@ -165,6 +165,21 @@ struct hhx_links_operand {
 #ifdef __HIPCC__
 #define HHX_WAVE 64
 
+namespace hhx {
+// Raises the dynamic-LDS limit of the kernels to `bytes` on the current device, once per device (the attribute is per device: keyed on
+// the current ordinal; one "device it was set for" per list of kernels).  HHX_TRY((raise_dynamic_lds<k_a, k_b<true>>()));
+template <auto... Kernels>
+inline int raise_dynamic_lds(int bytes = 160 * 1024) {
+    static int set_for = -1;
+    int dev = 0;
+    HHX_HIP(hipGetDevice(&dev));
+    if (set_for == dev) return 0;
+    for (const void *k : {(const void *)Kernels...}) HHX_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    set_for = dev;
+    return 0;
+}
+}  // namespace hhx
+
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, HHX_WAVE);

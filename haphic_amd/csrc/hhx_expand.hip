@@ -1445,28 +1445,149 @@ __device__ __forceinline__ float quot_f32(double a, double d, double rd) {
     const float q = quot_fast(a, rd, &exact);
     return __builtin_expect(exact, 1) ? q : (float)(a / d);
 }
-// LDS: the reduction scratch of ExLds plus a second i32 row (the scan's wave totals are written while the argmax's are still read)
 __device__ __forceinline__ float de_load(const float *base, i32 idx) {        // uniform base + 32-bit byte offset (no 64-bit address arithmetic per load)
     return *(const float *)((const char *)base + (u32)(idx << 2));
 }
-__host__ __device__ inline size_t dense_epi_sw_lds_bytes(i32 cap) { return (size_t)((cap + 31) & ~31) * 4 + (size_t)EX_WAVES_MAX * (8 + 4 + 4 + 4) + 8 + 8; }
+constexpr int MULTI_MAX = 8;            // k_dense_epilogue_multi: inflations per pass
+constexpr int MULTI_LREG = 11;          // of a thread's DE_PER logarithms, this many stay in registers; the others wait in LDS (conflict-free: slot tid + i * 1024)
+// LDS of the tuned epilogues (k_dense_epilogue_sw, k_dense_epilogue_multi): the reduction scratch of ExLds plus a second i32 row (the
+// scan's wave totals are written while the argmax's are still read), then the window's slots; the multi kernel adds the running sums
+// of its inflations and, behind the slots, the logarithms that do not stay in registers
+struct DeLds {
+    double *red_d;       // [EX_WAVES_MAX]
+    double *s_run_sh;    // [MULTI_MAX] (multi)
+    i64 *bcast;          // [1] block broadcast slot
+    i32 *red_i;          // [EX_WAVES_MAX]
+    float *red_f;        // [EX_WAVES_MAX]
+    i32 *red_s;          // [EX_WAVES_MAX]
+    float *slot;         // [cap rounded up to 32]
+    double *l_sh;        // [DE_PER - MULTI_LREG][EX_T_WIN] (multi)
+};
+struct DeLdsOff { size_t red_d, s_run_sh, bcast, red_i, red_f, red_s, slot, l_sh, bytes; };
+__host__ __device__ constexpr DeLdsOff de_lds_off(i32 cap, bool multi) {
+    DeLdsOff o{};
+    size_t p = 0;
+    o.red_d = p; p += EX_WAVES_MAX * 8;
+    o.s_run_sh = p; p += multi ? MULTI_MAX * 8 : 0;
+    o.bcast = p; p += 8;
+    o.red_i = p; p += EX_WAVES_MAX * 4;
+    o.red_f = p; p += EX_WAVES_MAX * 4;
+    o.red_s = p; p += EX_WAVES_MAX * 4 + 8;                 // (+ the two words ExLds keeps for ctr)
+    o.slot = p; p += (size_t)((cap + 31) & ~31) * 4;
+    p = (p + 15) & ~(size_t)15;
+    o.l_sh = p; p += multi ? (size_t)(DE_PER - MULTI_LREG) * EX_T_WIN * 8 : 0;
+    o.bytes = p;
+    return o;
+}
+__device__ __forceinline__ DeLds de_carve(unsigned char *smem, i32 cap, bool multi) {
+    const DeLdsOff o = de_lds_off(cap, multi);
+    DeLds l;
+    l.red_d = (double *)(smem + o.red_d); l.s_run_sh = (double *)(smem + o.s_run_sh); l.bcast = (i64 *)(smem + o.bcast);
+    l.red_i = (i32 *)(smem + o.red_i); l.red_f = (float *)(smem + o.red_f); l.red_s = (i32 *)(smem + o.red_s);
+    l.slot = (float *)(smem + o.slot); l.l_sh = (double *)(smem + o.l_sh);
+    return l;
+}
+__host__ __device__ constexpr size_t dense_epi_sw_lds_bytes(i32 cap) { return de_lds_off(cap, false).bytes; }
+__host__ __device__ constexpr size_t dense_epi_multi_lds_bytes(i32 cap) { return de_lds_off(cap, true).bytes; }
+// the layout the two kernels carved by hand before they shared it, number for number: launch sizes and bank positions depend on it
+constexpr bool de_lds_unchanged(i32 cap) {
+    const size_t slots = (size_t)((cap + 31) & ~31) * 4, sw = slots + (size_t)EX_WAVES_MAX * (8 + 4 + 4 + 4) + 8 + 8;
+    const size_t l_sh = (sw + MULTI_MAX * 8 + 15) & ~(size_t)15;
+    const DeLdsOff a = de_lds_off(cap, false), b = de_lds_off(cap, true);
+    return a.red_d == 0 && a.bcast == 128 && a.red_i == 136 && a.red_f == 200 && a.red_s == 264 && a.slot == 336 && a.bytes == sw &&
+           b.red_d == 0 && b.s_run_sh == 128 && b.bcast == 192 && b.red_i == 200 && b.red_f == 264 && b.red_s == 328 && b.slot == 400 &&
+           b.l_sh == l_sh && b.bytes == l_sh + (size_t)(DE_PER - MULTI_LREG) * EX_T_WIN * 8;
+}
+static_assert(de_lds_unchanged(64) && de_lds_unchanged(2112) && de_lds_unchanged(4032) && de_lds_unchanged(20352), "LDS layout of the dense epilogues");
+
+// The second half of a (row, window) step of the tuned epilogues, for one inflation: the thread's partial sum s, its best (bq, bs) and
+// its `maybe` bits over the owned slots [s0, s1) (window columns c0 + slot; the slots hold p, swizzled by gm) become the window sum and
+// the window maximum (block_sum_f64 and block_argmax in one exchange: the same wave trees, the same order over the waves), the exact
+// survivor test against the running sum, block_excl_scan_i32 of the survivor counts, the candidate segment of the (row, window) and
+// its entries.  Returns the running row sum including this window (s_prev: the windows before; 0 at window 0).  Three lds_barrier()s;
+// the caller places one more before the slots, the reduction rows and the broadcast word are written again.
+// s_run_sh / s_run_row (the multi kernel; null in k_dense_epilogue_sw, which carries the sum in registers): thread 0 also leaves the
+// sum in this LDS word for the next window and, at the last window, in the row's entry of s_run — there, next to the segment
+// table's stores, and not after the call: with the sum alive across the emission the multi kernel's register allocation moves its
+// spills into the log2 loop (14 -> 128 scratch instructions, the pass 13 % slower on the MI355X).
+struct DeDest {                         // where the candidates of this inflation go
+    i32 *cand_col; float *cand_val; i64 cand_cap;
+    unsigned long long *cursors;        // [0] candidate cursor [2] overflow flag
+    i64 *g_win_off; i32 *g_win_cnt;     // [n_rows][n_win] candidate segment of every (row, window)
+};
+__device__ __forceinline__ double de_step_tail(const DeLds l, int tid, int lane, int wave, double s, float bq, i32 bs, u32 maybe, i32 s0, i32 s1, i32 c0, i32 gm, double s_prev,
+                                               float thr, const DeDest &d, size_t win_at, double *s_run_sh, double *s_run_row) {
+    s = wave_sum_f64(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float oq = __shfl_down(bq, o, HHX_WAVE);
+        const i32 oc = __shfl_down(bs, o, HHX_WAVE);
+        if (oq > bq || (oq == bq && oc < bs)) { bq = oq; bs = oc; }
+    }
+    if (lane == 0) { l.red_d[wave] = s; l.red_f[wave] = bq; l.red_i[wave] = bs; }
+    lds_barrier();
+    double sw = l.red_d[0];
+    bq = l.red_f[0]; bs = l.red_i[0];
+#pragma unroll 3
+    for (int k = 1; k < EX_T_WIN / HHX_WAVE; ++k) {       // (a full unroll holds 16 x 4 registers at once)
+        sw += l.red_d[k];
+        if (l.red_f[k] > bq || (l.red_f[k] == bq && l.red_i[k] < bs)) { bq = l.red_f[k]; bs = l.red_i[k]; }
+    }
+    const double s_run = s_prev + sw;
+    // survivors against the running sum: one bit per owned slot
+    const double rs = 1.0 / s_run;
+    u32 keep = (bs >= s0 && bs < s1) ? 1u << (bs - s0) : 0u;          // the window maximum stays, whatever its value
+    while (maybe) {
+        const int k = __ffs(maybe) - 1;
+        maybe &= maybe - 1;
+        if (quot_f32((double)l.slot[de_swz(s0 + k, gm)], s_run, rs) >= thr) keep |= 1u << k;
+    }
+    const i32 cnt = __popc(keep);
+    i32 incl = cnt;
+#pragma unroll
+    for (int o = 1; o < HHX_WAVE; o <<= 1) {
+        const i32 t = __shfl_up(incl, o, HHX_WAVE);
+        if (lane >= o) incl += t;
+    }
+    if (lane == HHX_WAVE - 1) l.red_s[wave] = incl;
+    lds_barrier();
+    i32 off = 0, total = 0;
+#pragma unroll 4
+    for (int k = 0; k < EX_T_WIN / HHX_WAVE; ++k) { if (k < wave) off += l.red_s[k]; total += l.red_s[k]; }
+    off += incl - cnt;
+    if (tid == 0) {
+        i64 base = 0;
+        if (total) {
+            base = (i64)atomicAdd(&d.cursors[0], (unsigned long long)total);
+            if (base + total > d.cand_cap) { atomicExch(&d.cursors[2], 1ull); base = -1; }
+        }
+        d.g_win_off[win_at] = base;
+        d.g_win_cnt[win_at] = base < 0 ? 0 : total;
+        *l.bcast = base;
+        if (s_run_sh) { *s_run_sh = s_run; if (s_run_row) *s_run_row = s_run; }        // (every lane read the sum of the windows before ahead of the first barrier above)
+    }
+    lds_barrier();
+    const i64 base = *l.bcast;
+    if (base >= 0 && total) {
+        i64 o = base + off;
+        while (keep) {
+            const int k = __ffs(keep) - 1;
+            keep &= keep - 1;
+            d.cand_col[o] = c0 + s0 + k;
+            d.cand_val[o] = l.slot[de_swz(s0 + k, gm)];
+            ++o;
+        }
+    }
+    return s_run;
+}
 // PF: one workgroup per CU (128 registers a lane) that loads the window of step k + 1 into registers while step k is reduced — the
 // general inflation, whose pow() needs the registers anyway; !PF: two workgroups per CU (64 registers), each loading its window at
 // the start of the step — inflation 2 (measured: 28 ms against 32.5 ms with the prefetch and one workgroup).
 template <bool SQUARE, bool PF>
 __global__ __launch_bounds__(EX_T_WIN, PF ? 4 : 8) void k_dense_epilogue_sw(ExParams P, const DenseSrc S, i32 cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *red_d; i64 *bcast; i32 *red_i, *red_s; float *red_f, *slot;
-    {
-        unsigned char *p = smem;
-        red_d = (double *)p; p += EX_WAVES_MAX * 8;
-        bcast = (i64 *)p; p += 8;
-        red_i = (i32 *)p; p += EX_WAVES_MAX * 4;
-        red_f = (float *)p; p += EX_WAVES_MAX * 4;
-        red_s = (i32 *)p; p += EX_WAVES_MAX * 4;
-        p += 8;
-        slot = (float *)p;                                  // [cap rounded up to 32] floats
-    }
+    const DeLds l = de_carve(smem, cap, false);
+    float *slot = l.slot;
     const int tid = threadIdx.x, lane = lane_id(), wave = tid / HHX_WAVE;
     i32 nnzc = 0;                                           // at most rows per workgroup x n_cols slots: below 2^31
     // The (row, window) steps of this workgroup in one sequence (every barrier below orders LDS only: a __syncthreads() would wait
@@ -1509,7 +1630,7 @@ __global__ __launch_bounds__(EX_T_WIN, PF ? 4 : 8) void k_dense_epilogue_sw(ExPa
         // (float(p / S) is monotone in p and in 1 / S): the pass over the slots notes the others (a bit per owned slot), and the
         // exact test after the exchange visits those alone — every present slot in window 0, a handful of slots in the later ones.
         const double ts = (double)P.thr * s_run;            // s_run: still the sum of the windows before (unused at wv == 0)
-        const float lo_p = (wv > 0 && !P.raw && ts >= 0x1p-100 && ts <= 0x1p100) ? (float)(ts * (1.0 - 0x1p-18)) : 0.0f;
+        const float lo_p = (wv > 0 && ts >= 0x1p-100 && ts <= 0x1p100) ? (float)(ts * (1.0 - 0x1p-18)) : 0.0f;
         u32 maybe = 0;
         double s = 0.0;
         i32 nz = 0;
@@ -1526,7 +1647,7 @@ __global__ __launch_bounds__(EX_T_WIN, PF ? 4 : 8) void k_dense_epilogue_sw(ExPa
                     if (b[u] != 0) {
                         const float y = __uint_as_float(b[u]);
                         const float x = div != 0.0 ? quot_f32((double)y, div, rdiv) : y;
-                        p = SQUARE ? x * x : (P.raw ? x : ex_inflate(x, P.r, P.square));
+                        p = SQUARE ? x * x : ex_inflate(x, P.r, P.square);
                         s += (double)p;
                         ++nz;
                     }
@@ -1543,68 +1664,8 @@ __global__ __launch_bounds__(EX_T_WIN, PF ? 4 : 8) void k_dense_epilogue_sw(ExPa
 #pragma unroll
             for (int i = 0; i < DE_PER; ++i) v[i] = de_load(src, min(lt + i * EX_T_WIN, wlen_n - 1));
         }
-        // block_sum_f64 and block_argmax in one exchange: the same wave trees, the same order over the waves
-        s = wave_sum_f64(s);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float oq = __shfl_down(bq, o, HHX_WAVE);
-            const i32 oc = __shfl_down(bs, o, HHX_WAVE);
-            if (oq > bq || (oq == bq && oc < bs)) { bq = oq; bs = oc; }
-        }
-        if (lane == 0) { red_d[wave] = s; red_f[wave] = bq; red_i[wave] = bs; }
-        lds_barrier();
-        double sw = red_d[0];
-        bq = red_f[0]; bs = red_i[0];
-#pragma unroll 3
-        for (int k = 1; k < EX_T_WIN / HHX_WAVE; ++k) {       // (a full unroll holds 16 x 4 registers at once)
-            sw += red_d[k];
-            if (red_f[k] > bq || (red_f[k] == bq && red_i[k] < bs)) { bq = red_f[k]; bs = red_i[k]; }
-        }
-        s_run = (wv == 0 ? 0.0 : s_run) + sw;
-        // survivors against the running sum: one bit per owned slot
-        const double rs = 1.0 / s_run;
-        u32 keep = (bs >= s0 && bs < s1) ? 1u << (bs - s0) : 0u;          // the window maximum stays, whatever its value
-        while (maybe) {
-            const int k = __ffs(maybe) - 1;
-            maybe &= maybe - 1;
-            if (P.raw || quot_f32((double)slot[de_swz(s0 + k, gm)], s_run, rs) >= P.thr) keep |= 1u << k;
-        }
-        // block_excl_scan_i32 of the survivor counts
-        const i32 cnt = __popc(keep);
-        i32 incl = cnt;
-#pragma unroll
-        for (int o = 1; o < HHX_WAVE; o <<= 1) {
-            const i32 t = __shfl_up(incl, o, HHX_WAVE);
-            if (lane >= o) incl += t;
-        }
-        if (lane == HHX_WAVE - 1) red_s[wave] = incl;
-        lds_barrier();
-        i32 off = 0, total = 0;
-#pragma unroll 4
-        for (int k = 0; k < EX_T_WIN / HHX_WAVE; ++k) { if (k < wave) off += red_s[k]; total += red_s[k]; }
-        off += incl - cnt;
-        if (tid == 0) {
-            i64 base = 0;
-            if (total) {
-                base = (i64)atomicAdd(&P.cursors[0], (unsigned long long)total);
-                if (base + total > P.cand_cap) { atomicExch(&P.cursors[2], 1ull); base = -1; }
-            }
-            P.g_win_off[(size_t)row * P.n_win + wv] = base;
-            P.g_win_cnt[(size_t)row * P.n_win + wv] = base < 0 ? 0 : total;
-            *bcast = base;
-        }
-        lds_barrier();
-        const i64 base = *bcast;
-        if (base >= 0 && total) {
-            i64 o = base + off;
-            while (keep) {
-                const int k = __ffs(keep) - 1;
-                keep &= keep - 1;
-                P.cand_col[o] = c0 + s0 + k;
-                P.cand_val[o] = slot[de_swz(s0 + k, gm)];
-                ++o;
-            }
-        }
+        const DeDest dest = {P.cand_col, P.cand_val, P.cand_cap, P.cursors, P.g_win_off, P.g_win_cnt};
+        s_run = de_step_tail(l, tid, lane, wave, s, bq, bs, maybe, s0, s1, c0, gm, wv == 0 ? 0.0 : s_run, P.thr, dest, (size_t)row * P.n_win + wv, nullptr, nullptr);
         if (wv == P.n_win - 1 && tid == 0) P.s_run[row] = s_run;
         if (!more) break;
         lds_barrier();                                      // the slots, the reduction rows and the broadcast word are rewritten by the next step
@@ -1622,33 +1683,16 @@ __global__ __launch_bounds__(EX_T_WIN, PF ? 4 : 8) void k_dense_epilogue_sw(ExPa
 // into that inflation's own candidate pool.  The same operations on the same operands in the same order as the one-inflation
 // kernel: the same bits.  The log2 is more than half of hhx_powr and the 40 GB block is read once per group instead of once per
 // inflation.
-constexpr int MULTI_MAX = 8;
 struct MultiOut {                       // one inflation of the group: its parameters and where its results go
     double r; int square, pad;
-    i32 *cand_col; float *cand_val; i64 cand_cap;
-    unsigned long long *cursors;        // [0] candidate cursor [2] overflow flag
-    i64 *g_win_off; i32 *g_win_cnt;     // [n_rows][n_win]
+    DeDest to;
     double *s_run;                      // [n_rows]
 };
-constexpr int MULTI_LREG = 11;          // of a thread's DE_PER logarithms, this many stay in registers; the others wait in LDS (conflict-free: slot tid + i * 1024)
-__host__ __device__ inline size_t dense_epi_multi_lds_bytes(i32 cap) {
-    return ((dense_epi_sw_lds_bytes(cap) + MULTI_MAX * 8 + 15) & ~(size_t)15) + (size_t)(DE_PER - MULTI_LREG) * EX_T_WIN * 8;
-}
 __global__ __launch_bounds__(EX_T_WIN, 4) void k_dense_epilogue_multi(ExParams P, const DenseSrc S, i32 cap, i32 K, const MultiOut *__restrict__ mo) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *red_d, *s_run_sh; i64 *bcast; i32 *red_i, *red_s; float *red_f, *slot;
-    {
-        unsigned char *p = smem;
-        red_d = (double *)p; p += EX_WAVES_MAX * 8;
-        s_run_sh = (double *)p; p += MULTI_MAX * 8;
-        bcast = (i64 *)p; p += 8;
-        red_i = (i32 *)p; p += EX_WAVES_MAX * 4;
-        red_f = (float *)p; p += EX_WAVES_MAX * 4;
-        red_s = (i32 *)p; p += EX_WAVES_MAX * 4;
-        p += 8;
-        slot = (float *)p;                                  // [cap rounded up to 32] floats
-    }
-    double *l_sh = (double *)(smem + ((dense_epi_sw_lds_bytes(cap) + MULTI_MAX * 8 + 15) & ~(size_t)15));      // [DE_PER - MULTI_LREG][EX_T_WIN]
+    const DeLds l = de_carve(smem, cap, true);
+    float *slot = l.slot;
+    double *s_run_sh = l.s_run_sh, *l_sh = l.l_sh;
     const int tid = threadIdx.x, lane = lane_id(), wave = tid / HHX_WAVE;
     i32 nnzc = 0;
     i32 row = S.row0 + (i32)blockIdx.x, wv = 0;
@@ -1717,69 +1761,8 @@ __global__ __launch_bounds__(EX_T_WIN, 4) void k_dense_epilogue_multi(ExParams P
                     slot[de_swz(s0 + u, gm)] = p;
                     __builtin_amdgcn_sched_barrier(0);          // one exp2 at a time: twenty interleaved ones do not fit the 128 registers next to Ls
                 }
-            s = wave_sum_f64(s);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float oq = __shfl_down(bq, o, HHX_WAVE);
-                const i32 oc = __shfl_down(bs, o, HHX_WAVE);
-                if (oq > bq || (oq == bq && oc < bs)) { bq = oq; bs = oc; }
-            }
-            if (lane == 0) { red_d[wave] = s; red_f[wave] = bq; red_i[wave] = bs; }
-            lds_barrier();
-            double sw = red_d[0];
-            bq = red_f[0]; bs = red_i[0];
-#pragma unroll 3
-            for (int j = 1; j < EX_T_WIN / HHX_WAVE; ++j) {
-                sw += red_d[j];
-                if (red_f[j] > bq || (red_f[j] == bq && red_i[j] < bs)) { bq = red_f[j]; bs = red_i[j]; }
-            }
-            const double s_run = s_prev + sw;
-            const double rs = 1.0 / s_run;
-            u32 keep = (bs >= s0 && bs < s1) ? 1u << (bs - s0) : 0u;
-            while (maybe) {
-                const int j = __ffs(maybe) - 1;
-                maybe &= maybe - 1;
-                if (quot_f32((double)slot[de_swz(s0 + j, gm)], s_run, rs) >= P.thr) keep |= 1u << j;
-            }
-            const i32 cnt = __popc(keep);
-            i32 incl = cnt;
-#pragma unroll
-            for (int o = 1; o < HHX_WAVE; o <<= 1) {
-                const i32 t = __shfl_up(incl, o, HHX_WAVE);
-                if (lane >= o) incl += t;
-            }
-            if (lane == HHX_WAVE - 1) red_s[wave] = incl;
-            lds_barrier();
-            i32 off = 0, total = 0;
-#pragma unroll 4
-            for (int j = 0; j < EX_T_WIN / HHX_WAVE; ++j) { if (j < wave) off += red_s[j]; total += red_s[j]; }
-            off += incl - cnt;
-            if (tid == 0) {
-                i64 base = 0;
-                if (total) {
-                    base = (i64)atomicAdd(&mo[k].cursors[0], (unsigned long long)total);
-                    if (base + total > mo[k].cand_cap) { atomicExch(&mo[k].cursors[2], 1ull); base = -1; }
-                }
-                mo[k].g_win_off[(size_t)row * P.n_win + wv] = base;
-                mo[k].g_win_cnt[(size_t)row * P.n_win + wv] = base < 0 ? 0 : total;
-                *bcast = base;
-                s_run_sh[k] = s_run;                            // read again at the next window (every lane read s_prev before the first barrier above)
-                if (wv == P.n_win - 1) mo[k].s_run[row] = s_run;
-            }
-            lds_barrier();
-            const i64 base = *bcast;
-            if (base >= 0 && total) {
-                i32 *cc = mo[k].cand_col;
-                float *cv = mo[k].cand_val;
-                i64 o = base + off;
-                while (keep) {
-                    const int j = __ffs(keep) - 1;
-                    keep &= keep - 1;
-                    cc[o] = c0 + s0 + j;
-                    cv[o] = slot[de_swz(s0 + j, gm)];
-                    ++o;
-                }
-            }
+            // (the descriptor stays in memory: each field is fetched where the tail needs it)
+            de_step_tail(l, tid, lane, wave, s, bq, bs, maybe, s0, s1, c0, gm, s_prev, P.thr, mo[k].to, (size_t)row * P.n_win + wv, &s_run_sh[k], wv == P.n_win - 1 ? &mo[k].s_run[row] : nullptr);
             lds_barrier();                                      // the slots, the reduction rows and the broadcast word are rewritten by the next inflation / step
         }
         if (!more) break;
@@ -2330,13 +2313,7 @@ static void window_plan(i32 n_cols, i64 nnz_b, i32 *cap_win_out, i32 *n_win_out)
 
 template <int PROBE, int UX, int RX, int RW, bool FX, int T = EX_T_WIN, bool BLK = false>
 static int launch_window_fx(const ExParams &P, const i32 *rows, i32 n_list, i32 cap, size_t lds, unsigned grid) {
-    static int attr_dev = -1;           // the attribute is per device: keyed on the current ordinal
-    int dev = 0;
-    HHX_HIP(hipGetDevice(&dev));
-    if (attr_dev != dev) {
-        HHX_HIP(hipFuncSetAttribute((const void *)k_expand_window<PROBE, UX, RX, RW, FX, T, BLK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_dev = dev;
-    }
+    HHX_TRY((raise_dynamic_lds<k_expand_window<PROBE, UX, RX, RW, FX, T, BLK>>()));
     for (i32 wv = 0; wv < P.n_win; ++wv) {
         // symmetric mode: the rows are in identity order and launch wv takes the row blocks I <= wv (blocks J >= I of S)
         const i32 n_w = P.sym ? (i32)std::max<i64>(0, std::min<i64>(n_list, (i64)(wv + 1) * cap - P.sym_row0)) : n_list;
@@ -2353,13 +2330,7 @@ static int launch_window(const ExParams &P, const i32 *rows, i32 n_list, i32 cap
 
 template <int R, int UX, int G>
 static int launch_group(const ExParams &P, const GroupOp &op, i32 cap, size_t lds, unsigned grid) {
-    static int attr_dev = -1;
-    int dev = 0;
-    HHX_HIP(hipGetDevice(&dev));
-    if (attr_dev != dev) {
-        HHX_HIP(hipFuncSetAttribute((const void *)k_expand_group<R, UX, G>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_dev = dev;
-    }
+    HHX_TRY((raise_dynamic_lds<k_expand_group<R, UX, G>>()));
     static const int probe = getenv("HHX_GROUP_PROBE") ? (atoi(getenv("HHX_GROUP_PROBE")) & 1) : 0;     // 1, measurement only: the LDS atomics off, garbage results
     for (i32 wv = 0; wv < P.n_win; ++wv) k_expand_group<R, UX, G><<<grid, EX_T_WIN, lds, g_stream>>>(P, op, cap, wv, probe);
     return 0;
@@ -2417,13 +2388,7 @@ int hhx_expand_impl(const hhx_csr *a, const hhx_csr *b, const CodedOperand &code
     const i32 cap_cmp = (i32)((budget_cmp - fixed_cmp) / 8) & ~63;
     if (n_cols / 2 / cap_cmp + 2 > MAX_WIN - 1) return fail("expand: %d columns need too many LDS rank windows", n_cols);
     const size_t lds_win = (size_t)cap_win * 8 + fixed_win, lds_cmp = (size_t)cap_cmp * 8 + fixed_cmp;
-    static int attr_set = -1;           // the attribute is per device: keyed on the current ordinal
-    int attr_dev = 0;
-    HHX_HIP(hipGetDevice(&attr_dev));
-    if (attr_set != attr_dev) {
-        HHX_HIP(hipFuncSetAttribute((const void *)k_expand_compact, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = attr_dev;
-    }
+    HHX_TRY((raise_dynamic_lds<k_expand_compact>()));
     static const bool debug = getenv("HHX_DEBUG") != nullptr;
     const int probe = (int)tune_get("probe", 0);
     (void)probe;
@@ -2568,13 +2533,7 @@ int hhx_expand_impl(const hhx_csr *a, const hhx_csr *b, const CodedOperand &code
                 HHX_LAUNCH_CHECK();
             }
             P.Bjx = bjx.p;
-            static int hash_attr = -1;
-            int hash_dev = 0;
-            HHX_HIP(hipGetDevice(&hash_dev));
-            if (hash_attr != hash_dev) {
-                HHX_HIP(hipFuncSetAttribute((const void *)k_expand_hash, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                hash_attr = hash_dev;
-            }
+            HHX_TRY((raise_dynamic_lds<k_expand_hash>()));
             {
                 KTimer kt("expand_hash");
                 const unsigned per_cu = lds_hash > 80 * 1024 ? 1 : 2;
@@ -2647,14 +2606,7 @@ int hhx_expand_impl(const hhx_csr *a, const hhx_csr *b, const CodedOperand &code
                     DevBuf<i32> gcnt;
                     if (grp_rows.alloc(h_grp.size()) || gcnt.alloc((size_t)n_groups + 1) || Gp.alloc((size_t)n_groups + 2)) return 1;
                     HHX_HIP(hipMemcpyAsync(grp_rows.p, h_grp.data(), sizeof(i32) * h_grp.size(), hipMemcpyHostToDevice, g_stream));
-                    static int gu_attr = -1;
-                    int gu_dev = 0;
-                    HHX_HIP(hipGetDevice(&gu_dev));
-                    if (gu_attr != gu_dev) {
-                        HHX_HIP(hipFuncSetAttribute((const void *)k_group_union<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                        HHX_HIP(hipFuncSetAttribute((const void *)k_group_union<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                        gu_attr = gu_dev;
-                    }
+                    HHX_TRY((raise_dynamic_lds<k_group_union<false>, k_group_union<true>>()));
                     if (lds_u <= 160 * 1024) {
                         const unsigned ggrid = (unsigned)std::min<i32>(n_groups, 256 * 8);
                         k_group_union<false><<<ggrid, 256, lds_u, g_stream>>>(n_groups, reuse_R, grp_rows.p, a->indptr.p, a->indices.p, a->data.p, Wb, gcnt.p, nullptr, nullptr, nullptr);
@@ -2925,96 +2877,146 @@ int hhx_expand_dense_impl(const hhx_csr *a, const hhx_csr *b, const hhx_links_op
     return 0;
 }
 
-extern "C" int hhx_dense_inflate_prune(const hhx_dense *d, double inflation, double pruning, hhx_csr **out) {
-    if (!d || !out) return fail("null pointer");
-    if (!(inflation > 0)) return fail("inflation must be positive");
-    const i32 n_rows = d->n_rows, n_cols = d->n_cols, n_win = d->n_win, cap = d->cap_win;
-    DevBuf<i32> row_cnt, indptr, g_win_cnt;
+// ---- the host side of a dense epilogue pass, shared by the one-inflation and the multi-inflation driver -----------------------------
+namespace {
+// One inflation of a pass: its per-row table, its candidate and survivor pools
+struct DenseInfl {
+    DevBuf<i32> row_cnt, indptr, g_win_cnt, cand_col, out_col;
     DevBuf<i64> row_off, g_win_off;
+    DevBuf<float> cand_val, out_val;
     DevBuf<double> s_run;
     DevBuf<unsigned long long> cursors;
-    if (row_cnt.alloc((size_t)n_rows + 1) || indptr.alloc((size_t)n_rows + 1) || row_off.alloc((size_t)n_rows + 1) || cursors.alloc(12) ||
-        s_run.alloc((size_t)n_rows + 1) || g_win_off.alloc((size_t)n_rows * n_win + 1) || g_win_cnt.alloc((size_t)n_rows * n_win + 1)) return 1;
-    static int attr_dev = -1;
-    int dev = 0;
-    HHX_HIP(hipGetDevice(&dev));
-    if (attr_dev != dev) {
-        HHX_HIP(hipFuncSetAttribute((const void *)k_dense_epilogue<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HHX_HIP(hipFuncSetAttribute((const void *)k_dense_epilogue<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HHX_HIP(hipFuncSetAttribute((const void *)k_dense_epilogue_sw<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HHX_HIP(hipFuncSetAttribute((const void *)k_dense_epilogue_sw<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_dev = dev;
+    i64 pool_cap = 0, cand_cap = 0;
+    bool done = false;                  // packed into its result (pools released)
+    int alloc_table(i32 n_rows, i32 n_win) {
+        return row_cnt.alloc((size_t)n_rows + 1) || indptr.alloc((size_t)n_rows + 1) || row_off.alloc((size_t)n_rows + 1) || cursors.alloc(12) ||
+               s_run.alloc((size_t)n_rows + 1) || g_win_off.alloc((size_t)n_rows * n_win + 1) || g_win_cnt.alloc((size_t)n_rows * n_win + 1);
     }
-    // a pruned row holds at most 1 / pruning entries; an early window tests against a partial row sum and admits more
-    i64 pool_cap = std::max<i64>((i64)n_rows * 512, (i64)1 << 22), cand_cap = 2 * pool_cap;
-    if (d->last_out) {                                 // a sweep: the demand of the previous inflation, with room for a neighbouring one
-        const bool above = inflation >= d->last_inflation;     // (demands shrink as the inflation grows: the same size re-uses the cached block)
-        pool_cap = d->last_out + (above ? 0 : d->last_out / 2) + n_rows;
-        cand_cap = d->last_cand + (above ? 0 : d->last_cand / 2) + n_rows;
+    // Pool sizes.  No hint: a pruned row holds at most 1 / pruning entries; an early window tests against a partial row sum and admits
+    // more.  With one (a sweep): the demand of the call before.  Survivors and candidates shrink as the inflation grows, so an inflation
+    // at or above the one that left the hint gets exactly the hint's size — the block the previous call left in the pool is then re-used
+    // as it is (a larger request would be a fresh device allocation at ~30 ms per GB, and an overflow only costs a retry of the pass);
+    // one below it gets below_factor halves of the demand on top (1: the one-inflation driver, whose neighbour is close; 2: a group).
+    void size_from_hint(const hhx_dense *d, double inflation, int below_factor) {
+        pool_cap = std::max<i64>((i64)d->n_rows * 512, (i64)1 << 22);
+        cand_cap = 2 * pool_cap;
+        if (!d->last_out) return;
+        const bool above = inflation >= d->last_inflation;
+        pool_cap = d->last_out + (above ? 0 : d->last_out * below_factor / 2) + d->n_rows;
+        cand_cap = d->last_cand + (above ? 0 : d->last_cand * below_factor / 2) + d->n_rows;
     }
-    for (int attempt = 0; attempt < 4; ++attempt) {
-        DevBuf<i32> cand_col, out_col;
-        DevBuf<float> cand_val, out_val;
+    int alloc_pools() {                 // (the pools of an overflowed attempt go back first: the new ones may take their blocks)
+        release_pools();
         if (cand_col.alloc((size_t)cand_cap) || cand_val.alloc((size_t)cand_cap) || out_col.alloc((size_t)pool_cap) || out_val.alloc((size_t)pool_cap)) return 1;
         HHX_HIP(hipMemsetAsync(cursors.p, 0, 12 * sizeof(unsigned long long), g_stream));
-        ExParams P;
-        memset(&P, 0, sizeof P);
-        P.n_rows = n_rows; P.n_cols = n_cols;
-        P.scale = 1.0; P.inv_scale = 1.0;
-        P.r = (double)(float)inflation; P.square = inflation == 2.0; P.thr = (float)pruning;
+        return 0;
+    }
+    void release_pools() { cand_col.release(); cand_val.release(); out_col.release(); out_val.release(); }
+    void grow_after_overflow(const unsigned long long *cur, i32 n_rows) {      // the cursors hold the demand
+        if ((i64)cur[0] > cand_cap) cand_cap = (i64)cur[0] + (i64)n_rows;
+        if ((i64)cur[1] > pool_cap) pool_cap = std::max<i64>(pool_cap * 2, (i64)cur[1] + (i64)n_rows);
+    }
+    void fill(ExParams &P) const {
         P.cand_col = cand_col.p; P.cand_val = cand_val.p; P.cand_cap = cand_cap;
         P.out_col = out_col.p; P.out_val = out_val.p; P.out_cap = pool_cap;
         P.cursors = cursors.p; P.row_off = row_off.p; P.row_cnt = row_cnt.p;
-        P.n_win = n_win; P.s_run = s_run.p; P.g_win_off = g_win_off.p; P.g_win_cnt = g_win_cnt.p;
-        P.row_div = d->integer ? d->row_div.p : nullptr;
-        if (n_rows) {
-            // square block: one launch over all rows.  Upper block triangle: block row by block row — the blocks (J < I, I) are turned
-            // into rows of block row I in a scratch block first (k_transpose_tri), then the rows of block row I are finished
-            DevBuf<float> lower;
-            const i64 lo_ld = (i64)(n_win - 1) * cap;
-            if (d->tri && n_win > 1 && lower.alloc((size_t)cap * (size_t)lo_ld + 1)) return 1;
-            static const int use_sw = getenv("HHX_DENSE_EPI_SW") ? atoi(getenv("HHX_DENSE_EPI_SW")) : 1;
-            for (i32 I = 0; I < (d->tri ? n_win : 1); ++I) {
-                DenseSrc S;
-                if (d->tri) {
-                    S.row0 = I * cap; S.row1 = std::min<i32>(n_rows, (I + 1) * cap);
-                    S.up = d->x.p + tri_row_off(I, cap, d->ldn); S.up_ld = d->ldn - (i64)I * cap; S.up_win0 = I;
-                    S.lo = lower.p; S.lo_ld = lo_ld;
-                    if (I > 0) {
-                        KTimer kt("dense_transpose");
-                        const unsigned tiles = (unsigned)(cap / 64);
-                        k_transpose_tri<<<dim3(tiles, (unsigned)((S.row1 - S.row0 + 63) / 64), (unsigned)I), 256, 0, g_stream>>>(d->x.p, lower.p, lo_ld, I, S.row1 - S.row0, cap, d->ldn);
-                    }
-                } else { S.row0 = 0; S.row1 = n_rows; S.up = d->x.p; S.up_ld = d->ld; S.up_win0 = 0; S.lo = nullptr; S.lo_ld = 0; }
-                const i32 rows_here = S.row1 - S.row0;
-                if (rows_here <= 0) continue;
-                KTimer kt("dense_epilogue");
-                const unsigned grid = std::min<unsigned>((unsigned)rows_here, 512);
-                if (use_sw && (cap + EX_T_WIN - 1) / EX_T_WIN <= DE_PER) {
-                    const unsigned grid1 = std::min<unsigned>((unsigned)rows_here, 256);
-                    if (!P.square) k_dense_epilogue_sw<false, true><<<grid1, EX_T_WIN, dense_epi_sw_lds_bytes(cap), g_stream>>>(P, S, cap);
-                    else k_dense_epilogue_sw<true, false><<<grid, EX_T_WIN, dense_epi_sw_lds_bytes(cap), g_stream>>>(P, S, cap);
-                } else if (P.square) k_dense_epilogue<true><<<grid, EX_T_WIN, dense_epi_lds_bytes(cap), g_stream>>>(P, S, cap);
-                else k_dense_epilogue<false><<<grid, EX_T_WIN, dense_epi_lds_bytes(cap), g_stream>>>(P, S, cap);
+        P.s_run = s_run.p; P.g_win_off = g_win_off.p; P.g_win_cnt = g_win_cnt.p;
+    }
+};
+}  // namespace
+
+static ExParams dense_epi_params(const hhx_dense *d, double pruning) {      // what every inflation of a pass shares
+    ExParams P;
+    memset(&P, 0, sizeof P);
+    P.n_rows = d->n_rows; P.n_cols = d->n_cols;
+    P.scale = 1.0; P.inv_scale = 1.0;
+    P.thr = (float)pruning;
+    P.n_win = d->n_win;
+    P.row_div = d->integer ? d->row_div.p : nullptr;
+    return P;
+}
+
+// The block's rows, walked once: launch(S) starts the epilogue kernel over the rows S describes.  Square block: one launch over all
+// rows.  Upper block triangle: block row by block row — the blocks (J < I, I) are turned into rows of block row I in a scratch block
+// first (k_transpose_tri), then the rows of block row I are finished.
+template <class Launch>
+static int dense_walk_rows(const hhx_dense *d, Launch launch) {
+    const i32 n_rows = d->n_rows, n_win = d->n_win, cap = d->cap_win;
+    if (!n_rows) return 0;
+    DevBuf<float> lower;
+    const i64 lo_ld = (i64)(n_win - 1) * cap;
+    if (d->tri && n_win > 1 && lower.alloc((size_t)cap * (size_t)lo_ld + 1)) return 1;
+    for (i32 I = 0; I < (d->tri ? n_win : 1); ++I) {
+        DenseSrc S;
+        if (d->tri) {
+            S.row0 = I * cap; S.row1 = std::min<i32>(n_rows, (I + 1) * cap);
+            S.up = d->x.p + tri_row_off(I, cap, d->ldn); S.up_ld = d->ldn - (i64)I * cap; S.up_win0 = I;
+            S.lo = lower.p; S.lo_ld = lo_ld;
+            if (I > 0) {
+                KTimer kt("dense_transpose");
+                k_transpose_tri<<<dim3((unsigned)(cap / 64), (unsigned)((S.row1 - S.row0 + 63) / 64), (unsigned)I), 256, 0, g_stream>>>(d->x.p, lower.p, lo_ld, I, S.row1 - S.row0, cap, d->ldn);
             }
-            HHX_LAUNCH_CHECK();
-            if (lower.p) HHX_HIP(hipStreamSynchronize(g_stream));          // the scratch block dies with this scope
-            KTimer kt("expand_finalize");
-            k_expand_window_finalize<<<std::min<unsigned>((unsigned)n_rows, 256 * 8), EX_T_CMP, ex_fixed_bytes(0, 0), g_stream>>>(P, nullptr, n_rows);
-        }
-        HHX_LAUNCH_CHECK();
-        unsigned long long cur[8];
-        HHX_HIP(hipMemcpyAsync(cur, cursors.p, sizeof cur, hipMemcpyDeviceToHost, g_stream));
-        HHX_HIP(hipStreamSynchronize(g_stream));
-        if (cur[2]) {                                  // a pool overflowed: the cursors hold the demand
-            if ((i64)cur[0] > cand_cap) cand_cap = (i64)cur[0] + (i64)n_rows;
-            if ((i64)cur[1] > pool_cap) pool_cap = std::max<i64>(pool_cap * 2, (i64)cur[1] + (i64)n_rows);
-            continue;
-        }
-        d->last_cand = (i64)cur[0];
-        d->last_out = (i64)cur[1];
-        d->last_inflation = inflation;
-        return pack_rows_to_csr(n_rows, n_cols, row_cnt.p, indptr.p, row_off.p, out_col.p, out_val.p, out);
+        } else { S.row0 = 0; S.row1 = n_rows; S.up = d->x.p; S.up_ld = d->ld; S.up_win0 = 0; S.lo = nullptr; S.lo_ld = 0; }
+        if (S.row1 <= S.row0) continue;
+        KTimer kt("dense_epilogue");
+        launch(S);
+    }
+    HHX_LAUNCH_CHECK();
+    if (lower.p) HHX_HIP(hipStreamSynchronize(g_stream));          // the scratch block dies with this scope
+    return 0;
+}
+
+// The end of one inflation's pass: its rows are finished from their candidate segments; then either a pool overflowed — q's pools
+// grow to the demand and q.done stays false — or the rows are packed into *out.  leave_hint: the demand becomes the hint of the
+// next call on this block (at least hint_floor: a hint of 0 reads as "no hint").
+static int dense_finish(const hhx_dense *d, ExParams P, DenseInfl &q, double inflation, bool leave_hint, i64 hint_floor, hhx_csr **out) {
+    const i32 n_rows = d->n_rows;
+    P.r = (double)(float)inflation; P.square = inflation == 2.0;
+    q.fill(P);
+    if (n_rows) {
+        KTimer kt("expand_finalize");
+        k_expand_window_finalize<<<std::min<unsigned>((unsigned)n_rows, 256 * 8), EX_T_CMP, ex_fixed_bytes(0, 0), g_stream>>>(P, nullptr, n_rows);
+    }
+    HHX_LAUNCH_CHECK();
+    unsigned long long cur[4];
+    HHX_HIP(hipMemcpyAsync(cur, q.cursors.p, sizeof cur, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    if (cur[2]) { q.grow_after_overflow(cur, n_rows); return 0; }
+    if (leave_hint) {
+        d->last_cand = std::max<i64>((i64)cur[0], hint_floor); d->last_out = std::max<i64>((i64)cur[1], hint_floor); d->last_inflation = inflation;
+    }
+    HHX_TRY(pack_rows_to_csr(n_rows, d->n_cols, q.row_cnt.p, q.indptr.p, q.row_off.p, q.out_col.p, q.out_val.p, out));
+    q.done = true;
+    q.release_pools();
+    return 0;
+}
+
+extern "C" int hhx_dense_inflate_prune(const hhx_dense *d, double inflation, double pruning, hhx_csr **out) {
+    if (!d || !out) return fail("null pointer");
+    if (!(inflation > 0)) return fail("inflation must be positive");
+    const i32 cap = d->cap_win;
+    DenseInfl q;
+    if (q.alloc_table(d->n_rows, d->n_win)) return 1;
+    HHX_TRY((raise_dynamic_lds<k_dense_epilogue<true>, k_dense_epilogue<false>, k_dense_epilogue_sw<true, false>, k_dense_epilogue_sw<false, true>>()));
+    q.size_from_hint(d, inflation, 1);                 // a sweep: room for a neighbouring inflation
+    static const int use_sw = getenv("HHX_DENSE_EPI_SW") ? atoi(getenv("HHX_DENSE_EPI_SW")) : 1;
+    for (int attempt = 0; attempt < 4; ++attempt) {
+        HHX_TRY(q.alloc_pools());
+        ExParams P = dense_epi_params(d, pruning);
+        P.r = (double)(float)inflation; P.square = inflation == 2.0;
+        q.fill(P);
+        HHX_TRY(dense_walk_rows(d, [&](const DenseSrc &S) {
+            const i32 rows_here = S.row1 - S.row0;
+            const unsigned grid = std::min<unsigned>((unsigned)rows_here, 512);
+            if (use_sw && (cap + EX_T_WIN - 1) / EX_T_WIN <= DE_PER) {
+                const unsigned grid1 = std::min<unsigned>((unsigned)rows_here, 256);
+                if (!P.square) k_dense_epilogue_sw<false, true><<<grid1, EX_T_WIN, dense_epi_sw_lds_bytes(cap), g_stream>>>(P, S, cap);
+                else k_dense_epilogue_sw<true, false><<<grid, EX_T_WIN, dense_epi_sw_lds_bytes(cap), g_stream>>>(P, S, cap);
+            } else if (P.square) k_dense_epilogue<true><<<grid, EX_T_WIN, dense_epi_lds_bytes(cap), g_stream>>>(P, S, cap);
+            else k_dense_epilogue<false><<<grid, EX_T_WIN, dense_epi_lds_bytes(cap), g_stream>>>(P, S, cap);
+        }));
+        HHX_TRY(dense_finish(d, P, q, inflation, true, 0, out));
+        if (q.done) return 0;
     }
     return fail("dense inflate / prune: survivor pool kept overflowing");
 }
@@ -3024,7 +3026,7 @@ extern "C" int hhx_dense_inflate_prune(const hhx_dense *d, double inflation, dou
 static int dense_inflate_prune_multi_impl(const hhx_dense *d, int K, const double *inflations, double pruning, hhx_csr **outs);
 
 // all or nothing: whatever path fails (a pool allocation, a HIP call in the middle of a pass, a later part of a split), the matrices
-// already packed are released and every outs[k] is null on a non-zero return
+// already packed are released and every outs[k] is null on a non-zero return — here, for every path below
 extern "C" int hhx_dense_inflate_prune_multi(const hhx_dense *d, int K, const double *inflations, double pruning, hhx_csr **outs) {
     if (!d || !inflations || !outs) return fail("null pointer");
     if (K < 1 || K > MULTI_MAX) return fail("hhx_dense_inflate_prune_multi: 1 to %d inflations per pass", MULTI_MAX);
@@ -3038,183 +3040,92 @@ extern "C" int hhx_dense_inflate_prune_multi(const hhx_dense *d, int K, const do
 }
 
 static int dense_inflate_prune_multi_impl(const hhx_dense *d, int K, const double *inflations, double pruning, hhx_csr **outs) {
-    const i32 n_rows = d->n_rows, n_cols = d->n_cols, n_win = d->n_win, cap = d->cap_win;
-    // inflation 2 is x * x, not exp2(2 log2 x) (numpy's `** 2`, hhx_powr's callers): it goes through the one-inflation kernel;
-    // so does everything when the window is wider than the owned-slot registers of the fused kernel
-    bool single = (cap + EX_T_WIN - 1) / EX_T_WIN > DE_PER || K == 1;
-    for (int k = 0; k < K; ++k) single = single || inflations[k] == 2.0;
-    if (single) {
-        // the group pass FIRST: its hint (the demand of its lowest inflation) then covers the inflations that go alone — the other way round the lone
+    const i32 cap = d->cap_win;
+    if (K == 1) return hhx_dense_inflate_prune(d, inflations[0], pruning, &outs[0]);
+    int lowest = 0;
+    for (int k = 1; k < K; ++k) if (inflations[k] < inflations[lowest]) lowest = k;
+    // The parts this group is taken in, one after the other (each leaves the hint for the next, so a part is split further only when
+    // its turn comes); none: the whole group in the pass below.
+    std::vector<std::vector<int>> parts;
+    bool has2 = false;
+    for (int k = 0; k < K; ++k) has2 = has2 || inflations[k] == 2.0;
+    if ((cap + EX_T_WIN - 1) / EX_T_WIN > DE_PER) {
+        // the window is wider than the owned-slot registers of the fused kernel: everything through the one-inflation kernel
+        for (int k = 0; k < K; ++k) parts.push_back({k});
+    } else if (has2) {
+        // inflation 2 is x * x, not exp2(2 log2 x) (numpy's `** 2`, hhx_powr's callers): it goes through the one-inflation kernel.
+        // The group pass FIRST: its hint (the demand of its lowest inflation) then covers the inflations that go alone — the other way round the lone
         // 2.0 left a hint that every lower inflation of the group overflowed (a retry of the pass: 70 ms of the 259 ms of the 1.6-2.0 group until round 6)
-        int rc1 = 0;
-        std::vector<double> rest;
-        std::vector<int> at, alone;
-        for (int k = 0; k < K; ++k) {
-            if (inflations[k] == 2.0 || K == 1 || (cap + EX_T_WIN - 1) / EX_T_WIN > DE_PER) alone.push_back(k);
-            else { rest.push_back(inflations[k]); at.push_back(k); }
-        }
-        if (!rest.empty()) {
-            std::vector<hhx_csr *> o2(rest.size(), nullptr);
-            rc1 = hhx_dense_inflate_prune_multi(d, (int)rest.size(), rest.data(), pruning, o2.data());
-            for (size_t t = 0; t < at.size(); ++t) outs[at[t]] = o2[t];
-        }
-        for (size_t t = 0; t < alone.size() && !rc1; ++t) rc1 = hhx_dense_inflate_prune(d, inflations[alone[t]], pruning, &outs[alone[t]]);
-        if (rc1) for (int k = 0; k < K; ++k) if (outs[k]) { hhx_csr_free(outs[k]); outs[k] = nullptr; }
-        return rc1;
-    }
-    // No hint yet (first call on this block): the lowest inflation goes alone through the one-inflation kernel — its demand bounds
-    // everybody else's, so the pools of the pass over the others are sized right at once (a retry of a K-inflation pass, or K pools
-    // at a guess, cost more: device allocations run at ~30 ms per GB).  With a hint: as many inflations per pass as fit ~6 GB of pools.
-    {
-        int lowest = 0;
-        for (int k = 1; k < K; ++k) if (inflations[k] < inflations[lowest]) lowest = k;
-        i64 per_infl = d->last_out ? 8 * (d->last_out + d->last_cand) : 0;
-        if (d->last_out && inflations[lowest] < d->last_inflation) per_infl *= 2;
-        // pools of a pass: 6 GB when the device is tight, up to 32 GB when a quarter of what is free (driver + the pool's cache) allows it
+        std::vector<int> rest;
+        for (int k = 0; k < K; ++k) if (inflations[k] != 2.0) rest.push_back(k);
+        if (!rest.empty()) parts.push_back(rest);
+        for (int k = 0; k < K; ++k) if (inflations[k] == 2.0) parts.push_back({k});
+    } else if (!d->last_out) {
+        // No hint yet (first call on this block): the lowest inflation goes alone through the one-inflation kernel — its demand bounds
+        // everybody else's, so the pools of the pass over the others are sized right at once (a retry of a K-inflation pass, or K pools
+        // at a guess, cost more: device allocations run at ~30 ms per GB).
+        parts.resize(2);
+        for (int k = 0; k < K; ++k) parts[k == lowest ? 0 : 1].push_back(k);
+    } else {
+        // With a hint: as many inflations per pass as fit the pools of a pass — 6 GB when the device is tight, up to 32 GB when a quarter
+        // of what is free (driver + the pool's cache) allows it
+        i64 per_infl = 8 * (d->last_out + d->last_cand);
+        if (inflations[lowest] < d->last_inflation) per_infl *= 2;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
         const i64 pass_bytes = std::min<i64>((i64)32 << 30, std::max<i64>((i64)6 << 30, ((i64)free_b + pool_cached_bytes()) / 4));
-        const int fit = !d->last_out ? 0 : (int)std::max<i64>(1, std::min<i64>(MULTI_MAX, pass_bytes / std::max<i64>(per_infl, 1)));
-        if (!d->last_out || fit < K) {
-            // split: [lowest alone | the rest] without a hint; [the first `fit` | the rest] with one — recursion ends at K == 1 or fit >= K
-            std::vector<int> first, rest;
-            if (!d->last_out) { for (int k = 0; k < K; ++k) (k == lowest ? first : rest).push_back(k); }
-            else { for (int k = 0; k < K; ++k) (k < fit ? first : rest).push_back(k); }
-            int rc2 = 0;
-            for (const std::vector<int> *part : {&first, &rest}) {
-                if (rc2 || part->empty()) continue;
-                std::vector<double> r2;
-                for (int k : *part) r2.push_back(inflations[k]);
-                std::vector<hhx_csr *> o2(part->size(), nullptr);
-                rc2 = hhx_dense_inflate_prune_multi(d, (int)r2.size(), r2.data(), pruning, o2.data());
-                for (size_t t = 0; t < part->size(); ++t) outs[(*part)[t]] = o2[t];
-            }
-            if (rc2) for (int k = 0; k < K; ++k) if (outs[k]) { hhx_csr_free(outs[k]); outs[k] = nullptr; }
-            return rc2;
+        const int fit = (int)std::max<i64>(1, std::min<i64>(MULTI_MAX, pass_bytes / std::max<i64>(per_infl, 1)));
+        if (fit < K) {                                  // [the first `fit` | the rest]
+            parts.resize(2);
+            for (int k = 0; k < K; ++k) parts[k < fit ? 0 : 1].push_back(k);
         }
     }
-    static int attr_dev = -1;
-    int dev = 0;
-    HHX_HIP(hipGetDevice(&dev));
-    if (attr_dev != dev) {
-        HHX_HIP(hipFuncSetAttribute((const void *)k_dense_epilogue_multi, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_dev = dev;
+    if (!parts.empty()) {                               // (the recursion ends at K == 1 or fit >= K)
+        for (const std::vector<int> &part : parts) {
+            std::vector<double> r2;
+            for (int k : part) r2.push_back(inflations[k]);
+            std::vector<hhx_csr *> o2(part.size(), nullptr);
+            const int rc = hhx_dense_inflate_prune_multi(d, (int)r2.size(), r2.data(), pruning, o2.data());
+            for (size_t t = 0; t < part.size(); ++t) outs[part[t]] = o2[t];
+            if (rc) return rc;
+        }
+        return 0;
     }
-    int hint_k = 0;
-    for (int k = 1; k < K; ++k) if (inflations[k] < inflations[hint_k]) hint_k = k;
-    struct PerK {
-        DevBuf<i32> row_cnt, indptr, g_win_cnt, cand_col, out_col;
-        DevBuf<i64> row_off, g_win_off;
-        DevBuf<float> cand_val, out_val;
-        DevBuf<double> s_run;
-        DevBuf<unsigned long long> cursors;
-        i64 pool_cap = 0, cand_cap = 0;
-        bool done = false;
-    };
-    std::vector<PerK> pk((size_t)K);
+    HHX_TRY((raise_dynamic_lds<k_dense_epilogue_multi>()));
+    std::vector<DenseInfl> pk((size_t)K);
     for (int k = 0; k < K; ++k) {
-        PerK &q = pk[(size_t)k];
-        if (q.row_cnt.alloc((size_t)n_rows + 1) || q.indptr.alloc((size_t)n_rows + 1) || q.row_off.alloc((size_t)n_rows + 1) || q.cursors.alloc(12) ||
-            q.s_run.alloc((size_t)n_rows + 1) || q.g_win_off.alloc((size_t)n_rows * n_win + 1) || q.g_win_cnt.alloc((size_t)n_rows * n_win + 1)) return 1;
-        q.pool_cap = std::max<i64>((i64)n_rows * 512, (i64)1 << 22);
-        q.cand_cap = 2 * q.pool_cap;
-        if (d->last_out) {
-            // the demand of the call before.  Survivors and candidates shrink as the inflation grows: an inflation at or above the
-            // one that left the hint needs no more than it did (+ 10 %: the candidate test runs against partial row sums)
-            // (exactly the hint's size when above it — the block the previous call left in the pool is then re-used as it is; a
-            // larger request would be a fresh device allocation at ~30 ms per GB, and an overflow only costs a retry of this pass)
-            const bool above = inflations[k] >= d->last_inflation;
-            q.pool_cap = d->last_out + (above ? 0 : d->last_out) + n_rows;
-            q.cand_cap = d->last_cand + (above ? 0 : d->last_cand) + n_rows;
-        }
+        if (pk[(size_t)k].alloc_table(d->n_rows, d->n_win)) return 1;
+        pk[(size_t)k].size_from_hint(d, inflations[k], 2);
     }
     DevBuf<MultiOut> mo_dev;
     DevBuf<unsigned long long> cursors0;                    // P.cursors of the kernel: only [3] (entries of the block) is written
     if (mo_dev.alloc((size_t)MULTI_MAX) || cursors0.alloc(12)) return 1;
-    int rc = 0;
-    for (int attempt = 0; attempt < 4 && !rc; ++attempt) {
+    for (int attempt = 0; attempt < 4; ++attempt) {
         // the inflations still to do (first attempt: all; then those whose pools overflowed, with the pools at their demand)
         std::vector<int> todo;
         for (int k = 0; k < K; ++k) if (!pk[(size_t)k].done) todo.push_back(k);
-        if (todo.empty()) break;
+        if (todo.empty()) return 0;
         MultiOut mo[MULTI_MAX];
         memset(mo, 0, sizeof mo);
         for (size_t t = 0; t < todo.size(); ++t) {
-            PerK &q = pk[(size_t)todo[t]];
-            if (q.cand_col.alloc((size_t)q.cand_cap) || q.cand_val.alloc((size_t)q.cand_cap) || q.out_col.alloc((size_t)q.pool_cap) || q.out_val.alloc((size_t)q.pool_cap)) return 1;
-            HHX_HIP(hipMemsetAsync(q.cursors.p, 0, 12 * sizeof(unsigned long long), g_stream));
+            DenseInfl &q = pk[(size_t)todo[t]];
+            HHX_TRY(q.alloc_pools());
             mo[t].r = (double)(float)inflations[todo[t]]; mo[t].square = inflations[todo[t]] == 2.0;
-            mo[t].cand_col = q.cand_col.p; mo[t].cand_val = q.cand_val.p; mo[t].cand_cap = q.cand_cap;
-            mo[t].cursors = q.cursors.p; mo[t].g_win_off = q.g_win_off.p; mo[t].g_win_cnt = q.g_win_cnt.p; mo[t].s_run = q.s_run.p;
+            mo[t].to = {q.cand_col.p, q.cand_val.p, q.cand_cap, q.cursors.p, q.g_win_off.p, q.g_win_cnt.p};
+            mo[t].s_run = q.s_run.p;
         }
         HHX_HIP(hipMemcpyAsync(mo_dev.p, mo, sizeof mo, hipMemcpyHostToDevice, g_stream));
         HHX_HIP(hipMemsetAsync(cursors0.p, 0, 12 * sizeof(unsigned long long), g_stream));
-        ExParams P;
-        memset(&P, 0, sizeof P);
-        P.n_rows = n_rows; P.n_cols = n_cols;
-        P.scale = 1.0; P.inv_scale = 1.0;
-        P.thr = (float)pruning;
-        P.n_win = n_win;
+        ExParams P = dense_epi_params(d, pruning);
         P.cursors = cursors0.p;
-        P.row_div = d->integer ? d->row_div.p : nullptr;
-        if (n_rows) {
-            DevBuf<float> lower;
-            const i64 lo_ld = (i64)(n_win - 1) * cap;
-            if (d->tri && n_win > 1 && lower.alloc((size_t)cap * (size_t)lo_ld + 1)) return 1;
-            for (i32 I = 0; I < (d->tri ? n_win : 1); ++I) {
-                DenseSrc S;
-                if (d->tri) {
-                    S.row0 = I * cap; S.row1 = std::min<i32>(n_rows, (I + 1) * cap);
-                    S.up = d->x.p + tri_row_off(I, cap, d->ldn); S.up_ld = d->ldn - (i64)I * cap; S.up_win0 = I;
-                    S.lo = lower.p; S.lo_ld = lo_ld;
-                    if (I > 0) {
-                        KTimer kt("dense_transpose");
-                        k_transpose_tri<<<dim3((unsigned)(cap / 64), (unsigned)((S.row1 - S.row0 + 63) / 64), (unsigned)I), 256, 0, g_stream>>>(d->x.p, lower.p, lo_ld, I, S.row1 - S.row0, cap, d->ldn);
-                    }
-                } else { S.row0 = 0; S.row1 = n_rows; S.up = d->x.p; S.up_ld = d->ld; S.up_win0 = 0; S.lo = nullptr; S.lo_ld = 0; }
-                if (S.row1 <= S.row0) continue;
-                KTimer kt("dense_epilogue");
-                k_dense_epilogue_multi<<<std::min<unsigned>((unsigned)(S.row1 - S.row0), 256), EX_T_WIN, dense_epi_multi_lds_bytes(cap), g_stream>>>(P, S, cap, (i32)todo.size(), mo_dev.p);
-            }
-            HHX_LAUNCH_CHECK();
-            for (size_t t = 0; t < todo.size(); ++t) {         // the rows of every inflation finished from its own candidate segments
-                PerK &q = pk[(size_t)todo[t]];
-                ExParams Q = P;
-                Q.r = mo[t].r; Q.square = mo[t].square;
-                Q.cand_col = q.cand_col.p; Q.cand_val = q.cand_val.p; Q.cand_cap = q.cand_cap;
-                Q.out_col = q.out_col.p; Q.out_val = q.out_val.p; Q.out_cap = q.pool_cap;
-                Q.cursors = q.cursors.p; Q.row_off = q.row_off.p; Q.row_cnt = q.row_cnt.p;
-                Q.s_run = q.s_run.p; Q.g_win_off = q.g_win_off.p; Q.g_win_cnt = q.g_win_cnt.p;
-                KTimer kt("expand_finalize");
-                k_expand_window_finalize<<<std::min<unsigned>((unsigned)n_rows, 256 * 8), EX_T_CMP, ex_fixed_bytes(0, 0), g_stream>>>(Q, nullptr, n_rows);
-            }
-            HHX_LAUNCH_CHECK();
-            HHX_HIP(hipStreamSynchronize(g_stream));             // (the scratch block row of the triangle dies with this scope)
-        }
-        for (size_t t = 0; t < todo.size() && !rc; ++t) {
-            PerK &q = pk[(size_t)todo[t]];
-            unsigned long long cur[4];
-            HHX_HIP(hipMemcpyAsync(cur, q.cursors.p, sizeof cur, hipMemcpyDeviceToHost, g_stream));
-            HHX_HIP(hipStreamSynchronize(g_stream));
-            if (cur[2]) {                                      // a pool overflowed: the cursors hold the demand
-                if ((i64)cur[0] > q.cand_cap) q.cand_cap = (i64)cur[0] + (i64)n_rows;
-                if ((i64)cur[1] > q.pool_cap) q.pool_cap = std::max<i64>(q.pool_cap * 2, (i64)cur[1] + (i64)n_rows);
-                continue;
-            }
-            if (todo[t] == hint_k) {                           // the hint for the next call: the demand of THIS call's lowest inflation (its largest)
-                d->last_cand = std::max<i64>((i64)cur[0], 1); d->last_out = std::max<i64>((i64)cur[1], 1); d->last_inflation = inflations[todo[t]];
-            }
-            rc = pack_rows_to_csr(n_rows, n_cols, q.row_cnt.p, q.indptr.p, q.row_off.p, q.out_col.p, q.out_val.p, &outs[todo[t]]);
-            q.done = true;
-            q.cand_col.release(); q.cand_val.release(); q.out_col.release(); q.out_val.release();
-        }
+        HHX_TRY(dense_walk_rows(d, [&](const DenseSrc &S) {
+            k_dense_epilogue_multi<<<std::min<unsigned>((unsigned)(S.row1 - S.row0), 256), EX_T_WIN, dense_epi_multi_lds_bytes(cap), g_stream>>>(P, S, cap, (i32)todo.size(), mo_dev.p);
+        }));
+        // the rows of every inflation finished from its own candidate segments; the hint for the next call: the demand of THIS call's
+        // lowest inflation (its largest)
+        for (int k : todo) HHX_TRY(dense_finish(d, P, pk[(size_t)k], inflations[k], k == lowest, 1, &outs[k]));
     }
-    bool all = true;
-    for (int k = 0; k < K; ++k) all = all && pk[(size_t)k].done;
-    if (rc || !all) {
-        for (int k = 0; k < K; ++k) if (outs[k]) { hhx_csr_free(outs[k]); outs[k] = nullptr; }
-        return rc ? rc : fail("dense inflate / prune (multi): survivor pool kept overflowing");
-    }
+    for (int k = 0; k < K; ++k) if (!pk[(size_t)k].done) return fail("dense inflate / prune (multi): survivor pool kept overflowing");
     return 0;
 }
 
