@@ -7,6 +7,9 @@ Argument parsing, logging, file formats and every stage outside the hot path are
 `python -m haphic_amd plot <arguments of "haphic plot">` does the same for HapHiC_plot.py: parse_pairs / parse_bam (the read-pair
 binning into the scaffold-bin contact matrix) and normalize_matrix (the Knight-Ruiz balancing of `--normalization KR`, the scaled
 matrix and the median behind vmax; `log10` / `none`: the median alone) run on the device (haphic_amd.plot.patch_plot), main() is the reference's.
+`python -m haphic_amd reassign <arguments of "haphic reassign">` wraps HapHiC_reassign.py: parse_link_dict (the per-group link sums) and
+split_clm_file (paired_links.clm split into split_clms/<group>.clm, haphic_amd/reassign.py) run on the device (haphic_amd.patch.patch_reassign);
+the rescue rounds and run() :752-916 are the reference's, called as its main() :919-924 calls them.
 
 The reference checkout is found through --reference DIR or $HAPHIC_REFERENCE (the repository root or its scripts/
 directory).  Extra flags of the wrapper (removed before the reference parses the command line):
@@ -52,11 +55,11 @@ def main(argv=None):
         print(__doc__)
         return 0
     command = argv.pop(0)
-    if command not in ('cluster', 'plot'):
-        raise SystemExit('haphic_amd wraps the "cluster" and "plot" steps only (got {!r}); run the other steps with the reference'.format(command))
+    if command not in ('cluster', 'plot', 'reassign'):
+        raise SystemExit('haphic_amd wraps the "cluster", "plot" and "reassign" steps only (got {!r}); run the other steps with the reference'.format(command))
     from . import ranks
     gpus, host_transport = ranks.take_args(argv)
-    if command == 'plot' and (gpus or 1) > 1:
+    if command in ('plot', 'reassign') and (gpus or 1) > 1:
         raise SystemExit('--gpus is a flag of the "cluster" step only')
     if (gpus or 1) > 1 and not ranks.in_torchrun():
         # one fresh child process per rank (never exec: this process may not replace itself), each with RANK / WORLD_SIZE / LOCAL_RANK
@@ -86,6 +89,12 @@ def main(argv=None):
         plot.patch_plot(P)
         sys.argv = ['haphic plot'] + argv
         P.main()
+        return 0
+    if command == 'reassign':
+        import HapHiC_reassign as R                                 # needs pysam / sklearn, as the reference does
+        patch.patch_reassign(R)
+        sys.argv = ['haphic reassign'] + argv
+        R.run(R.parse_arguments(), 'HapHiC_reassign.log')           # == HapHiC_reassign.main() :919-924
         return 0
     import HapHiC_cluster as H                                      # the unmodified reference module
     patch.patch_reference(H, ingest=not keep_ingest)

@@ -163,8 +163,15 @@ SIGNATURES = {
     'hhx_text_reader_open': (C.c_int, [C.c_char_p, C.c_int64, C.c_int, c_vpp]),
     'hhx_text_reader_open_bgzf': (C.c_int, [C.c_char_p, C.c_int64, C.c_int, c_vpp]),
     'hhx_text_reader_open_range': (C.c_int, [C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, c_vpp]),
+    'hhx_text_reader_open_raw': (C.c_int, [C.c_char_p, C.c_int64, C.c_int, c_vpp]),
     'hhx_text_reader_next': (C.c_int, [C.c_void_p, c_vpp, c_i64p]),
     'hhx_text_reader_close': (C.c_int, [C.c_void_p]),
+    'hhx_clm_split_create': (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, c_vpp]),
+    'hhx_clm_split_push': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    'hhx_clm_split_file': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int]),
+    'hhx_clm_split_finish': (C.c_int, [C.c_void_p, c_i64p, c_i64p, C.c_void_p]),
+    'hhx_clm_split_stats': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_clm_split_destroy': (C.c_int, [C.c_void_p]),
     'hhx_files_pending': (C.c_int, [c_i64p, c_i64p]),
     'hhx_files_join': (C.c_int, [c_i64p]),
     'hhx_correct_create': (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, c_vpp]),
@@ -625,6 +632,70 @@ class TextReader:
     def close(self):
         if self.h is not None and self.h.value:
             load().hhx_text_reader_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ClmSplit:
+    """hhx_clm_split: CLM text, pushed in pieces cut anywhere, routed line by line to one file per group (split_clm_file,
+    HapHiC_reassign.py:581-622).  names[k] belongs to group group_of_name[k] (-1: to none); paths[g] is the file of group g."""
+    STATS = ('lines', 'kept', 'heads', 'seams', 'continuations', 'multi_line_tiles', 'multi_tile_lines')
+
+    def __init__(self, names, group_of_name, paths):
+        blob, off = names_blob(names)
+        grp = np.ascontiguousarray(group_of_name, np.int32)
+        if grp.size != len(names):
+            raise ValueError('ClmSplit: {} names, {} groups of names'.format(len(names), grp.size))
+        enc = [os.fsencode(p) for p in paths]
+        poff = np.zeros(len(enc) + 1, np.int64)
+        if enc:
+            poff[1:] = np.cumsum([len(b) for b in enc])
+        pblob = np.frombuffer(b''.join(enc) or b'\0', np.uint8)
+        self.n_groups = len(enc)
+        self.h = C.c_void_p()
+        check(load().hhx_clm_split_create(len(names), ptr(blob), ptr(off), ptr(grp) if grp.size else None, self.n_groups, ptr(pblob), ptr(poff),
+                                          C.byref(self.h)))
+
+    @staticmethod
+    def _raise(rc):
+        """IndexError as the reference's cols[1] raises it; everything else is the library's RuntimeError"""
+        if rc:
+            msg = load().hhx_last_error().decode('utf-8', 'replace')
+            if msg.startswith('IndexError: '):
+                raise IndexError(msg.split(': ', 1)[1])
+            raise RuntimeError('libhaphic_hip: ' + msg)
+
+    def push(self, text=None, device_ptr=None, n_bytes=None):
+        """the next bytes of the file: bytes-like, or a device pointer + n_bytes"""
+        if device_ptr is not None:
+            return self._raise(load().hhx_clm_split_push(self.h, C.c_void_p(device_ptr), int(n_bytes), 1))
+        buf = np.frombuffer(text, np.uint8)
+        self._raise(load().hhx_clm_split_push(self.h, ptr(buf) if buf.size else None, buf.size, 0))
+
+    def push_file(self, path, chunk_bytes=64 << 20, threads=4):
+        """the whole file through the library's pinned read-ahead reader, in raw chunks of chunk_bytes"""
+        self._raise(load().hhx_clm_split_file(self.h, os.fsencode(path), int(chunk_bytes), int(threads)))
+
+    def finish(self):
+        """flushes the open line; the files are complete on return.  -> (lines, lines kept, bytes per group)"""
+        nl, nk = C.c_int64(0), C.c_int64(0)
+        per = np.zeros(max(self.n_groups, 1), np.int64)
+        self._raise(load().hhx_clm_split_finish(self.h, C.byref(nl), C.byref(nk), ptr(per)))
+        return nl.value, nk.value, per[:self.n_groups]
+
+    def stats(self):
+        v = np.zeros(len(self.STATS), np.int64)
+        check(load().hhx_clm_split_stats(self.h, ptr(v)))
+        return dict(zip(self.STATS, (int(x) for x in v)))
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            load().hhx_clm_split_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -23,6 +23,7 @@ struct hhx_text_reader {
     i64 len[2] = {0, 0};                  // bytes of whole lines ready in buf[k]
     int state[2] = {0, 0};                // 0 free for the reader, 1 filled, 2 held by the caller
     std::vector<unsigned char> tail;      // the bytes after the last line break of the chunk read last: the front of the next chunk
+    bool raw = false;                     // hhx_text_reader_open_raw: fixed-size chunks cut anywhere, nothing carried (a consumer that keeps its own state across cuts)
     bool bgzf = false;                    // the file is BGZF: `at` / `size` count COMPRESSED bytes, the buffers hold inflated text
     i64 skip = 0;                         // BGZF range: inflated bytes to drop in front of the first line (the range starts inside a block)
     i64 limit = -1;                       // BGZF range: inflated bytes to hand out in all (-1: to the end of the file)
@@ -107,7 +108,7 @@ struct hhx_text_reader {
                     have += want;
                     last = at >= size;
                     cut = have;
-                    if (last) break;
+                    if (last || raw) break;
                 }
                 while (cut > 0 && buf[b][cut - 1] != '\n' && buf[b][cut - 1] != '\r') --cut;
                 if (cut > 0) break;                                  // else: no line break in the whole chunk, keep reading into the same buffer
@@ -206,7 +207,7 @@ int plain_line_start(int fd, i64 size, i64 x, i64 &start) {
 
 }  // namespace
 
-static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, bool bgzf, int64_t begin, int64_t end, hhx_text_reader **out);
+static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, bool bgzf, int64_t begin, int64_t end, hhx_text_reader **out, bool raw = false);
 extern "C" int hhx_text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, hhx_text_reader **out) {
     return text_reader_open(path, chunk_bytes, n_threads, false, -1, -1, out);
 }
@@ -220,7 +221,11 @@ extern "C" int hhx_text_reader_open_range(const char *path, int64_t begin, int64
     if (begin < 0 || end < begin) return fail("hhx_text_reader_open_range: bad range [%lld, %lld)", (long long)begin, (long long)end);
     return text_reader_open(path, chunk_bytes, n_threads, bgzf != 0, begin, end, out);
 }
-static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, bool bgzf, int64_t begin, int64_t end, hhx_text_reader **out) {
+// the bytes of the file as they are, chunk_bytes at a time (the last chunk shorter): a line of any length passes, the consumer joins the pieces
+extern "C" int hhx_text_reader_open_raw(const char *path, int64_t chunk_bytes, int n_threads, hhx_text_reader **out) {
+    return text_reader_open(path, chunk_bytes, n_threads, false, -1, -1, out, true);
+}
+static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads, bool bgzf, int64_t begin, int64_t end, hhx_text_reader **out, bool raw) {
     if (!path || !out || chunk_bytes <= 0) return fail("hhx_text_reader_open: bad argument");
     const int fd = ::open(path, O_RDONLY);
     if (fd < 0) return fail("cannot open %s: %s", path, strerror(errno));
@@ -270,6 +275,7 @@ static int text_reader_open(const char *path, int64_t chunk_bytes, int n_threads
     r->chunk = (size_t)chunk_bytes;
     r->cap = 2 * (size_t)chunk_bytes + 4096;                           // a carried tail is shorter than a chunk (or the file has a line longer than one)
     r->bgzf = bgzf;
+    r->raw = raw;
     if (!bgzf && (size_t)(hi - lo) + 4096 < r->cap) r->cap = (size_t)(hi - lo) + 4096;     // a small file: no more pinned memory than it has bytes (pinning costs ~0.5 ms per MB)
     if (bgzf && text_bound >= 0 && (size_t)text_bound + ((size_t)68 << 10) < r->cap) r->cap = (size_t)text_bound + ((size_t)68 << 10);   // the ISIZE trailers bound the text (+ one block of room)
     r->n_threads = n_threads > 0 ? std::min(n_threads, 16) : 4;

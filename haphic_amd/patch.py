@@ -140,16 +140,24 @@ def patch_reference(H, ingest=True, matrix_build=True):
 
 def patch_reassign(R):
     """R: the imported HapHiC_reassign module.  f3: parse_link_dict :217-263 (the per-group link sums behind reassign's
-    link densities) on the device for integer link counts; float / normalised links go to the original function."""
-    from . import _lib
+    link densities) on the device for integer link counts; float / normalised links go to the original function.
+    split_clm_file :581-622 (paired_links.clm routed line by line to split_clms/<group>.clm) goes through the device too
+    (haphic_amd/reassign.py); the cases the reference answers with an exception of its own go to the original function."""
+    from . import _lib, reassign
     _lib.load()
     original = R.parse_link_dict
+    original_split = R.split_clm_file
 
     def parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks=False):
         return cluster.parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks, _original=original)
     parse_link_dict.__wrapped__ = cluster.parse_link_dict
     R.parse_link_dict = parse_link_dict
-    return {'parse_link_dict': original}
+
+    def split_clm_file(clm_file, group_ctg_dict, ctg_group_dict, subdir):
+        return reassign.split_clm_file(clm_file, group_ctg_dict, ctg_group_dict, subdir, _original=original_split)
+    split_clm_file.__wrapped__ = reassign.split_clm_file
+    R.split_clm_file = split_clm_file
+    return {'parse_link_dict': original, 'split_clm_file': original_split}
 
 
 def unpatch_reference(H, saved):

@@ -399,6 +399,9 @@ int hhx_text_reader_open_bgzf(const char *path, int64_t chunk_bytes, int n_threa
  * the next '\n', so the ranges [b_r, b_{r+1}) of consecutive boundaries hand out every line once, in order; a range may be empty.  bgzf != 0: begin /
  * end are COMPRESSED offsets, the range owns the BGZF blocks that start in it and the same line rule applies to their inflated text. */
 int hhx_text_reader_open_range(const char *path, int64_t begin, int64_t end, int64_t chunk_bytes, int n_threads, int bgzf, hhx_text_reader **out);
+/* the bytes of the file as they are, chunk_bytes per chunk (the last one shorter), cut anywhere and nothing carried: for a consumer that keeps its own
+ * state across cuts (hhx_clm_split_file), so that a line of any length passes. */
+int hhx_text_reader_open_raw(const char *path, int64_t chunk_bytes, int n_threads, hhx_text_reader **out);
 int hhx_text_reader_next(hhx_text_reader *r, const uint8_t **host, int64_t *n_bytes);
 int hhx_text_reader_close(hhx_text_reader *r);
 /* measurement only — the writer counterpart of hhx_pairs_parse for synthetic read pairs ("pairs written as .pairs text"): line k =
@@ -570,6 +573,29 @@ int hhx_byte_sink_close(hhx_byte_sink *sink, int64_t *n_bytes_pushed);
 int hhx_byte_sink_open_deferred(const char *path, int64_t hbm_budget_bytes, int64_t expected_bytes, hhx_byte_sink **out);
 int hhx_byte_sink_set_base(hhx_byte_sink *sink, int64_t base);
 int hhx_pairs_parser_set_bed_sink(hhx_pairs_parser *p, hhx_byte_sink *sink);
+/* paired_links.clm split by group for `haphic reassign`: split_clm_file, scripts/HapHiC_reassign.py:581-622.  Per line (text mode, universal
+ * newlines: '\n', "\r\n" and a lone '\r' end a line, which is written with '\n'; a last line without a break keeps none): cols = line.split();
+ * the last character of cols[0] and of cols[1] is dropped; the line goes verbatim to the file of the group both names belong to, when both are
+ * in the table and in the same group (group_of_name[k] in [0, n_groups), -1: in no group).  Every group's file (paths_blob / path_off, one path
+ * per group) is created, possibly empty; lines keep file order inside a file; at most n_groups descriptors are open, as in the reference.
+ * hhx_clm_split_push takes ANY byte range of the file, in order: a cut may fall anywhere (inside a token, between '\r' and '\n', inside a line
+ * of megabytes, which is never held whole).  Only the head of a line whose first two tokens are not complete yet is buffered (at most 64 KB,
+ * a clear failure beyond).  hhx_clm_split_file pushes the whole file as raw chunks of chunk_bytes from pinned read-ahead buffers.
+ * The first line with fewer than two tokens fails the call with "IndexError: list index out of range" in hhx_last_error(), as :617 raises;
+ * a line still open at hhx_clm_split_finish counts too unless it has no bytes.  hhx_clm_split_finish flushes the open line and waits for the
+ * writer lanes: the files are complete and closed on return (bytes_per_group[n_groups], may be NULL).  Whitespace is the ASCII subset of
+ * str.split()'s, bytes >= 0x80 are name bytes (as for hhx_pairs_parse).
+ * hhx_clm_split_stats: values[HHX_CLM_SPLIT_N_STATS] = lines parsed, lines kept, heads carried to the next push, "\r" | "\n" seams joined,
+ * continuation segments of an open line, gather tiles that held more than one line, lines that spanned more than one gather tile. */
+#define HHX_CLM_SPLIT_N_STATS 7
+typedef struct hhx_clm_split hhx_clm_split;
+int hhx_clm_split_create(int32_t n_names, const uint8_t *names_blob, const int64_t *name_off, const int32_t *group_of_name, int32_t n_groups,
+                         const uint8_t *paths_blob, const int64_t *path_off, hhx_clm_split **out);
+int hhx_clm_split_push(hhx_clm_split *s, const uint8_t *text, int64_t n_bytes, int on_device);
+int hhx_clm_split_file(hhx_clm_split *s, const char *clm_path, int64_t chunk_bytes, int n_threads);
+int hhx_clm_split_finish(hhx_clm_split *s, int64_t *n_lines, int64_t *n_kept, int64_t *bytes_per_group);
+int hhx_clm_split_stats(hhx_clm_split *s, int64_t *values);
+int hhx_clm_split_destroy(hhx_clm_split *s);
 int hhx_files_pending(int64_t *n_pending, int64_t *n_done);
 int hhx_files_join(int64_t *n_failed);
 
