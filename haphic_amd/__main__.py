@@ -10,6 +10,9 @@ matrix and the median behind vmax; `log10` / `none`: the median alone) run on th
 `python -m haphic_amd reassign <arguments of "haphic reassign">` wraps HapHiC_reassign.py: parse_link_dict (the per-group link sums) and
 split_clm_file (paired_links.clm split into split_clms/<group>.clm, haphic_amd/reassign.py) run on the device (haphic_amd.patch.patch_reassign);
 the rescue rounds and run() :752-916 are the reference's, called as its main() :919-924 calls them.
+`python -m haphic_amd sort <arguments of "haphic sort">` wraps HapHiC_sort.py: the dense work of fast sorting (link matrix, density graph, confidence
+graph and the link re-aggregation of every round, haphic_amd/sort.py) runs on the device (haphic_amd.patch.patch_sort); fast_sort's loop, the spanning
+forest, the ALLHiC child per group and run() :847-959 are the reference's, its process pool replaced by threads; called as its main() :962-967 does.  `sort` with nothing after it has nothing to hand on and exits with a usage message.
 
 The reference checkout is found through --reference DIR or $HAPHIC_REFERENCE (the repository root or its scripts/
 directory).  Extra flags of the wrapper (removed before the reference parses the command line):
@@ -55,11 +58,15 @@ def main(argv=None):
         print(__doc__)
         return 0
     command = argv.pop(0)
-    if command not in ('cluster', 'plot', 'reassign'):
-        raise SystemExit('haphic_amd wraps the "cluster", "plot" and "reassign" steps only (got {!r}); run the other steps with the reference'.format(command))
+    if command not in ('cluster', 'plot', 'reassign', 'sort'):
+        raise SystemExit('haphic_amd wraps the "cluster", "plot", "reassign" and "sort" steps only (got {!r}); run the other steps with the reference'.format(command))
+    if command == 'sort' and not argv:
+        # nothing to hand to the reference: say what the wrapper is, as for a step it does not wrap, rather than go looking for the checkout
+        raise SystemExit('haphic_amd wraps the "cluster", "plot", "reassign" and "sort" steps only and hands them the arguments of the reference\'s '
+                         'command; {!r} came without any (haphic sort: fasta HT_links clm_dir groups ...)'.format(command))
     from . import ranks
     gpus, host_transport = ranks.take_args(argv)
-    if command in ('plot', 'reassign') and (gpus or 1) > 1:
+    if command in ('plot', 'reassign', 'sort') and (gpus or 1) > 1:
         raise SystemExit('--gpus is a flag of the "cluster" step only')
     if (gpus or 1) > 1 and not ranks.in_torchrun():
         # one fresh child process per rank (never exec: this process may not replace itself), each with RANK / WORLD_SIZE / LOCAL_RANK
@@ -95,6 +102,14 @@ def main(argv=None):
         patch.patch_reassign(R)
         sys.argv = ['haphic reassign'] + argv
         R.run(R.parse_arguments(), 'HapHiC_reassign.log')           # == HapHiC_reassign.main() :919-924
+        return 0
+    if command == 'sort':
+        import HapHiC_sort as S                                     # needs networkx / scipy, as the reference does
+        from . import sort
+        sort.DEVICE = device                                        # the pool's threads select it before their first call
+        patch.patch_sort(S)
+        sys.argv = ['haphic sort'] + argv
+        S.run(S.parse_arguments(), 'HapHiC_sort.log')               # == HapHiC_sort.main() :962-967
         return 0
     import HapHiC_cluster as H                                      # the unmodified reference module
     patch.patch_reference(H, ingest=not keep_ingest)

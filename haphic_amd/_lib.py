@@ -190,6 +190,20 @@ SIGNATURES = {
     'hhx_remap_create': (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, c_vpp]),
     'hhx_remap_apply': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'hhx_remap_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_sort_graph_create': (C.c_int, [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, c_vpp]),
+    'hhx_sort_graph_shape': (C.c_int, [C.c_void_p, c_i32p, c_i64p, c_i64p]),
+    'hhx_sort_graph_density': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64p]),
+    'hhx_sort_graph_fetch_flagged': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_patch_len': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_confidence': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_drop': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    'hhx_sort_graph_aggregate': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, c_i64p, c_i64p]),
+    'hhx_sort_graph_fetch_edges': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_fetch_over': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_patch_cells': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_fetch_dense': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    'hhx_sort_graph_stats': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_destroy': (C.c_int, [C.c_void_p]),
 }
 
 _lib = None
@@ -696,6 +710,103 @@ class ClmSplit:
     def close(self):
         if self.h is not None and self.h.value:
             load().hhx_clm_split_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SortGraph:
+    """hhx_sort_graph: the dense work of one group of `haphic sort`'s fast sorting (HapHiC_sort.py :60-88 :158-244 :406-435 :456-467), per round.
+    Built from the round-1 edges (index pairs, integer weights); tests/sort_cases.py holds a numpy engine with the same interface."""
+    METHODS = {'sum': 0, 'multiplication': 1, 'geometric_mean': 2}
+    STATS = ('lds_aggregations', 'global_aggregations', 'cells_over', 'pairs_flagged')
+
+    def __init__(self, shape, ei, ej, w):
+        ei, ej = np.ascontiguousarray(ei, np.int32), np.ascontiguousarray(ej, np.int32)
+        w = np.ascontiguousarray(w, np.int64)
+        if not (ei.size == ej.size == w.size):
+            raise ValueError('SortGraph: {} / {} indices, {} weights'.format(ei.size, ej.size, w.size))
+        self.h = C.c_void_p()
+        check(load().hhx_sort_graph_create(int(shape), ei.size, ptr(ei) if ei.size else None, ptr(ej) if ei.size else None, ptr(w) if ei.size else None,
+                                           C.byref(self.h)))
+
+    @property
+    def shape(self):
+        n = C.c_int32(0)
+        check(load().hhx_sort_graph_shape(self.h, C.byref(n), None, None))
+        return n.value
+
+    def density(self, lengths, method):
+        """D = S / L on the device -> the flagged geometric-mean pairs as an (n, 2) int32 array (usually empty) for patch_len"""
+        ln = np.ascontiguousarray(lengths, np.float64)
+        if ln.size != self.shape:
+            raise ValueError('SortGraph.density: {} lengths for shape {}'.format(ln.size, self.shape))
+        n = C.c_int64(0)
+        check(load().hhx_sort_graph_density(self.h, ptr(ln), self.METHODS[method] if isinstance(method, str) else int(method), C.byref(n)))
+        pairs = np.empty((n.value, 2), np.int32)
+        if n.value:
+            check(load().hhx_sort_graph_fetch_flagged(self.h, ptr(pairs)))
+        return pairs
+
+    def patch_len(self, pairs, L):
+        pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+        pi, pj = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+        L = np.ascontiguousarray(L, np.float32)
+        check(load().hhx_sort_graph_patch_len(self.h, pi.size, ptr(pi), ptr(pj), ptr(L)))
+
+    def confidence(self, pair_a, pair_b):
+        """-> (float64 array shape x shape, MAXS as numpy.float64); the array is a view of the one buffer the device copy filled"""
+        pa, pb = np.ascontiguousarray(pair_a, np.int32), np.ascontiguousarray(pair_b, np.int32)
+        n = self.shape
+        buf = np.empty(n * n + 1, np.float64)
+        check(load().hhx_sort_graph_confidence(self.h, pa.size, ptr(pa) if pa.size else None, ptr(pb) if pb.size else None, ptr(buf)))
+        return buf[:n * n].reshape(n, n), buf[n * n]
+
+    def drop(self, a, b):
+        check(load().hhx_sort_graph_drop(self.h, int(a), int(b)))
+
+    def aggregate(self, new_shape, index_map):
+        """-> (i, j, w, cells_over): the new edges (i > j, row-major, float32 values) and the positions i * new_shape + j of the cells above 2^24"""
+        m = np.ascontiguousarray(index_map, np.int32)
+        ne, no = C.c_int64(0), C.c_int64(0)
+        check(load().hhx_sort_graph_aggregate(self.h, int(new_shape), ptr(m), C.byref(ne), C.byref(no)))
+        ei, ej, w = np.empty(ne.value, np.int32), np.empty(ne.value, np.int32), np.empty(ne.value, np.float32)
+        check(load().hhx_sort_graph_fetch_edges(self.h, ptr(ei), ptr(ej), ptr(w)))
+        over = np.empty(no.value, np.int64)
+        if no.value:
+            check(load().hhx_sort_graph_fetch_over(self.h, ptr(over)))
+            over.sort()
+        return ei, ej, w, over
+
+    def patch_cells(self, cells, ordinal, values):
+        c, o = np.ascontiguousarray(cells, np.int64), np.ascontiguousarray(ordinal, np.int64)
+        v = np.ascontiguousarray(values, np.float32)
+        check(load().hhx_sort_graph_patch_cells(self.h, c.size, ptr(c), ptr(o), ptr(v)))
+
+    def matrix(self):
+        return self._dense(0)
+
+    def density_graph(self):
+        return self._dense(1)
+
+    def _dense(self, which):
+        n = self.shape
+        out = np.empty((n, n), np.float32)
+        check(load().hhx_sort_graph_fetch_dense(self.h, which, ptr(out)))
+        return out
+
+    def stats(self):
+        v = np.zeros(len(self.STATS), np.int64)
+        check(load().hhx_sort_graph_stats(self.h, ptr(v)))
+        return dict(zip(self.STATS, (int(x) for x in v)))
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            load().hhx_sort_graph_destroy(self.h)
             self.h = None
 
     def __del__(self):

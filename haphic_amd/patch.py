@@ -160,6 +160,39 @@ def patch_reassign(R):
     return {'parse_link_dict': original, 'split_clm_file': original_split}
 
 
+# `haphic sort`: the module globals fast_sort :470-615 resolves at call time (haphic_amd/sort.py)
+SORT_SEAMS = {
+    'dict_to_matrix': 'HapHiC_sort.py:60-88',
+    'get_density_graph': 'HapHiC_sort.py:158-192',
+    'get_unfiltered_confidence_graph': 'HapHiC_sort.py:195-244',
+    'filter_confidence_graph': 'HapHiC_sort.py:247-255',
+    'remove_shortest_path': 'HapHiC_sort.py:456-467',
+    'update': 'HapHiC_sort.py:338-437',
+    'fast_sort': 'HapHiC_sort.py:470-615',          # the reference's own function, entered under sort.DEVICE_LOCK
+}
+
+
+def patch_sort(S, engine=None):
+    """S: the imported HapHiC_sort module.  The dense work of fast sorting goes to the device (haphic_amd/sort.py); fast_sort, the spanning forest,
+    split_new_scaffold, the .tour writer, the ALLHiC child and run() stay the reference's.  run() :875-876 forks a multiprocessing.Pool: a process
+    that has initialised the GPU must not be forked into workers that use it, so S.Pool becomes the ThreadPool (same apply_async / close / join);
+    one lock serialises the device part across its threads, the ALLHiC children run beside it.  engine: a stand-in for _lib.SortGraph (the tests'
+    numpy engine).  Returns {name: original}."""
+    from multiprocessing.pool import ThreadPool
+    from . import sort
+    if engine is None:
+        from . import _lib
+        _lib.load()
+    mirrors = sort.bind(S, engine)
+    assert set(mirrors) == set(SORT_SEAMS)
+    saved = {name: getattr(S, name) for name in mirrors}
+    saved['Pool'] = S.Pool
+    for name, fn in mirrors.items():
+        setattr(S, name, fn)
+    S.Pool = ThreadPool
+    return saved
+
+
 def unpatch_reference(H, saved):
     for name, fn in saved.items():
         if fn is None and hasattr(H, name):

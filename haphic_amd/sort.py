@@ -1,0 +1,266 @@
+"""`haphic sort` (scripts/HapHiC_sort.py), fast sorting on the MI355X library: the dense work of fast_sort :470-615 per group and round.
+
+fast_sort itself, the spanning forest :570-595, split_new_scaffold, output_tour_file, the ALLHiC optimisation and run() stay the reference's code;
+the functions below replace the module globals fast_sort resolves at call time (patch.patch_sort):
+
+    dict_to_matrix :60-88                     round 1: the dict's edges go to the device once (_lib.SortGraph), later rounds: the handle again
+    get_density_graph :158-192                lengths per index on the host (float64), length matrix and division on the device
+    get_unfiltered_confidence_graph :195-244  per-row top-3 + one thread per edge; one copy of the float64 array networkx reads
+    filter_confidence_graph :247-255          vectorised over the edge arrays
+    remove_shortest_path :456-467             the last pair popped, its edges dropped, the matrices cut as a view on the device
+    update :338-437                           the work on names here, the link re-aggregation as a scatter-add on the device
+
+What the device path does not cover (weights that are not non-negative integers, an empty dict, a shape below 4) is decided once, in round 1:
+dict_to_matrix then returns the reference's numpy matrix and every seam hands such a group to the original functions.  The new sub_HT_dict is a
+SubHT: a defaultdict that stays arrays until something other than these seams touches it (the pattern of containers.py)."""
+import threading
+from itertools import product
+
+import numpy as np
+
+from . import containers
+
+METHODS = ('sum', 'multiplication', 'geometric_mean')
+DEVICE_LOCK = threading.Lock()        # one group on the device at a time; the other threads of run()'s pool are in their ALLHiC child meanwhile
+_tls = threading.local()              # .graph: the Graph of the group this thread's fast_sort is working on
+
+
+DEVICE = None                         # the HIP device of `--device N`: HIP's current device is per thread, and run()'s pool threads start on device 0
+
+
+def _default_engine(shape, ei, ej, w):
+    from . import _lib
+    if DEVICE is not None:
+        _lib.check(_lib.load().hhx_set_device(DEVICE))
+    return _lib.SortGraph(shape, ei, ej, w)
+
+
+class Graph:
+    """What dict_to_matrix / get_density_graph / remove_shortest_path hand to fast_sort in place of a numpy matrix: the device handle of the group
+    plus the round-1 edges as host arrays (filter_confidence_graph and the cells update() has to sum in the reference's order need them)."""
+
+    def __init__(self, engine, shape, source, ei, ej, w):
+        self.engine = engine
+        self.shape0 = shape
+        self.source = source                              # the round-1 dict itself: recognised by identity
+        self.ei, self.ej, self.w = ei, ej, w
+        self.alive = np.ones(ei.size, bool)               # remove_shortest_path in round 1
+        self.host_mode = False                            # a SubHT was thawed by foreign code: the rest of the group runs the reference's functions
+        self._lookup = None
+        self.thaws = 0
+
+    def note_thawed(self):
+        self.thaws += 1
+
+    def links(self, a, b):
+        """old_sub_HT_matrix[a, b] (:432) as numpy.float32"""
+        if self._lookup is None:
+            vals = self.w.astype(np.float32)
+            self._lookup = dict(zip(zip(np.minimum(self.ei, self.ej).tolist(), np.maximum(self.ei, self.ej).tolist()), list(vals)))
+        return self._lookup.get((a, b) if a < b else (b, a), np.float32(0))
+
+    def dense_round1(self):
+        m = np.zeros((self.shape0, self.shape0), np.float32)
+        m[self.ei, self.ej] = self.w
+        m[self.ej, self.ei] = self.w
+        return m
+
+    def close(self):
+        close = getattr(self.engine, 'close', None)
+        if close is not None:
+            close()
+
+
+class SubHT(containers._Frozen):
+    """The sub_HT_dict update() returns: {(i_1, i_2): numpy.float32}, i_1 > i_2, row-major — as three arrays until it is touched."""
+
+    def __init__(self, graph, i, j, w):
+        containers._Frozen.__init__(self, int, graph, 'sub_HT')
+        self.i, self.j, self.w = i, j, w
+
+    def _n(self):
+        return int(self.i.size)
+
+    def _source_items(self):
+        return zip(zip(self.i.tolist(), self.j.tolist()), list(self.w))
+
+    def drop_touching(self, a, b):
+        keep = ~((self.i == a) | (self.i == b) | (self.j == a) | (self.j == b))
+        self.i, self.j, self.w = self.i[keep], self.j[keep], self.w[keep]
+
+
+def _frozen(d):
+    return isinstance(d, SubHT) and d.frozen
+
+
+def _round1_arrays(dict_, shape):
+    """(i, j, w) of a dict the device path covers, else None"""
+    n = len(dict_)
+    if n == 0 or shape < 4 or shape % 2:
+        return None
+    try:
+        keys = np.array(list(dict_.keys()))
+        vals = np.array(list(dict_.values()))
+    except (ValueError, TypeError, OverflowError):
+        return None
+    if keys.shape != (n, 2) or keys.dtype.kind not in 'iu' or vals.shape != (n,) or vals.dtype.kind not in 'iu':
+        return None
+    i, j = keys[:, 0].astype(np.int64), keys[:, 1].astype(np.int64)
+    if i.min() < 0 or j.min() < 0 or i.max() >= shape or j.max() >= shape or (i == j).any() or vals.min() < 0 or int(vals.max()) > 2 ** 53:
+        return None
+    if np.unique(np.maximum(i, j) * shape + np.minimum(i, j)).size != n:       # (a, b) and (b, a): coo_matrix would add them up
+        return None
+    return i.astype(np.int32), j.astype(np.int32), vals.astype(np.int64)
+
+
+def bind(S, engine=None):
+    """The mirrors for the imported HapHiC_sort module S -> {name: function}.  engine(shape, ei, ej, w): the SortGraph factory (the device by default)."""
+    make_engine = engine or _default_engine
+    original = {name: getattr(S, name) for name in ('dict_to_matrix', 'get_density_graph', 'get_unfiltered_confidence_graph', 'filter_confidence_graph',
+                                                    'remove_shortest_path', 'update', 'fast_sort')}
+
+    def dict_to_matrix(dict_, shape, add_self_loops=False):
+        g = getattr(_tls, 'graph', None)
+        if add_self_loops:                                 # the length matrix inside the reference's own get_density_graph
+            return original['dict_to_matrix'](dict_, shape, add_self_loops)
+        if g is not None and _frozen(dict_) and dict_._session is g and not g.host_mode:
+            return g                                       # the link matrix is already on the device (update)
+        if g is None and not isinstance(dict_, SubHT):
+            arrays = _round1_arrays(dict_, shape)
+            if arrays is not None:
+                g = Graph(make_engine(shape, *arrays), shape, dict_, *arrays)
+                _tls.graph = g
+                return g
+            _tls.graph = False                             # decided once: this group is the reference's
+        elif g:
+            g.host_mode = True
+        return original['dict_to_matrix'](dict_, shape)
+
+    def get_density_graph(sub_HT_matrix, shape, index_HT_dict, fa_dict, flank_HT_dict, density_cal_method):
+        if not isinstance(sub_HT_matrix, Graph):
+            return original['get_density_graph'](sub_HT_matrix, shape, index_HT_dict, fa_dict, flank_HT_dict, density_cal_method)
+        g = sub_HT_matrix
+        lengths = []
+        for k in range(shape):
+            HT = index_HT_dict[k]
+            lengths.append(flank_HT_dict[HT][1] if HT in flank_HT_dict else S.get_len(HT, fa_dict))
+        flagged = g.engine.density(lengths, density_cal_method)
+        if len(flagged):                                   # geometric_mean: Python's ** decides the pairs next to a float32 rounding boundary
+            g.engine.patch_len(flagged, [np.float32((lengths[a] * lengths[b]) ** 0.5) for a, b in flagged.tolist()])
+        return g
+
+    def get_unfiltered_confidence_graph(shape, index_pairs, sub_HT_dict, density_graph):
+        if not isinstance(density_graph, Graph):
+            return original['get_unfiltered_confidence_graph'](shape, index_pairs, sub_HT_dict, density_graph)
+        pairs = np.array(index_pairs, np.int32).reshape(-1, 2)
+        confidence_graph, maxs = density_graph.engine.confidence(pairs[:, 0], pairs[:, 1])
+        assert confidence_graph.shape == (shape, shape)
+        return confidence_graph, maxs
+
+    def _edges_of(sub_HT_dict):
+        g = getattr(_tls, 'graph', None)
+        if _frozen(sub_HT_dict):
+            return sub_HT_dict.i, sub_HT_dict.j
+        if g and sub_HT_dict is g.source and not g.host_mode:
+            return g.ei[g.alive], g.ej[g.alive]
+        return None
+
+    def filter_confidence_graph(confidence_graph, sub_HT_dict, confidence_cutoff):
+        edges = _edges_of(sub_HT_dict)
+        if edges is None:
+            return original['filter_confidence_graph'](confidence_graph, sub_HT_dict, confidence_cutoff)
+        i, j = edges
+        low = confidence_graph[i, j] <= confidence_cutoff
+        confidence_graph[i[low], j[low]] = 0
+        confidence_graph[j[low], i[low]] = 0
+
+    def remove_shortest_path(index_pairs, sub_HT_dict, density_graph):
+        if not isinstance(density_graph, Graph):
+            return original['remove_shortest_path'](index_pairs, sub_HT_dict, density_graph)
+        g = density_graph
+        a, b = index_pairs.pop(-1)
+        if _frozen(sub_HT_dict):
+            sub_HT_dict.drop_touching(a, b)
+        else:
+            for key in [key for key in sub_HT_dict if a in key or b in key]:
+                sub_HT_dict.pop(key)
+            if sub_HT_dict is g.source:
+                g.alive &= ~((g.ei == a) | (g.ei == b) | (g.ej == a) | (g.ej == b))
+        g.engine.drop(a, b)                                # the last two rows and columns leave the view; no copy
+        return g
+
+    def update(path_list, old_sub_HT_matrix, index_HT_dict, HT_index_dict, flank_HT_dict, fa_dict, known_adjacency, flank):
+        if not isinstance(old_sub_HT_matrix, Graph):
+            return original['update'](path_list, old_sub_HT_matrix, index_HT_dict, HT_index_dict, flank_HT_dict, fa_dict, known_adjacency, flank)
+        g = old_sub_HT_matrix
+        if g.host_mode:
+            return original['update'](path_list, g.dense_round1(), index_HT_dict, HT_index_dict, flank_HT_dict, fa_dict, known_adjacency, flank)
+
+        def trim(half, order):
+            """the part of a scaffold half within `flank` of the junction-far end (get_flank_HT :347-363)"""
+            rest = S.get_len(half, fa_dict)
+            if rest <= flank:
+                return
+            m = 0
+            for m, HT in enumerate(half[::order]):
+                length = S.get_len(HT, fa_dict)
+                if rest - length > flank:
+                    rest -= length
+                else:
+                    break
+            kept = half if m == 0 else (half[:-m] if order == 1 else half[m:])
+            flank_HT_dict[half] = (kept, S.get_len(kept, fa_dict))
+
+        index_pairs, new_index_HT_dict, output_path_list = [], {}, []
+        for n, path in enumerate(path_list):
+            lo, hi = 2 * n, 2 * n + 1
+            index_pairs.append((hi, lo))
+            if len(path) == 2:                             # a contig, or a scaffold of an earlier round
+                left, right = index_HT_dict[path[0]], index_HT_dict[path[1]]
+                output_path_list.append(list(S.format_HTs(left)) + list(S.format_HTs(right)))
+            else:                                          # linked in this round: two halves of about the same length
+                left, right = S.split_new_scaffold(path, fa_dict, index_HT_dict, known_adjacency)
+                output_path_list.append(list(left) + list(right))
+                if flank:
+                    trim(left, -1)
+                    trim(right, 1)
+            new_index_HT_dict[lo], new_index_HT_dict[hi] = left, right
+
+        def ends_of(k):
+            HT = new_index_HT_dict[k]
+            return S.format_HTs(flank_HT_dict[HT][0] if HT in flank_HT_dict else HT)
+
+        new_shape = 2 * len(path_list)
+        index_map = np.full(g.shape0, -1, np.int32)
+        for k in range(new_shape):
+            for ht in ends_of(k):
+                index_map[HT_index_dict[ht]] = k
+        i, j, w, over = g.engine.aggregate(new_shape, index_map)
+        if over.size:                                      # sums past 2^24: numpy.float32 by numpy.float32 in the order of product(HT_1, HT_2) :427-435
+            ordinal = np.searchsorted(i.astype(np.int64) * new_shape + j, over)
+            values = np.empty(over.size, np.float32)
+            for k, cell in enumerate(over.tolist()):
+                total = 0
+                for ht_1, ht_2 in product(ends_of(cell // new_shape), ends_of(cell % new_shape)):
+                    links = g.links(HT_index_dict[ht_1], HT_index_dict[ht_2])
+                    if links:
+                        total += links
+                values[k] = total
+            w[ordinal] = values
+            g.engine.patch_cells(over, ordinal, values)
+        return new_index_HT_dict, SubHT(g, i, j, w), index_pairs, output_path_list
+
+    def fast_sort(args, fa_dict, group_specific_data, prefix):
+        with DEVICE_LOCK:
+            _tls.graph = None
+            try:
+                return original['fast_sort'](args, fa_dict, group_specific_data, prefix)
+            finally:
+                g = getattr(_tls, 'graph', None)
+                _tls.graph = None
+                if g:
+                    g.close()
+    fast_sort.__wrapped__ = original['fast_sort']
+
+    return {'dict_to_matrix': dict_to_matrix, 'get_density_graph': get_density_graph, 'get_unfiltered_confidence_graph': get_unfiltered_confidence_graph,
+            'filter_confidence_graph': filter_confidence_graph, 'remove_shortest_path': remove_shortest_path, 'update': update, 'fast_sort': fast_sort}

@@ -69,7 +69,8 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * block (bins) hhx_plotnorm_balance runs inside one workgroup, clamped to [0, 512] (default 512; 0: every block is steered from the host;
  * the two implementations sum in another order, so the blocks' x agrees within the spread the reference's bnewt shows under a permutation,
  * step counts equal); "plotnorm_chunk_cells" = cells per upload / apply chunk of hhx_plotnorm (default 2^24, at least 1: one row per chunk;
- * same bits).  value INT64_MIN: back to the default.  Unset knobs fall back to the
+ * same bits); "sort_lds_shape" = the largest new shape whose re-aggregation of hhx_sort_graph_aggregate accumulates in LDS, clamped to [0, 192]
+ * (default 192; 0: always global atomics; same bits).  value INT64_MIN: back to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
 int hhx_profile_enable(int on);
@@ -657,6 +658,47 @@ typedef struct hhx_remap hhx_remap;
 int hhx_remap_create(int32_t n_src, const int32_t *off, const int32_t *break_pos, const int32_t *new_id, hhx_remap **out);
 int hhx_remap_apply(hhx_remap *r, int64_t n, int32_t *dev_id, int32_t *dev_pos);
 int hhx_remap_destroy(hhx_remap *r);
+
+/* ---------------------------------------------------------------- `haphic sort`: fast sorting (HapHiC_sort.py fast_sort :470-615)
+ * One handle per group holds the dense work of every round on the device (csrc/hhx_sort.hip); the spanning forest and the work on names stay on the host.
+ * hhx_sort_graph_create — dict_to_matrix :60-88 of round 1: the dict's keys (index pairs in [0, shape), either orientation, no pair twice) and integer
+ *   weights >= 0 become the dense symmetric float32 link matrix; the edge list stays on the device for the whole group, because update :406-435 always
+ *   aggregates from old_sub_HT_matrix.  shape: even, at least 4.
+ * hhx_sort_graph_density — get_density_graph :158-192: len[shape] float64 (get_HT_len of every index, flank_HT_dict included); L[i][j] = len_i + len_j
+ *   (method 0, 'sum'), len_i * len_j (1, 'multiplication') or sqrt(len_i * len_j) (2, 'geometric_mean') in float64, rounded to float32, 1 on the diagonal;
+ *   D = S / L in float32.  Method 2 reports in *n_flagged the pairs i < j whose float64 root lies within 2 ulp of a float32 rounding boundary (Python's
+ *   (a * b) ** 0.5 may round the other way): hhx_sort_graph_fetch_flagged copies them (i, j interleaved), the caller computes L with ** and hands it
+ *   to hhx_sort_graph_patch_len, which redoes D[i][j] = D[j][i] = S / L.
+ * hhx_sort_graph_confidence — get_unfiltered_confidence_graph :195-244 on the current edges: out[shape * shape + 1] float64 receives the matrix (0 where
+ *   no edge; per edge 0 if its density is 0, 2 if the second largest density incident on either end is 0, else float32(d / second); sister pairs
+ *   (pair_a[k], pair_b[k]) get 2 * MAXS if MAXS > 1 else 2) and, in its last element, MAXS — one copy.
+ * hhx_sort_graph_drop — remove_shortest_path :456-467: the edges touching a or b (which must be the last two indices) leave the current edge list,
+ *   the matrices keep their pitch and lose their last two rows and columns (no copy).
+ * hhx_sort_graph_aggregate — the link re-aggregation of update :406-435: map[old index of round 1] = new index or -1; every round-1 edge (a, b, w) with
+ *   i = map[a], j = map[b], both >= 0, i != j, i ^ 1 != j adds w to cell (max, min) of an integer accumulator (in LDS while new_shape <= 192 and the
+ *   weights sum to less than 2^32, hhx_tune "sort_lds_shape"; with global atomics above).  The handle then holds the new link matrix and the new edge
+ *   list (keys (i_1, i_2) with i_1 > i_2 in row-major order, float32 values: hhx_sort_graph_fetch_edges).  *n_over: cells whose sum exceeds 2^24, where
+ *   the reference's float32 running sum may round: hhx_sort_graph_fetch_over copies their positions (i_1 * new_shape + i_2, any order), the caller sums
+ *   them in the reference's order and hands the values to hhx_sort_graph_patch_cells (ordinal: the edge's position in the list).
+ * hhx_sort_graph_fetch_dense: the leading shape x shape block of the link matrix (which = 0) or the density graph (1), row-major float32.
+ * hhx_sort_graph_stats: values[HHX_SORT_GRAPH_N_STATS] = re-aggregations through LDS, through global atomics, cells above 2^24 of the last one, flagged
+ *   pairs of the last density call. */
+#define HHX_SORT_GRAPH_N_STATS 4
+typedef struct hhx_sort_graph hhx_sort_graph;
+int hhx_sort_graph_create(int32_t shape, int64_t n_edges, const int32_t *ei, const int32_t *ej, const int64_t *w, hhx_sort_graph **out);
+int hhx_sort_graph_shape(const hhx_sort_graph *g, int32_t *shape, int64_t *ld, int64_t *n_edges);
+int hhx_sort_graph_density(hhx_sort_graph *g, const double *len, int method, int64_t *n_flagged);
+int hhx_sort_graph_fetch_flagged(hhx_sort_graph *g, int32_t *pairs);
+int hhx_sort_graph_patch_len(hhx_sort_graph *g, int64_t n, const int32_t *pi, const int32_t *pj, const float *L);
+int hhx_sort_graph_confidence(hhx_sort_graph *g, int32_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double *out);
+int hhx_sort_graph_drop(hhx_sort_graph *g, int32_t a, int32_t b);
+int hhx_sort_graph_aggregate(hhx_sort_graph *g, int32_t new_shape, const int32_t *map, int64_t *n_edges, int64_t *n_over);
+int hhx_sort_graph_fetch_edges(hhx_sort_graph *g, int32_t *ei, int32_t *ej, float *w);
+int hhx_sort_graph_fetch_over(hhx_sort_graph *g, int64_t *cells);
+int hhx_sort_graph_patch_cells(hhx_sort_graph *g, int64_t n, const int64_t *cells, const int64_t *ordinal, const float *val);
+int hhx_sort_graph_fetch_dense(hhx_sort_graph *g, int which, float *out);
+int hhx_sort_graph_stats(const hhx_sort_graph *g, int64_t *values);
+int hhx_sort_graph_destroy(hhx_sort_graph *g);
 
 #ifdef __cplusplus
 }
