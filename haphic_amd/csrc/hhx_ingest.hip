@@ -130,9 +130,10 @@ struct SrcMapped {
     typedef u32 w1_t;
     static constexpr bool MARK = false;
     static constexpr bool BATCHED = true;      // hhx_partition.h: the loads of a whole tile are issued before the first is consumed
-    static constexpr int CHUNK = 16, CHUNK_SCATTER = 16;
+    static constexpr int CHUNK = 16, CHUNK_SCATTER = 16, PREFETCH = 2;     // k_part_scatter: the whole next tile in flight
     const u64 *rec;
     struct Raw { u64 a; };
+    static __device__ __forceinline__ void pin(Raw &r) { asm volatile("" : "+v"(r.a)); }
     __device__ __forceinline__ void load1(i64 idx, Raw &r) const { r.a = rec[idx]; }
     __device__ __forceinline__ void load2(Raw &) const {}
     __device__ __forceinline__ bool decode(i64 idx, const Raw &r, u64 &w0, u32 &ord) const {
@@ -150,9 +151,10 @@ struct SrcRows {            // table rows to be merged: the record is the bare k
     typedef u32 w1_t;
     static constexpr bool MARK = false;
     static constexpr bool BATCHED = true;
-    static constexpr int CHUNK = 16, CHUNK_SCATTER = 16;
+    static constexpr int CHUNK = 16, CHUNK_SCATTER = 16, PREFETCH = 2;     // k_part_scatter: the whole next tile in flight
     const u64 *key;
     struct Raw { u64 a; };
+    static __device__ __forceinline__ void pin(Raw &r) { asm volatile("" : "+v"(r.a)); }
     __device__ __forceinline__ void load1(i64 idx, Raw &r) const { r.a = key[idx]; }
     __device__ __forceinline__ void load2(Raw &) const {}
     __device__ __forceinline__ bool decode(i64 idx, const Raw &r, u64 &rec, u32 &ord) const {

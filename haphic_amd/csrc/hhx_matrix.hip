@@ -327,6 +327,10 @@ struct SrcDirectedPacked {
     // the loads of a record without a branch between them (hhx_partition.h: BATCHED): the three words of the table row, then the
     // two membership bytes its key points at — every load of a chunk of records is in flight before the first is consumed
     struct Raw { u64 ord, ky; u32 c; unsigned char si, sj; };
+    // k_part_scatter keeps the three table words of the next tile in flight (hhx_partition.h: PREFETCH); the membership gathers are
+    // issued when the tile is taken up
+    static constexpr int PREFETCH = 1;
+    static __device__ __forceinline__ void pin(Raw &r) { asm volatile("" : "+v"(r.ord)); asm volatile("" : "+v"(r.ky)); asm volatile("" : "+v"(r.c)); }
     __device__ __forceinline__ u32 frag_i(const Raw &r) const { return min((u32)(r.ky >> ID_BITS), (u32)n_frag - 1u); }     // (clamped: the gathers are
     __device__ __forceinline__ u32 frag_j(const Raw &r) const { return min((u32)(r.ky & ID_MASK), (u32)n_frag - 1u); }      //  unconditional)
     __device__ __forceinline__ void load1(i64 idx, Raw &r) const {

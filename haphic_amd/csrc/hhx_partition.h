@@ -3,11 +3,17 @@
 // matrix build (hhx_matrix.hip: bucket = matrix row).
 //
 // Per level: a COUNT pass (LDS histogram per 4096-record tile -> global histogram), an exclusive scan, and
-// a SCATTER pass.  The scatter stages the tile in LDS grouped by bucket (LDS histogram rank + tile-local
+// a SCATTER pass.  The scatter stages a tile in LDS grouped by bucket (LDS histogram rank + tile-local
 // exclusive scan) and then writes it out linearly, so every (tile, bucket) group is one contiguous,
 // coalesced run of records; one global atomicAdd per (tile, bucket) reserves the run.  Scattering single
 // 8/4-byte stores instead (first version) measured 4-5x write amplification in the HBM counters
 // (profiles/r01_pmc_c3.txt).  Nothing here is stable or needs to be: records carry what they need.
+//
+// The scatter's tile loop is a pipeline (k_part_scatter has the phases): the loads of a workgroup's NEXT tile and the
+// reservation atomics of the current one are in flight while the current tile is scanned and staged, four LDS barriers
+// a tile; and a source whose whole next tile fits the registers runs 1024 threads on a tile twice as long (8192 records
+// of 12 B), because the length of the runs a tile writes — tile / buckets of the level — is what bounds these passes
+// once the loads are hidden.  The count pass keeps its own 512-thread tiles: the two need not agree.
 #pragma once
 #include "hhx_common.h"
 
@@ -17,8 +23,9 @@ constexpr int PT = 512, P_MAX_BINS = 512;
 struct NoPayload {};       // w1_t of a source whose records are the bare 64-bit word
 template <class W1> struct PartW1 { static constexpr bool HAS = true; static constexpr size_t BYTES = sizeof(W1); };
 template <> struct PartW1<NoPayload> { static constexpr bool HAS = false; static constexpr size_t BYTES = 0; };
-// records per thread and tile: 8 x 512 = 4096 records of 12 B, 7 x 512 of 16 B, 14 x 512 of 8 B — all stage in < 80 KB
-// of LDS (two workgroups per CU).  The longer the tile, the longer the contiguous run a (tile, bucket) pair writes.
+// records per thread and tile: 8 records of 12 B, 7 of 16 B, 14 of 8 B.  With 512 threads a tile stages in < 80 KB of LDS (two
+// workgroups per CU), with the 1024 of part_scatter_threads() in < 152 KB (one: the same sixteen waves).  The longer the tile, the
+// longer the contiguous run a (tile, bucket) pair writes.
 template <class W1> struct PartTile { static constexpr int ITEMS = !PartW1<W1>::HAS ? 14 : (sizeof(W1) == 4 ? 8 : 7), TILE = PT * ITEMS; };
 
 struct PartLevel {
@@ -39,10 +46,14 @@ struct SrcRecs {
     typedef W1 w1_t;
     static constexpr bool MARK = false;
     static constexpr bool BATCHED = true;
-    static constexpr int CHUNK = 16, CHUNK_SCATTER = 16;
+    static constexpr int CHUNK = 16, CHUNK_SCATTER = 16, PREFETCH = 2;
     const u64 *w0;
     const W1 *w1;
     struct Raw { u64 a; W1 b; };
+    static __device__ __forceinline__ void pin(Raw &r) {
+        asm volatile("" : "+v"(r.a));
+        if constexpr (PartW1<W1>::HAS) asm volatile("" : "+v"(r.b));
+    }
     __device__ __forceinline__ void load1(i64 idx, Raw &r) const {
         r.a = w0[idx];
         if constexpr (PartW1<W1>::HAS) r.b = w1[idx];
@@ -148,46 +159,116 @@ __global__ __launch_bounds__(PT) void k_part_count(Src src, Dig dig, i64 n, Part
             if (hist[t]) atomicAdd(&ghist[((u64)cur << L.lds_bits) | (u64)t], (unsigned long long)hist[t]);
 }
 
-template <class W1>
+template <class W1, int T>
 constexpr size_t part_scatter_lds() {
-    return (size_t)PartTile<W1>::TILE * (8 + PartW1<W1>::BYTES + 2) + (size_t)P_MAX_BINS * (4 + 4 + 8) + 16;
+    return (size_t)PartTile<W1>::ITEMS * T * (8 + PartW1<W1>::BYTES + 2) + (size_t)P_MAX_BINS * (4 + 4 + 8) + 16;
 }
 
-template <class Src, class Dig>
-__global__ __launch_bounds__(PT) void k_part_scatter(Src src, Dig dig, i64 n, PartLevel L, unsigned long long *__restrict__ cursor,
+// what k_part_scatter keeps in flight for the NEXT tile of a workgroup while it scans, reserves and stages the current one (a BATCHED
+// source says so in PREFETCH): 0 nothing, 1 the load1 words, 2 the load1 words and the load2 gathers; Src::pin(raw) names the
+// registers of that prefetch, so that the wait for them can be put where it belongs (see the kernel)
+template <class Src, bool B = Src::BATCHED> struct PartRaw { struct type {}; static constexpr int PF = 0; };
+template <class Src> struct PartRaw<Src, true> { typedef typename Src::Raw type; static constexpr int PF = Src::PREFETCH; };
+
+// The tile loop, four LDS barriers a tile:
+//   top   decode the tile's records from the registers the previous iteration (or the prologue) loaded; rank them with one LDS
+//         atomic each (the histogram is clear: see below); THEN issue the loads of tile + gridDim.x
+//   (1)   scan: thread t reads bin t — and clears it for the next tile, nobody else reads it — wave scan
+//   (2)   tile-local bases to LDS; the global reservation atomic of bin t is ISSUED, its result stays in a register
+//   (3)   stage the tile in LDS grouped by bucket (needs the local bases only); behind the staging the reserved base goes to LDS —
+//         the one place that waits for global memory: the reservation's round trip and the next tile's loads (issued before it,
+//         vmcnt retires in order) have had the scan, the bases and the staging to come back.  The prefetched registers are pinned
+//         here, BEFORE the write-out's stores are issued: the waitcnt pass is static and the write-out has a data-dependent trip
+//         count, so a wait placed behind it (where the next iteration consumes the registers) is vmcnt(0) and drains the stores too
+//   (4)   write-out: linear sweep over the staged tile, lanes write consecutive addresses inside a run.  No barrier ends the tile:
+//         what the write-out reads (staged records, bins, both bases, the count) is next written behind barrier (2) of the next
+//         tile, and no wave passes (1) before every wave has left its write-out.
+// The group of a later level's tile (tile_group) comes from a load of the tile's first record that every thread issues with the
+// prefetch (one line per wave) instead of a read by thread 0, an LDS word and a barrier.  A prefetch past the last tile reads
+// record n - 1 (the clamp the tile's own tail uses) and is never decoded.
+template <class Src, class Dig, int T>
+__global__ __launch_bounds__(T) void k_part_scatter(Src src, Dig dig, i64 n, PartLevel L, unsigned long long *__restrict__ cursor,
                                                      u64 *__restrict__ out_w0, typename Src::w1_t *__restrict__ out_w1) {
     typedef typename Src::w1_t W1;
-    constexpr int P_ITEMS = PartTile<W1>::ITEMS, P_TILE = PartTile<W1>::TILE;
+    typedef typename PartRaw<Src>::type RawT;
+    constexpr int P_ITEMS = PartTile<W1>::ITEMS, P_TILE = PartTile<W1>::ITEMS * T, PF = PartRaw<Src>::PF;
+    static_assert(P_TILE <= 0x10000 && P_MAX_BINS <= 0x8000, "bin and rank of a record share one register");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64 *s_w0 = (u64 *)smem;                                     // [P_TILE] tile grouped by bucket
     unsigned long long *gbase = (unsigned long long *)(s_w0 + P_TILE);   // [P_MAX_BINS] reserved global run of every bucket
     W1 *s_w1 = (W1 *)(gbase + P_MAX_BINS);                       // [P_TILE] (nothing for payload-free records)
     u32 *hist = (u32 *)((unsigned char *)s_w1 + (size_t)P_TILE * PartW1<W1>::BYTES);   // [P_MAX_BINS]
     u32 *lbase = hist + P_MAX_BINS;                              // [P_MAX_BINS] tile-local exclusive prefix
-    u32 *s_misc = lbase + P_MAX_BINS;                            // [4]: group, wave sums scratch
+    u32 *s_misc = lbase + P_MAX_BINS;                            // [4]: [1] records staged by the tile
     unsigned short *s_bin = (unsigned short *)(s_misc + 4);      // [P_TILE]
     const int tid = threadIdx.x, lane = lane_id(), wave = tid / HHX_WAVE, nb = 1 << L.lds_bits;
-    __shared__ u32 wsum[PT / HHX_WAVE];
+    __shared__ u32 wsum[T / HHX_WAVE];
     const i64 n_tiles = (n + P_TILE - 1) / P_TILE;
+    if ((i64)blockIdx.x >= n_tiles) return;                      // (also n == 0: the clamp below needs a record)
+    const bool later = L.shift + L.lds_bits < L.total_bits;      // a level whose tiles have a group (tile_group)
+    for (int t = tid; t < nb; t += T) hist[t] = 0;
+    lds_barrier();
+    [[maybe_unused]] auto prefetch = [&](const i64 pbase, RawT (&raw)[P_ITEMS], u64 &gw) {
+        if constexpr (PF > 0) {
+#pragma unroll
+            for (int k = 0; k < P_ITEMS; ++k) {
+                const i64 idx = pbase + (i64)k * T + tid;
+                src.load1(idx < n ? idx : n - 1, raw[k]);
+            }
+            if constexpr (PF > 1) {
+#pragma unroll
+                for (int k = 0; k < P_ITEMS; ++k) src.load2(raw[k]);
+            }
+            if (later) { W1 gw1; (void)src.get(pbase < n ? pbase : n - 1, gw, gw1); }   // later levels read compact records: never invalid
+        }
+    };
+    [[maybe_unused]] auto pin = [&](RawT (&raw)[P_ITEMS], u64 &gw) {
+        if constexpr (PF > 0) {
+#pragma unroll
+            for (int k = 0; k < P_ITEMS; ++k) Src::pin(raw[k]);
+            asm volatile("" : "+v"(gw));
+        }
+    };
+    // the loop is entered with the first tile's registers DEFINED, not pending (k_aggregate has the reason)
+    [[maybe_unused]] RawT raw_c[P_ITEMS];
+    [[maybe_unused]] u64 gw_c = 0;
+    prefetch((i64)blockIdx.x * P_TILE, raw_c, gw_c);
+    pin(raw_c, gw_c);
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const i64 base = tile * P_TILE;
-        for (int t = tid; t < nb; t += PT) hist[t] = 0;
-        if (tid == 0) s_misc[0] = tile_group(src, dig, base, n, L);
-        lds_barrier();
-        const u32 tg = s_misc[0];
+        u32 tg = 0;
+        if constexpr (PF > 0) { if (later) tg = (dig(gw_c) >> L.shift) >> L.lds_bits; }
+        else tg = tile_group(src, dig, base, n, L);
         u64 w0[P_ITEMS];
         W1 w1[P_ITEMS];
-        u32 loc[P_ITEMS], rank[P_ITEMS];
+        u32 lr[P_ITEMS];                                             // bin << 16 | rank in the bin; all ones: not staged
         bool have[P_ITEMS];
-        if constexpr (Src::BATCHED) {                                // every load of a chunk in flight before the first is consumed (see SrcRecs)
-            constexpr int CH = Src::CHUNK_SCATTER < P_ITEMS ? Src::CHUNK_SCATTER : P_ITEMS;
+        if constexpr (PF > 0) {
+            constexpr int CH = PF > 1 ? P_ITEMS : (Src::CHUNK_SCATTER < P_ITEMS ? Src::CHUNK_SCATTER : P_ITEMS);
 #pragma unroll
             for (int h = 0; h < P_ITEMS; h += CH) {
-                typename Src::Raw raw[CH];
+                if constexpr (PF == 1) {
+#pragma unroll
+                    for (int k = 0; k < CH; ++k)
+                        if (h + k < P_ITEMS) src.load2(raw_c[h + k]);
+                }
 #pragma unroll
                 for (int k = 0; k < CH; ++k)
                     if (h + k < P_ITEMS) {
-                        const i64 idx = base + (i64)(h + k) * PT + tid;
+                        const i64 idx = base + (i64)(h + k) * T + tid;
+                        const bool ok = src.decode(idx, raw_c[h + k], w0[h + k], w1[h + k]);
+                        have[h + k] = idx < n && ok;
+                    }
+            }
+        } else if constexpr (Src::BATCHED) {                         // every load of a chunk in flight before the first is consumed (see SrcRecs)
+            constexpr int CH = Src::CHUNK_SCATTER < P_ITEMS ? Src::CHUNK_SCATTER : P_ITEMS;
+#pragma unroll
+            for (int h = 0; h < P_ITEMS; h += CH) {
+                RawT raw[CH];
+#pragma unroll
+                for (int k = 0; k < CH; ++k)
+                    if (h + k < P_ITEMS) {
+                        const i64 idx = base + (i64)(h + k) * T + tid;
                         src.load1(idx < n ? idx : n - 1, raw[k]);
                     }
 #pragma unroll
@@ -196,7 +277,7 @@ __global__ __launch_bounds__(PT) void k_part_scatter(Src src, Dig dig, i64 n, Pa
 #pragma unroll
                 for (int k = 0; k < CH; ++k)
                     if (h + k < P_ITEMS) {
-                        const i64 idx = base + (i64)(h + k) * PT + tid;
+                        const i64 idx = base + (i64)(h + k) * T + tid;
                         const bool ok = src.decode(idx, raw[k], w0[h + k], w1[h + k]);
                         have[h + k] = idx < n && ok;
                     }
@@ -204,14 +285,14 @@ __global__ __launch_bounds__(PT) void k_part_scatter(Src src, Dig dig, i64 n, Pa
         }
 #pragma unroll
         for (int k = 0; k < P_ITEMS; ++k) {
-            const i64 idx = base + (i64)k * PT + tid;
-            loc[k] = 0xffffffffu;
+            const i64 idx = base + (i64)k * T + tid;
+            lr[k] = 0xffffffffu;
             if constexpr (!Src::BATCHED) have[k] = idx < n && src.get(idx, w0[k], w1[k]);
             if (have[k]) {
                 const u32 d = dig(w0[k]) >> L.shift;
                 if ((d >> L.lds_bits) == tg) {
-                    loc[k] = d & (u32)(nb - 1);
-                    rank[k] = atomicAdd(&hist[loc[k]], 1u);
+                    const u32 loc = d & (u32)(nb - 1);
+                    lr[k] = (loc << 16) | atomicAdd(&hist[loc], 1u);
                 } else {                                         // straddling record: reserve its slot directly
                     const unsigned long long pos = atomicAdd(&cursor[d], 1ull);
                     out_w0[pos] = w0[k];
@@ -219,46 +300,64 @@ __global__ __launch_bounds__(PT) void k_part_scatter(Src src, Dig dig, i64 n, Pa
                 }
             }
         }
-        lds_barrier();
-        // tile-local exclusive scan of the histogram (one bin per thread, nb <= PT) + global reservation
-        {
-            const u32 c = tid < nb ? hist[tid] : 0;
-            u32 incl = c;
+        [[maybe_unused]] RawT raw_n[P_ITEMS];
+        [[maybe_unused]] u64 gw_n = 0;
+        prefetch(base + (i64)gridDim.x * P_TILE, raw_n, gw_n);
+        lds_barrier();                                               // (1)
+        // tile-local exclusive scan of the histogram (one bin per thread, nb <= T)
+        const u32 c = tid < nb ? hist[tid] : 0;
+        if (tid < nb) hist[tid] = 0;
+        u32 incl = c;
 #pragma unroll
-            for (int o = 1; o < HHX_WAVE; o <<= 1) {
-                const u32 v = __shfl_up(incl, o, HHX_WAVE);
-                if (lane >= o) incl += v;
-            }
-            if (lane == HHX_WAVE - 1) wsum[wave] = incl;
-            lds_barrier();
-            u32 woff = 0;
-            for (int w = 0; w < wave; ++w) woff += wsum[w];
-            if (tid < nb) {
-                lbase[tid] = woff + incl - c;
-                if (c) gbase[tid] = atomicAdd(&cursor[((u64)tg << L.lds_bits) | (u64)tid], (unsigned long long)c);
-            }
-            if (tid == PT - 1) s_misc[1] = woff + incl;          // records staged by this tile
+        for (int o = 1; o < HHX_WAVE; o <<= 1) {
+            const u32 v = __shfl_up(incl, o, HHX_WAVE);
+            if (lane >= o) incl += v;
         }
-        lds_barrier();
+        if (lane == HHX_WAVE - 1) wsum[wave] = incl;
+        lds_barrier();                                               // (2)
+        u32 woff = 0;
+        for (int w = 0; w < wave; ++w) woff += wsum[w];
+        unsigned long long gb = 0;
+        if (tid < nb) {
+            lbase[tid] = woff + incl - c;
+            if (c) gb = atomicAdd(&cursor[((u64)tg << L.lds_bits) | (u64)tid], (unsigned long long)c);
+        }
+        if (tid == T - 1) s_misc[1] = woff + incl;              // records staged by this tile
+        lds_barrier();                                               // (3)
 #pragma unroll
         for (int k = 0; k < P_ITEMS; ++k)
-            if (loc[k] != 0xffffffffu) {
-                const u32 s = lbase[loc[k]] + rank[k];
+            if (lr[k] != 0xffffffffu) {
+                const u32 loc = lr[k] >> 16;
+                const u32 s = lbase[loc] + (lr[k] & 0xffffu);
                 s_w0[s] = w0[k];
                 if constexpr (PartW1<W1>::HAS) s_w1[s] = w1[k];
-                s_bin[s] = (unsigned short)loc[k];
+                s_bin[s] = (unsigned short)loc;
             }
-        lds_barrier();
+        if (c) gbase[tid] = gb;                                      // (c != 0 implies tid < nb)
+        pin(raw_n, gw_n);
+        lds_barrier();                                               // (4)
         const u32 staged = s_misc[1];
-        for (u32 s = tid; s < staged; s += PT) {                 // linear sweep: lanes write consecutive addresses inside a run
+        for (u32 s = tid; s < staged; s += T) {                 // linear sweep: lanes write consecutive addresses inside a run
             const u32 b = s_bin[s];
             const unsigned long long pos = gbase[b] + (s - lbase[b]);
             out_w0[pos] = s_w0[s];
             if constexpr (PartW1<W1>::HAS) out_w1[pos] = s_w1[s];
         }
-        lds_barrier();
+        if constexpr (PF > 0) {
+#pragma unroll
+            for (int k = 0; k < P_ITEMS; ++k) raw_c[k] = raw_n[k];
+            gw_c = gw_n;
+        }
     }
 }
+
+// threads of a scatter workgroup: a source whose whole next tile is prefetched runs ONE workgroup of 1024 threads a CU instead of two of
+// 512 — the same sixteen waves, but a tile twice as long, so every (tile, bucket) run it writes is twice as long
+template <class Src> constexpr int part_scatter_threads() { return PartRaw<Src>::PF == 2 ? 2 * PT : PT; }
+
+// workgroups of the count and scatter passes at most (HHX_PART_GRID, read at every launch: a test gives one workgroup several tiles
+// of a few tens of thousands of records)
+inline i64 part_grid_cap() { const char *e = getenv("HHX_PART_GRID"); return e && atoll(e) > 0 ? atoll(e) : 256 * 4; }
 
 void u64_copy_async(const unsigned long long *src, unsigned long long *dst, i64 n);   // hhx_runtime.hip
 
@@ -296,12 +395,13 @@ int partition_records(const Src &src, const Dig &dig, i64 n_items, int total_bit
                       Partitioned<typename Src::w1_t> *out, const char *timer_prefix, const Src *count_src = nullptr,
                       const unsigned long long *hist0 = nullptr) {
     typedef typename Src::w1_t W1;
+    constexpr int T1 = part_scatter_threads<Src>(), TN = part_scatter_threads<SrcRecs<W1>>();      // first level, later levels
     static int attr_dev = -1;           // the attribute is per device: keyed on the current ordinal (one static per instantiation)
     int dev = 0;
     HHX_HIP(hipGetDevice(&dev));
     if (attr_dev != dev) {
-        HHX_HIP(hipFuncSetAttribute((const void *)k_part_scatter<Src, Dig>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_scatter_lds<W1>()));
-        HHX_HIP(hipFuncSetAttribute((const void *)k_part_scatter<SrcRecs<W1>, Dig>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_scatter_lds<W1>()));
+        HHX_HIP(hipFuncSetAttribute((const void *)k_part_scatter<Src, Dig, T1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_scatter_lds<W1, T1>()));
+        HHX_HIP(hipFuncSetAttribute((const void *)k_part_scatter<SrcRecs<W1>, Dig, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_scatter_lds<W1, TN>()));
         attr_dev = dev;
     }
     if (max_bits_per_level > 9) max_bits_per_level = 9;          // P_MAX_BINS
@@ -326,7 +426,7 @@ int partition_records(const Src &src, const Dig &dig, i64 n_items, int total_bit
         if (hist.alloc((size_t)nbk + 1) || cursor.alloc((size_t)nbk + 1) || nbase.alloc((size_t)nbk + 2)) return 1;
         HHX_HIP(hipMemsetAsync(hist.p, 0, sizeof(unsigned long long) * ((size_t)nbk + 1), g_stream));
         const i64 tile = l == 0 ? PartTile<W1>::TILE : PartTile<W1>::TILE;
-        const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>((n_cur + tile - 1) / tile, 256 * 4));
+        const unsigned grid = (unsigned)std::max<i64>(1, std::min<i64>((n_cur + tile - 1) / tile, part_grid_cap()));
         const SrcRecs<W1> rs{cur_w0.p, cur_w1.p};
         snprintf(tname, sizeof tname, "%s_count%d", timer_prefix, l + 1);
         { KTimer kt(tname);
@@ -346,8 +446,10 @@ int partition_records(const Src &src, const Dig &dig, i64 n_items, int total_bit
         u64_copy_async((const unsigned long long *)nbase.p, cursor.p, (i64)nbk + 1);
         snprintf(tname, sizeof tname, "%s_scatter%d", timer_prefix, l + 1);
         { KTimer kt(tname);
-        if (l == 0) k_part_scatter<Src, Dig><<<grid, PT, part_scatter_lds<W1>(), g_stream>>>(src, dig, n_cur, L, cursor.p, nxt_w0.p, nxt_w1.p);
-        else k_part_scatter<SrcRecs<W1>, Dig><<<grid, PT, part_scatter_lds<W1>(), g_stream>>>(rs, dig, n_cur, L, cursor.p, nxt_w0.p, nxt_w1.p); }
+        const i64 stile = (i64)PartTile<W1>::ITEMS * (l == 0 ? T1 : TN);
+        const unsigned sgrid = (unsigned)std::max<i64>(1, std::min<i64>((n_cur + stile - 1) / stile, part_grid_cap()));
+        if (l == 0) k_part_scatter<Src, Dig, T1><<<sgrid, T1, part_scatter_lds<W1, T1>(), g_stream>>>(src, dig, n_cur, L, cursor.p, nxt_w0.p, nxt_w1.p);
+        else k_part_scatter<SrcRecs<W1>, Dig, TN><<<sgrid, TN, part_scatter_lds<W1, TN>(), g_stream>>>(rs, dig, n_cur, L, cursor.p, nxt_w0.p, nxt_w1.p); }
         HHX_LAUNCH_CHECK();
         HHX_HIP(hipStreamSynchronize(g_stream));                 // hist / cursor die here; the previous level's records too
         cur_w0 = std::move(nxt_w0);
