@@ -311,33 +311,62 @@ __device__ __forceinline__ u32 xcc_id() {            // the XCD this wave runs o
     return 0;
 #endif
 }
+// Membership in frag_set is ONE BIT per fragment (bit f & 31 of word f >> 5, zero past n_frag; packed on the host from the caller's
+// bytes at every call).  IN_LDS: every workgroup copies the words to LDS in front of its tile loop (hhx_partition.h: LDS_TABLE) and a
+// membership test is two LDS reads in decode — nothing of it passes the vector-memory pipeline, where the byte gathers of the first
+// version were two divergent lane addresses per entry and pass.  !IN_LDS (more than HHX_D2M_LDS_FRAGS fragments): the words stay
+// in global memory and are gathered in load2, as the bytes were.
+constexpr i32 D2M_LDS_MAX_FRAGS = 1 << 19;           // 64 KB of bits: beside the scatter's 78 KB of staging, under the 160 KB of a CU
+struct PackedRawBase { u64 ord, ky; u32 c; };
+struct PackedRawWords : PackedRawBase { u32 wi, wj; };
+template <bool IN_LDS>
 struct SrcDirectedPacked {
     typedef NoPayload w1_t;
     static constexpr bool MARK = true;      // k_part_count calls mark_load / mark_apply once per record (level 1 only)
     static constexpr bool BATCHED = true;
+    static constexpr bool LDS_TABLE = IN_LDS;
+    static constexpr size_t LDS_TABLE_MAX = (size_t)D2M_LDS_MAX_FRAGS / 8;
     // records whose raw words are in flight together: half a tile in the count pass; fewer in the scatter pass, which keeps the whole
     // tile in registers besides (more would cost either kernel its second workgroup per CU)
     static constexpr int CHUNK = 7, CHUNK_SCATTER = 4;
     const u64 *key, *ord_flank;
     const u32 *fl;
-    const unsigned char *in_set;
+    const u32 *in_bits;                     // [(n_frag + 31) / 32]; in the copy lds_table() returns: the workgroup's words in LDS
     unsigned long long *first_pos;          // [N_XCC][n_frag]; set in the object the level-1 count pass reads through, null otherwise
     unsigned int *too_big;
     i32 n_frag;
-    // the loads of a record without a branch between them (hhx_partition.h: BATCHED): the three words of the table row, then the
-    // two membership bytes its key points at — every load of a chunk of records is in flight before the first is consumed
-    struct Raw { u64 ord, ky; u32 c; unsigned char si, sj; };
-    // k_part_scatter keeps the three table words of the next tile in flight (hhx_partition.h: PREFETCH); the membership gathers are
-    // issued when the tile is taken up
+    // the loads of a record without a branch between them (hhx_partition.h: BATCHED): the three words of the table row, then
+    // (!IN_LDS) the two membership words its key points at — every load of a chunk of records is in flight before the first is consumed
+    typedef typename std::conditional<IN_LDS, PackedRawBase, PackedRawWords>::type Raw;
+    // k_part_scatter keeps the three table words of the next tile in flight (hhx_partition.h: PREFETCH); the membership gathers
+    // (!IN_LDS) are issued when the tile is taken up
     static constexpr int PREFETCH = 1;
     static __device__ __forceinline__ void pin(Raw &r) { asm volatile("" : "+v"(r.ord)); asm volatile("" : "+v"(r.ky)); asm volatile("" : "+v"(r.c)); }
-    __device__ __forceinline__ u32 frag_i(const Raw &r) const { return min((u32)(r.ky >> ID_BITS), (u32)n_frag - 1u); }     // (clamped: the gathers are
+    __device__ __forceinline__ u32 frag_i(const Raw &r) const { return min((u32)(r.ky >> ID_BITS), (u32)n_frag - 1u); }     // (clamped: the reads are
     __device__ __forceinline__ u32 frag_j(const Raw &r) const { return min((u32)(r.ky & ID_MASK), (u32)n_frag - 1u); }      //  unconditional)
+    size_t lds_table_bytes() const { return ((size_t)n_frag + 31) / 32 * sizeof(u32); }
+    __device__ __forceinline__ SrcDirectedPacked lds_table(void *at) const {
+        u32 *t = (u32 *)at;
+        const u32 words = ((u32)n_frag + 31u) >> 5;
+        for (u32 w = threadIdx.x; w < words; w += blockDim.x) t[w] = in_bits[w];
+        SrcDirectedPacked s = *this;
+        s.in_bits = t;
+        return s;
+    }
     __device__ __forceinline__ void load1(i64 idx, Raw &r) const {
         const i64 k = idx >> 1;
         r.ord = ord_flank[k]; r.ky = key[k]; r.c = fl[k];
     }
-    __device__ __forceinline__ void load2(Raw &r) const { r.si = in_set[frag_i(r)]; r.sj = in_set[frag_j(r)]; }
+    __device__ __forceinline__ void load2(Raw &r) const {
+        if constexpr (!IN_LDS) { r.wi = in_bits[frag_i(r) >> 5]; r.wj = in_bits[frag_j(r) >> 5]; }
+    }
+    __device__ __forceinline__ bool member(const Raw &r) const {                   // both ends of the key in frag_set
+        const u32 fi = frag_i(r), fj = frag_j(r);
+        u32 wi, wj;
+        if constexpr (IN_LDS) { wi = in_bits[fi >> 5]; wj = in_bits[fj >> 5]; }
+        else { wi = r.wi; wj = r.wj; }
+        return ((wi >> (fi & 31u)) & (wj >> (fj & 31u)) & 1u) != 0;
+    }
     // extra: the entry's position in the insertion order, 2 * ordinal + side (all ones: its count does not fit PK_CNT_BITS)
     __device__ __forceinline__ bool decode_marked(i64 idx, const Raw &r, u64 &w0, u64 &extra) const {
         const u32 i = (u32)(r.ky >> ID_BITS), j = (u32)(r.ky & ID_MASK);
@@ -345,7 +374,7 @@ struct SrcDirectedPacked {
         const u32 a = side ? j : i, b = side ? i : j;
         w0 = ((u64)a << (PK_ID_BITS + PK_CNT_BITS)) | ((u64)b << PK_CNT_BITS) | (u64)(r.c & PK_CNT_MASK);
         extra = r.c > PK_CNT_MASK ? ~0ull : 2 * r.ord + side;
-        return r.ord != NO_ORD && r.si && r.sj;
+        return r.ord != NO_ORD && member(r);
     }
     __device__ __forceinline__ bool decode(i64 idx, const Raw &r, u64 &w0, NoPayload &) const {
         u64 extra;
@@ -551,14 +580,52 @@ __global__ __launch_bounds__(256) void k_rest_rows(i32 r0, i32 shape, const i32 
     for (i32 r = r0 + blockIdx.x * blockDim.x + threadIdx.x; r < shape; r += gridDim.x * blockDim.x) { oj[indptr[r]] = r; ox[indptr[r]] = 1.0f; }
 }
 
+// frag_set as one bit per fragment (SrcDirectedPacked), eight of the caller's bytes at a step; returns the number of members
+i64 pack_membership(const uint8_t *in_set_host, i32 n_frag, u32 *bits) {
+    const i32 n_words = (n_frag + 31) / 32;
+    for (i32 w = 0; w < n_words; ++w) bits[w] = 0;
+    i64 members = 0;
+    i32 f = 0;
+    for (; f + 8 <= n_frag; f += 8) {
+        u64 x;
+        memcpy(&x, in_set_host + f, 8);
+        // bit 7 of every non-zero byte, then those eight bits next to each other (byte k -> bit k: a little-endian host)
+        const u64 y = (((x & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full) | x) & 0x8080808080808080ull;
+        const u32 m = (u32)(((y >> 7) * 0x0102040810204080ull) >> 56);
+        bits[f >> 5] |= m << (f & 31);
+        members += __builtin_popcount(m);
+    }
+    for (; f < n_frag; ++f)
+        if (in_set_host[f]) { bits[f >> 5] |= 1u << (f & 31); ++members; }
+    return members;
+}
+// largest n_frag whose bitmap the row partition keeps in LDS (HHX_D2M_LDS_FRAGS, read at every launch; 0: never, the words are
+// gathered from global memory); at most D2M_LDS_MAX_FRAGS
+i32 d2m_lds_frags() {
+    const char *e = getenv("HHX_D2M_LDS_FRAGS");
+    if (!e || !*e) return D2M_LDS_MAX_FRAGS;
+    const long long v = atoll(e);
+    return v <= 0 ? 0 : (i32)std::min<long long>(v, D2M_LDS_MAX_FRAGS);
+}
+
 // PACKED: 8-byte entries (see SrcDirectedPacked); returns -2 when a count does not fit 24 bits (the caller takes the 16-byte path)
 template <bool PACKED>
 int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const uint8_t *in_set_host, i32 n_rest, int add_self_loops,
                             i32 *frag_index_host, i32 *n_linked_out, hhx_csr **out) {
     typedef typename std::conditional<PACKED, NoPayload, u64>::type W1;
-    DevBuf<unsigned char> in_set;
-    if (in_set.alloc((size_t)n_frag)) return 1;
-    HHX_HIP(hipMemcpyAsync(in_set.p, in_set_host, (size_t)n_frag, hipMemcpyHostToDevice, g_stream));
+    DevBuf<unsigned char> in_set;                                // the 16-byte path reads the caller's bytes,
+    DevBuf<u32> in_bits;                                         // the packed path one bit per fragment
+    std::vector<u32> bits_host;
+    i64 members = 0;
+    if constexpr (PACKED) {
+        bits_host.resize(((size_t)n_frag + 31) / 32);
+        members = pack_membership(in_set_host, n_frag, bits_host.data());
+        if (in_bits.alloc(bits_host.size())) return 1;
+        HHX_HIP(hipMemcpyAsync(in_bits.p, bits_host.data(), sizeof(u32) * bits_host.size(), hipMemcpyHostToDevice, g_stream));
+    } else {
+        if (in_set.alloc((size_t)n_frag)) return 1;
+        HHX_HIP(hipMemcpyAsync(in_set.p, in_set_host, (size_t)n_frag, hipMemcpyHostToDevice, g_stream));
+    }
     int row_bits = 0;
     while (((i64)1 << row_bits) < n_frag) ++row_bits;
     DevBuf<unsigned long long> first_pos;
@@ -572,9 +639,15 @@ int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const
         DevBuf<unsigned long long> per_xcc;
         if (per_xcc.alloc((size_t)N_XCC * (size_t)n_frag)) return 1;
         HHX_HIP(hipMemsetAsync(per_xcc.p, 0xff, sizeof(unsigned long long) * (size_t)N_XCC * (size_t)n_frag, g_stream));
-        const SrcDirectedPacked src{run->key.p, run->ord_flank.p, run->fl.p, in_set.p, nullptr, nullptr, n_frag};
-        const SrcDirectedPacked marking{run->key.p, run->ord_flank.p, run->fl.p, in_set.p, per_xcc.p, nl.p + 1, n_frag};
-        HHX_TRY(partition_records(src, DigRowPacked(), 2 * run->n, row_bits, level_bits, &part, "d2m", &marking));
+        if (n_frag <= d2m_lds_frags()) {
+            const SrcDirectedPacked<true> src{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, nullptr, nullptr, n_frag};
+            const SrcDirectedPacked<true> marking{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, per_xcc.p, nl.p + 1, n_frag};
+            HHX_TRY(partition_records(src, DigRowPacked(), 2 * run->n, row_bits, level_bits, &part, "d2m", &marking));
+        } else {
+            const SrcDirectedPacked<false> src{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, nullptr, nullptr, n_frag};
+            const SrcDirectedPacked<false> marking{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, per_xcc.p, nl.p + 1, n_frag};
+            HHX_TRY(partition_records(src, DigRowPacked(), 2 * run->n, row_bits, level_bits, &part, "d2m", &marking));
+        }
         k_min_over_xcc<<<grid_for((u64)n_frag), 256, 0, g_stream>>>(n_frag, per_xcc.p, first_pos.p);
         HHX_LAUNCH_CHECK();
         // (whether a count was too big for the packed entry is read back together with n_linked, below)
@@ -595,8 +668,7 @@ int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const
     HHX_TRY(rank_first_positions(n_frag, first_pos.p, 2 * ord_limit + 1, frag_index.p, nl.p)); }
     unsigned int nl_host[2] = {0, 0};                             // n_linked, "a count does not fit the packed entry"
     HHX_HIP(hipMemcpyAsync(nl_host, nl.p, sizeof nl_host, hipMemcpyDeviceToHost, g_stream));
-    i64 members = 0;                                             // counted while the device works
-    if (n_rest < 0)
+    if (!PACKED && n_rest < 0)                                   // counted while the device works (the packed path counted while it packed)
         for (i32 f = 0; f < n_frag; ++f) members += in_set_host[f] != 0;
     HHX_HIP(hipStreamSynchronize(g_stream));
     if (PACKED && nl_host[1]) return -2;

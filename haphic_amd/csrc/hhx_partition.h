@@ -15,6 +15,7 @@
 // of 12 B), because the length of the runs a tile writes — tile / buckets of the level — is what bounds these passes
 // once the loads are hidden.  The count pass keeps its own 512-thread tiles: the two need not agree.
 #pragma once
+#include <type_traits>
 #include "hhx_common.h"
 
 namespace hhx {
@@ -71,6 +72,25 @@ struct SrcRecs {
     }
 };
 
+// A source may keep a small READ-ONLY TABLE IN LDS, one copy per workgroup (hhx_matrix.hip: the membership bitmap of
+// SrcDirectedPacked<true>, so that a membership test is an LDS read instead of a divergent gather).  It says so with
+//     static constexpr bool LDS_TABLE = true;  static constexpr size_t LDS_TABLE_MAX = <bytes at most>;
+//     size_t lds_table_bytes() const;          (host: bytes of this object's table)
+//     Src lds_table(void *at) const;           (device, every thread of the workgroup: copies the table to `at`, 16-byte aligned,
+//                                               and returns a copy of the source that reads it there; the caller runs the barrier)
+// k_part_count and k_part_scatter place the table in dynamic LDS — the scatter behind its staging arrays, which never reach it —
+// fill it once per workgroup in front of the tile loop and read through the returned copy; the host driver adds the bytes to the
+// launch.  A source without the declaration compiles to the code it had before.
+template <class Src, class = void> struct PartLds { static constexpr bool HAS = false; static constexpr size_t MAX = 0; };
+template <class Src> struct PartLds<Src, std::void_t<decltype(Src::LDS_TABLE)>> {
+    static constexpr bool HAS = Src::LDS_TABLE;
+    static constexpr size_t MAX = HAS ? (Src::LDS_TABLE_MAX + 15) / 16 * 16 : 0;
+};
+template <class Src> inline size_t part_lds_table_bytes(const Src &src) {
+    if constexpr (PartLds<Src>::HAS) return (src.lds_table_bytes() + 15) / 16 * 16;
+    else return 0;
+}
+
 template <class Src, class Dig>
 __device__ __forceinline__ u32 tile_group(const Src &src, const Dig &dig, i64 first, i64 n, const PartLevel &L) {
     if (L.shift + L.lds_bits >= L.total_bits) return 0;          // first level: the LDS histogram spans the whole digit
@@ -80,12 +100,18 @@ __device__ __forceinline__ u32 tile_group(const Src &src, const Dig &dig, i64 fi
 }
 
 template <class Src, class Dig>
-__global__ __launch_bounds__(PT) void k_part_count(Src src, Dig dig, i64 n, PartLevel L, unsigned long long *__restrict__ ghist) {
+__global__ __launch_bounds__(PT) void k_part_count(Src src_arg, Dig dig, i64 n, PartLevel L, unsigned long long *__restrict__ ghist) {
     constexpr int P_ITEMS = PartTile<typename Src::w1_t>::ITEMS, P_TILE = PartTile<typename Src::w1_t>::TILE;
     __shared__ u32 hist[P_MAX_BINS];
     __shared__ u32 s_grp;
+    extern __shared__ __attribute__((aligned(16))) unsigned char count_smem[];      // the source's LDS table, if it has one: nothing else
     const int tid = threadIdx.x, nb = 1 << L.lds_bits;
     for (int t = tid; t < nb; t += PT) hist[t] = 0;
+    Src src = src_arg;
+    if constexpr (PartLds<Src>::HAS) {
+        src = src_arg.lds_table(count_smem);
+        lds_barrier();
+    }
     u32 cur = 0xffffffffu;
     const i64 n_tiles = (n + P_TILE - 1) / P_TILE;
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -163,6 +189,9 @@ template <class W1, int T>
 constexpr size_t part_scatter_lds() {
     return (size_t)PartTile<W1>::ITEMS * T * (8 + PartW1<W1>::BYTES + 2) + (size_t)P_MAX_BINS * (4 + 4 + 8) + 16;
 }
+// where a source's LDS table starts in the scatter's dynamic LDS: behind s_bin, the last of the staging arrays
+template <class W1, int T>
+constexpr size_t part_scatter_table_at() { return (part_scatter_lds<W1, T>() + 15) / 16 * 16; }
 
 // what k_part_scatter keeps in flight for the NEXT tile of a workgroup while it scans, reserves and stages the current one (a BATCHED
 // source says so in PREFETCH): 0 nothing, 1 the load1 words, 2 the load1 words and the load2 gathers; Src::pin(raw) names the
@@ -187,7 +216,7 @@ template <class Src> struct PartRaw<Src, true> { typedef typename Src::Raw type;
 // prefetch (one line per wave) instead of a read by thread 0, an LDS word and a barrier.  A prefetch past the last tile reads
 // record n - 1 (the clamp the tile's own tail uses) and is never decoded.
 template <class Src, class Dig, int T>
-__global__ __launch_bounds__(T) void k_part_scatter(Src src, Dig dig, i64 n, PartLevel L, unsigned long long *__restrict__ cursor,
+__global__ __launch_bounds__(T) void k_part_scatter(Src src_arg, Dig dig, i64 n, PartLevel L, unsigned long long *__restrict__ cursor,
                                                      u64 *__restrict__ out_w0, typename Src::w1_t *__restrict__ out_w1) {
     typedef typename Src::w1_t W1;
     typedef typename PartRaw<Src>::type RawT;
@@ -207,6 +236,9 @@ __global__ __launch_bounds__(T) void k_part_scatter(Src src, Dig dig, i64 n, Par
     if ((i64)blockIdx.x >= n_tiles) return;                      // (also n == 0: the clamp below needs a record)
     const bool later = L.shift + L.lds_bits < L.total_bits;      // a level whose tiles have a group (tile_group)
     for (int t = tid; t < nb; t += T) hist[t] = 0;
+    // the source's LDS table lies behind s_bin[P_TILE]: the staging writes s_bin[s] for s < P_TILE only, so it outlives every tile
+    Src src = src_arg;
+    if constexpr (PartLds<Src>::HAS) src = src_arg.lds_table(smem + part_scatter_table_at<W1, T>());
     lds_barrier();
     [[maybe_unused]] auto prefetch = [&](const i64 pbase, RawT (&raw)[P_ITEMS], u64 &gw) {
         if constexpr (PF > 0) {
@@ -400,7 +432,9 @@ int partition_records(const Src &src, const Dig &dig, i64 n_items, int total_bit
     int dev = 0;
     HHX_HIP(hipGetDevice(&dev));
     if (attr_dev != dev) {
-        HHX_HIP(hipFuncSetAttribute((const void *)k_part_scatter<Src, Dig, T1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_scatter_lds<W1, T1>()));
+        HHX_HIP(hipFuncSetAttribute((const void *)k_part_scatter<Src, Dig, T1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(part_scatter_table_at<W1, T1>() + PartLds<Src>::MAX)));
+        if constexpr (PartLds<Src>::HAS)
+            HHX_HIP(hipFuncSetAttribute((const void *)k_part_count<Src, Dig>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PartLds<Src>::MAX));
         HHX_HIP(hipFuncSetAttribute((const void *)k_part_scatter<SrcRecs<W1>, Dig, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)part_scatter_lds<W1, TN>()));
         attr_dev = dev;
     }
@@ -410,6 +444,8 @@ int partition_records(const Src &src, const Dig &dig, i64 n_items, int total_bit
     int used = 0;
     for (int l = 0; l < n_levels; ++l) used += bits[l];
     if (used != total_bits) return fail("partition: %d bits do not fit %d levels", total_bits, n_levels);
+    const size_t table_bytes = part_lds_table_bytes(src);        // the source's LDS table (level 1 reads through the source): 0 without one
+    if (table_bytes > PartLds<Src>::MAX) return fail("partition: an LDS table of %zu bytes exceeds the %zu its source declares", table_bytes, PartLds<Src>::MAX);
     out->n_buckets = 1u << total_bits;
     DevBuf<u64> cur_w0, nxt_w0;
     DevBuf<W1> cur_w1, nxt_w1;
@@ -431,7 +467,7 @@ int partition_records(const Src &src, const Dig &dig, i64 n_items, int total_bit
         snprintf(tname, sizeof tname, "%s_count%d", timer_prefix, l + 1);
         { KTimer kt(tname);
         if (l == 0 && hist0) u64_copy_async(hist0, hist.p, (i64)nbk);
-        else if (l == 0) k_part_count<Src, Dig><<<grid, PT, 0, g_stream>>>(count_src ? *count_src : src, dig, n_cur, L, hist.p);
+        else if (l == 0) k_part_count<Src, Dig><<<grid, PT, table_bytes, g_stream>>>(count_src ? *count_src : src, dig, n_cur, L, hist.p);
         else k_part_count<SrcRecs<W1>, Dig><<<grid, PT, 0, g_stream>>>(rs, dig, n_cur, L, hist.p); }
         HHX_LAUNCH_CHECK();
         i64 n_valid = 0;
@@ -448,7 +484,7 @@ int partition_records(const Src &src, const Dig &dig, i64 n_items, int total_bit
         { KTimer kt(tname);
         const i64 stile = (i64)PartTile<W1>::ITEMS * (l == 0 ? T1 : TN);
         const unsigned sgrid = (unsigned)std::max<i64>(1, std::min<i64>((n_cur + stile - 1) / stile, part_grid_cap()));
-        if (l == 0) k_part_scatter<Src, Dig, T1><<<sgrid, T1, part_scatter_lds<W1, T1>(), g_stream>>>(src, dig, n_cur, L, cursor.p, nxt_w0.p, nxt_w1.p);
+        if (l == 0) k_part_scatter<Src, Dig, T1><<<sgrid, T1, part_scatter_table_at<W1, T1>() + table_bytes, g_stream>>>(src, dig, n_cur, L, cursor.p, nxt_w0.p, nxt_w1.p);
         else k_part_scatter<SrcRecs<W1>, Dig, TN><<<sgrid, TN, part_scatter_lds<W1, TN>(), g_stream>>>(rs, dig, n_cur, L, cursor.p, nxt_w0.p, nxt_w1.p); }
         HHX_LAUNCH_CHECK();
         HHX_HIP(hipStreamSynchronize(g_stream));                 // hist / cursor die here; the previous level's records too
