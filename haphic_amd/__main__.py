@@ -18,6 +18,13 @@ The reference checkout is found through --reference DIR or $HAPHIC_REFERENCE (th
 directory).  Extra flags of the wrapper (removed before the reference parses the command line):
   --device N                 HIP device ordinal (default 0)
   --keep-reference-ingest    leave S5 / a1 (parse_alignments*, pairs_generator*) and the correction passes to the reference
+  --keep-reference-allelic   cluster only: leave --remove_allelic_links N (remove_allelic_HiC_links :474-692) to the reference's per-key loops, which
+                             thaw full_link_dict, flank_link_dict and ctg_coord_dict into Python dicts first.  Without the flag a one-rank job
+                             takes the concordance ratios and the verdict on the device tables (haphic_amd/allelic.py); under --gpus N > 1 or
+                             torchrun the reference's loops run whatever the flag says (the sharded tables are not served).  The device path
+                             also hands a call back to the reference's function when the containers were already thawed, flank_link_dict is
+                             empty, --remove_concentrated_links or ultra-long reads (--ul) are on, the log level is DEBUG (the per-key debug
+                             lines), a contig is shorter than --nwindows bp, or --max_read_pairs exceeds 4096
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
@@ -74,6 +81,7 @@ def main(argv=None):
     ref = _take(argv, '--reference', True) or os.environ.get('HAPHIC_REFERENCE')
     device = int(_take(argv, '--device', True) or 0)
     keep_ingest = bool(_take(argv, '--keep-reference-ingest', False))
+    keep_allelic = bool(_take(argv, '--keep-reference-allelic', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
     scripts = _reference_scripts(ref)
     if stub:
@@ -112,7 +120,7 @@ def main(argv=None):
         S.run(S.parse_arguments(), 'HapHiC_sort.log')               # == HapHiC_sort.main() :962-967
         return 0
     import HapHiC_cluster as H                                      # the unmodified reference module
-    patch.patch_reference(H, ingest=not keep_ingest)
+    patch.patch_reference(H, ingest=not keep_ingest, allelic=not keep_allelic and ctx is None)      # the allelic seam: one-rank jobs only
     sys.argv = ['haphic cluster'] + argv
     return ranks.run_rank(lambda: H.run(H.parse_arguments(), 'HapHiC_cluster.log'))      # == HapHiC_cluster.main() :2962-2967
 

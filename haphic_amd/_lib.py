@@ -143,6 +143,8 @@ SIGNATURES = {
     'hhx_ingest_fetch_frag_pairs': (C.c_int, [C.c_void_p, c_i64p, C.c_void_p, C.c_void_p]),
     'hhx_ingest_fetch_pairs': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_ingest_set_ordinal_base': (C.c_int, [C.c_void_p, C.c_int64]),
+    'hhx_ingest_concordance': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_ingest_drop_links': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64p, c_i64p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_ingest_link_matrix': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, c_i32p, c_vpp]),
     'hhx_ingest_table_device': (C.c_int, [C.c_void_p, C.c_int, c_i64p, c_vpp, c_vpp, c_vpp, c_vpp, c_vpp]),
     'hhx_ingest_push_table': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1279,6 +1281,45 @@ class Ingest:
         n = C.c_int64(0)
         check(load().hhx_ingest_fetch_ht_items(self.h, C.byref(n), None, None, None))
         return n.value
+
+    UNSUPPORTED = 2      # HHX_UNSUPPORTED: "not served here, take the reference's loop" (the handle is untouched)
+
+    def concordance_counts(self, max_read_pairs, nwindows, min_read_pairs=0):
+        """cal_concordance_ratio :419-428 as integers (hhx_ingest_concordance): (m, diag, anti) int32 arrays in full_link_dict order —
+        m = min(count, max_read_pairs), the modal counts of the diagonal / anti-diagonal windows of the key's first m read pairs; the
+        ratio is max(diag / m, anti / m).  Keys with m < min(min_read_pairs, max_read_pairs) get 0 / 0.  None: the library does not
+        serve this call (max_read_pairs beyond its cap, a contig shorter than nwindows)."""
+        if self.n_full is None:
+            self.finalize()
+        m, diag, anti = (np.zeros(self.n_full, np.int32) for _ in range(3))
+        rc = load().hhx_ingest_concordance(self.h, int(max_read_pairs), int(min_read_pairs), int(nwindows), ptr(m), ptr(diag), ptr(anti))
+        if rc == self.UNSUPPORTED:
+            return None
+        check(rc)
+        return m, diag, anti
+
+    def drop_links(self, full_drop, in_set):
+        """update_link_dicts :488-509 for a whole verdict (hhx_ingest_drop_links): full_drop — one flag per full_link_dict key, in_set — one per
+        fragment (filtered_frags).  Returns (n_full, n_flank, flank_dropped, remaining) — the sizes afterwards, which flank keys left (dict order
+        before the call) and which fragments of in_set still have a flank key inside in_set (:680-683; self.first_row orders them as that loop
+        meets them) — or None when the library does not serve the call.  The handle's tables are the smaller dicts from then on."""
+        if self.n_full is None:
+            self.finalize()
+        full_drop = np.ascontiguousarray(full_drop, np.uint8)
+        in_set = np.ascontiguousarray(in_set, np.uint8)
+        if full_drop.shape != (self.n_full,) or in_set.shape != (self.n_frag,):
+            raise ValueError('Ingest.drop_links: one flag per full key ({}) and per fragment ({})'.format(self.n_full, self.n_frag))
+        a, b = C.c_int64(0), C.c_int64(0)
+        gone = np.zeros(self.n_flank, np.uint8)
+        remaining = np.zeros(self.n_frag, np.uint8)
+        first_row = np.full(self.n_frag, -1, np.int64)
+        rc = load().hhx_ingest_drop_links(self.h, ptr(full_drop), ptr(in_set), C.byref(a), C.byref(b), ptr(gone), ptr(remaining), ptr(first_row))
+        if rc == self.UNSUPPORTED:
+            return None
+        check(rc)
+        self.n_full, self.n_flank = a.value, b.value
+        self.first_row = first_row
+        return self.n_full, self.n_flank, gone, remaining
 
     def keep_frag_pairs(self, on=True):
         check(load().hhx_ingest_keep_frag_pairs(self.h, int(on)))

@@ -1447,6 +1447,7 @@ class IngestSession:
         self.dist = ('i', np.int32) if dist_int_type == 'int32' else ('l', np.int64)
         self.pos = ('i', np.int32) if pos_int_type == 'int32' else ('l', np.int64)
         self.weighted = False                   # flank values are float64 weights (normalize_by_nlinks) instead of counts
+        self.bins = False                       # set by ingest_session
         self._host = {}
         self._pairs = None
         self._ht_names = None
@@ -1522,6 +1523,12 @@ class IngestSession:
     def note_thawed(self):
         pass
 
+    def links_dropped(self):
+        """keys left the tables of the handle (allelic.remove_allelic_HiC_links -> hhx_ingest_drop_links): the host copies in dict order are
+        fetched again when someone asks; frag_link_dict (frag_links) is not affected by :488-509 and stays"""
+        self._host = {k: v for k, v in self._host.items() if k == 'frag_links'}
+        self._pairs = None
+
     # ---- device-side steps on the resident flank table
     def weigh_flank(self, mode, per_frag=None, tag=None, param=0.0):
         """hhx_link_weights over the flank table in HBM (a6); the values become float64"""
@@ -1560,7 +1567,9 @@ def ingest_session(alignments, table, fa_dict, args, bins, pos_int_type, dist_in
     ingest; the handle stays alive inside the returned IngestSession."""
     ing = _ingest_handle(alignments, table, int(args.flank * 1000), bins, chunk, want_pairs=True, want_frag_pairs=want_frag_pairs,
                          sweep_follows=not getattr(args, 'skip_clustering', False))
-    return IngestSession(ing, table, fa_dict, args, pos_int_type, dist_int_type)
+    session = IngestSession(ing, table, fa_dict, args, pos_int_type, dist_int_type)
+    session.bins = bool(bins)               # parse_alignments :1658 (some contigs split): flank_link_dict is keyed by fragments, not contigs
+    return session
 
 
 def _s5_containers(session):

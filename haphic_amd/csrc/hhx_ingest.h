@@ -160,6 +160,8 @@ struct hhx_ingest {
     bool keep_pairs = false;
     std::vector<hhx::DevBuf<u64>> side_key, side_xy;     // one pair of arrays per push: key, (xi << 32 | xj)
     i64 n_side = 0;
+    bool links_dropped = false;            // hhx_ingest_drop_links removed keys: the side records still hold their read pairs, so nothing groups them any more
+    std::vector<i32> frag_ctg;             // fragment -> its contig (the map behind ctg_pair_to_frag :1731); empty when ctg_frag0 is not ascending
     bool pairs_dropped = false;            // side_key / side_xy were released after paired_links.clm was written (hhx_ingest_write_clm_async)
     i64 max_ctg_len = 0;                   // longest contig (bounds the CLM distances: hhx_ingest_write_clm)
     hhx::DevBuf<i32> stage[4];             // staging for host-side inputs
@@ -178,6 +180,18 @@ struct hhx_ingest {
 // (POS = i32 or i64 positions; the records hold 32-bit coordinates: a 64-bit stream must stay below 2^32, checked by the caller)
 template <class POS>
 int hhx_side_records_push(hhx_ingest *h, i64 n_pairs, const i32 *id1, const POS *pos1, const i32 *id2, const POS *pos2);
+
+// hhx_pairs.hip: the kept read pairs grouped by contig pair: sorted (key, xy) records (stream order inside a group), the boundaries of
+// the groups, and for the g-th smallest key the position r = srank[g] of that contig pair in full_link_dict (dict insertion order).
+// Everything stays in HBM; hhx_ingest_fetch_pairs, the CLM writer and hhx_ingest_concordance (hhx_allelic.hip) read it.
+namespace hhx {
+struct PairGroups {
+    i64 K = 0, N = 0;
+    DevBuf<u64> skey, sxy, stk, srank;
+    DevBuf<i64> gstart;                    // [K + 1]
+};
+int group_pairs(hhx_ingest *h, PairGroups &G, const char *who);
+}
 
 // hhx_matrix.hip: dict_to_matrix on a run (flank rows, first-seen order taken from ord_flank)
 int hhx_link_matrix_from_run(const hhx::LinkRun *run, i32 n_frag, u64 ord_limit, const uint8_t *in_set_host, i32 n_rest, int add_self_loops,

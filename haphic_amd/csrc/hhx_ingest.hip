@@ -688,6 +688,14 @@ extern "C" int hhx_ingest_create(const hhx_ingest_config *cfg, hhx_ingest **out)
     }
     hhx_ingest *h = new hhx_ingest();
     for (i32 c = 0; c < cfg->n_ctg; ++c) h->max_ctg_len = std::max<i64>(h->max_ctg_len, cfg->ctg_len[c]);
+    // fragment -> contig (hhx_ingest_drop_links): contig c owns the fragments [ctg_frag0[c], ctg_frag0[c + 1])
+    bool ascending = cfg->ctg_frag0[0] == 0;
+    for (i32 c = 1; ascending && c < cfg->n_ctg; ++c) ascending = cfg->ctg_frag0[c] > cfg->ctg_frag0[c - 1];
+    if (ascending) {
+        h->frag_ctg.resize((size_t)cfg->n_frag);
+        for (i32 c = 0; c < cfg->n_ctg; ++c)
+            for (i32 f = cfg->ctg_frag0[c], e = c + 1 < cfg->n_ctg ? cfg->ctg_frag0[c + 1] : cfg->n_frag; f < e; ++f) h->frag_ctg[(size_t)f] = c;
+    }
     int rc = upload(h->ctg_info, ci.data(), ci.size()) || upload(h->frag_info, fi.data(), fi.size());
     if (rc) { delete h; return 1; }
     hipError_t e = hipStreamSynchronize(g_stream);               // the host vectors die at return

@@ -195,15 +195,9 @@ template int hhx_side_records_push<i64>(hhx_ingest *, i64, const i32 *, const i6
 
 int hhx_ingest_ordered_full_device(hhx_ingest *h, const i32 **fi, const i32 **fj);   // hhx_ingest.hip
 
-// The kept read pairs grouped by contig pair: sorted (key, xy) records (stream order inside a group), the boundaries of the groups,
-// and for the g-th smallest key the position r = srank[g] of that contig pair in full_link_dict (dict insertion order).
-struct PairGroups {
-    i64 K = 0, N = 0;
-    DevBuf<u64> skey, sxy, stk, srank;
-    DevBuf<i64> gstart;                    // [K + 1]
-};
-
-static int group_pairs(hhx_ingest *h, PairGroups &G, const char *who) {
+// the kept read pairs grouped by contig pair (PairGroups, hhx_ingest.h)
+int hhx::group_pairs(hhx_ingest *h, PairGroups &G, const char *who) {
+    if (h->links_dropped) return fail("%s: keys left the link tables (hhx_ingest_drop_links): the kept read pairs no longer match them", who);
     if (h->pairs_dropped) return fail("%s: the kept read pairs were released after paired_links.clm was written", who);
     const i32 *fi = nullptr, *fj = nullptr;
     HHX_TRY(hhx_ingest_ordered_full_device(h, &fi, &fj));
@@ -286,6 +280,7 @@ static int ht_first_device(hhx_ingest *h, DevBuf<i64> &d_first, const char *who)
     if (!h || !h->finalized) return fail("ingest handle not finalized");
     if (!h->keep_pairs) return fail("%s: the handle was not created with hhx_ingest_keep_pairs", who);
     if (h->pairs_dropped) return fail("%s: the kept read pairs were released after paired_links.clm was written", who);
+    if (h->links_dropped) return fail("%s: keys left the link tables (hhx_ingest_drop_links): the kept read pairs no longer match them", who);
     const i32 *fi = nullptr, *fj = nullptr;
     HHX_TRY(hhx_ingest_ordered_full_device(h, &fi, &fj));
     const i64 K = h->n_full, N = h->n_side;

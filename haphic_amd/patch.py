@@ -6,7 +6,7 @@
 
 Nothing under /root/reference is edited; the reference resolves these names at call time through its
 module globals, so `setattr` on the module is all that is needed."""
-from . import cluster, correct
+from . import allelic, cluster, correct
 
 # seam -> (reference line, replacement)
 SEAMS = {
@@ -57,6 +57,12 @@ CORRECTION_SEAMS = {
     'bam_generator_for_correction': ('HapHiC_cluster.py:1512-1536', correct.bam_generator_for_correction),
 }
 _NEEDS_ORIGINAL = ('detect_break_points', 'break_and_update_ctgs')
+# --remove_allelic_links on the device tables (haphic_amd/allelic.py).  OPT-IN: the mirror works on the frozen containers of the S5 mirrors where
+# the reference's function thaws them, and what patch_reference(H) does by default stays what it was.  Calls the array path does not
+# serve (allelic.py lists them) go to the original function.
+ALLELIC_SEAMS = {
+    'remove_allelic_HiC_links': ('HapHiC_cluster.py:474-692', allelic.remove_allelic_HiC_links),
+}
 
 
 # position of `dense_matrix` in the reference signatures: --dense_matrix (:2723) is the reference's own numpy mode, which
@@ -109,8 +115,9 @@ def _run_then_join(original):
     return run
 
 
-def patch_reference(H, ingest=True, matrix_build=True):
-    """H: the imported reference module (HapHiC_cluster).  Returns {name: original} so the caller can undo."""
+def patch_reference(H, ingest=True, matrix_build=True, allelic=False):
+    """H: the imported reference module (HapHiC_cluster).  Returns {name: original} so the caller can undo.  allelic=True (together with
+    ingest): remove_allelic_HiC_links :474-692 is re-bound too (ALLELIC_SEAMS); `python -m haphic_amd cluster` asks for it on one-rank jobs."""
     from . import _lib
     _lib.load()                          # fail loudly here if the HIP library is missing
     saved = {}
@@ -125,9 +132,11 @@ def patch_reference(H, ingest=True, matrix_build=True):
         seams['bam_generator'] = OPTIONAL['bam_generator']                    # f4: consumed by the same S5 mirrors
         seams.update(CONTAINER_SEAMS)
         seams.update(CORRECTION_SEAMS)
+    if ingest and allelic:
+        seams.update(ALLELIC_SEAMS)
     for name, (_cite, fn) in seams.items():
         saved[name] = getattr(H, name, None)
-        if name in CONTAINER_SEAMS or name in _NEEDS_ORIGINAL:
+        if name in CONTAINER_SEAMS or name in _NEEDS_ORIGINAL or name in ALLELIC_SEAMS:
             fn = _with_original(fn, saved[name])
         setattr(H, name, _dense_dispatch(fn, saved[name], DENSE_ARG[name]) if name in DENSE_ARG else fn)
     if ingest and getattr(H, 'run', None) is not None:

@@ -492,6 +492,40 @@ int hhx_ingest_fetch_ht_order(hhx_ingest *h, int64_t *first);
  * NULL arrays for the size). */
 int hhx_ingest_keep_frag_pairs(hhx_ingest *h, int on);
 int hhx_ingest_fetch_frag_pairs(hhx_ingest *h, int64_t *n_pairs, int32_t *frag_i, int32_t *frag_j);
+
+/* --remove_allelic_links on the device tables (remove_allelic_HiC_links :474-692, haphic_amd/csrc/hhx_allelic.hip).  Both entries take a
+ * finalized handle; a return value of HHX_UNSUPPORTED (hhx_last_error() says why) means "not served here, take the reference's loop" and
+ * leaves the handle untouched.
+ *
+ * hhx_ingest_concordance: record_coord_pairs :454-465 + cal_concordance_ratio :419-428 as integers.  For every full_link_dict key, in dict
+ * insertion order (the order of hhx_ingest_fetch; host arrays [n_full_keys]):
+ *   m    = min(count, max_read_pairs);
+ *   diag = the modal count of floor((y - x) / w) over the key's first m read pairs in STREAM order (across pushes),
+ *   anti = the modal count of (y + x) / w over the same pairs, w = min(len_i, len_j) / nwindows (integer division, :421),
+ * x, y the oriented 1-based contig coordinates of the kept read pairs (hhx_ingest_keep_pairs).  The ratio of :428 is
+ * max(diag / m, anti / m) in float64 on the host: the same two IEEE divisions, so no float leaves the device.  Keys with
+ * m < min(min_read_pairs, max_read_pairs) are not evaluated (:589) and get diag = anti = 0.  One wavefront per key: up to 256 pairs an
+ * all-pairs equality count out of LDS, above that a sort in LDS and the longest run.  max_read_pairs is served up to 4096 (the list one
+ * wavefront sorts in 32 KB of LDS); beyond that, and when a contig is shorter than nwindows (w = 0: the reference raises), HHX_UNSUPPORTED.
+ * The grouped read pairs stay in HBM; the call only reads the kept pairs (a queued paired_links.clm may be reading them too).
+ *
+ * hhx_ingest_drop_links: update_link_dicts :488-509 for a whole verdict at once, and the isolated-fragment pass :678-692.
+ *   full_drop [n_full_keys] (host): non-zero = the key leaves full_link_dict;  in_set [n_frag] (host): the fragment is in filtered_frags.
+ * A flank_link_dict key leaves when the contig pair of its two fragments was dropped and both fragments are in in_set — with split contigs
+ * through the fragment -> contig map (what ctg_pair_to_frag :1731 encodes; bins of one contig are never affected), else it is the same key.
+ * Outputs (host, each may be null): the sizes of the two dicts afterwards; flank_dropped [n_flank_keys before the call], in dict order;
+ * remaining [n_frag]: the fragment is in in_set and occurs in a surviving flank key whose other fragment is in in_set too (:680-683);
+ * first_row [n_frag]: 2 * (dict position of the first such key) + (1 if the fragment is its second name), -1 if none — sorting by it gives
+ * the order in which :680-683 meets the fragments.  The rows say "not in this dict" from then on (first-seen ordinal = UINT64_MAX), so
+ * hhx_ingest_fetch, _flank_device (the float64 values, weights included, are carried over), _link_matrix, _write_link_pickle_async, _table_device
+ * and the sharded builds see the smaller dicts; frag_links (frag_link_dict) and the HT counts of the surviving keys do not change.  The kept
+ * read pairs no longer match the table: hhx_ingest_fetch_pairs / _fetch_ht_order / _fetch_ht_items / _write_clm / _concordance fail afterwards
+ * (the reference writes HT_links.pkl and paired_links.clm before :2911).  Waits for the files queued on this handle first. */
+#define HHX_UNSUPPORTED 2
+int hhx_ingest_concordance(hhx_ingest *h, int64_t max_read_pairs, int64_t min_read_pairs, int64_t nwindows, int32_t *m, int32_t *diag,
+                           int32_t *anti);
+int hhx_ingest_drop_links(hhx_ingest *h, const uint8_t *full_drop, const uint8_t *in_set, int64_t *n_full_left, int64_t *n_flank_left,
+                          uint8_t *flank_dropped, uint8_t *remaining, int64_t *first_row);
 int hhx_ingest_destroy(hhx_ingest *h);
 
 /* Multi-GPU exchange step (ingest).  The aggregated table of a finalized handle, device
