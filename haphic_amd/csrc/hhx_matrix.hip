@@ -483,13 +483,22 @@ __device__ __forceinline__ float entry_val(u64 w0, const u64 *__restrict__ w1, i
 // The rows are short (3.3k entries on average at C3), so a row is a chain of dependent round trips — entries, index
 // gather, barriers, stores — and the kernel is latency bound: the entries of the NEXT row of the workgroup are loaded
 // into registers before the current row's gather / rank / store phases begin.
+// Write-out, STAGED: an entry's CSR position is the bitmap rank of its column, an effectively random place in the row, so storing it
+// from the thread that holds it is two lane-scattered dword stores (~55 64-byte segments per wave instruction instead of 4).
+// Instead the entries held in registers (the first EMIT_R * EMIT_T of the row, and the self loop) go to an LDS staging area of
+// S positions at their rank, in passes over the rank windows [q, q + S), and the workgroup copies each window to oj / ox with
+// consecutive lanes on consecutive positions.  Entries beyond the registers are read and ranked again in every pass.
+// !STAGED: every entry is stored directly (no room to stage, or HHX_EMIT_STAGE=0).
 constexpr int EMIT_T = 512, EMIT_R = 8;
-template <bool PACKED>
-__global__ __launch_bounds__(EMIT_T) void k_row_emit(i32 n_frag, i32 W, int self_loop, const i64 *__restrict__ base, const u64 *__restrict__ w0,
+constexpr int EMIT_MIN_STAGE = EMIT_T;      // fewer positions than one per thread are not worth the two barriers of a pass
+template <bool PACKED, bool STAGED>
+__global__ __launch_bounds__(EMIT_T) void k_row_emit(i32 n_frag, i32 W, i32 S, int self_loop, const i64 *__restrict__ base, const u64 *__restrict__ w0,
                                                      const u64 *__restrict__ w1, const i32 *__restrict__ frag_index,
                                                      const i32 *__restrict__ indptr, i32 *__restrict__ oj, float *__restrict__ ox) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32 *bitmap = (u32 *)smem, *prefix = bitmap + W, *wsum = prefix + W;       // wsum[EMIT_T / 64]
+    i32 *sj = (i32 *)(wsum + EMIT_T / HHX_WAVE);                               // STAGED: sj[S], sx[S]
+    float *sx = (float *)(sj + S);
     const int tid = threadIdx.x, lane = lane_id(), wave = tid / HHX_WAVE;
     i32 a = blockIdx.x;
     if (a >= n_frag) return;
@@ -518,6 +527,11 @@ __global__ __launch_bounds__(EMIT_T) void k_row_emit(i32 n_frag, i32 W, int self
             i32 cc[EMIT_R];
 #pragma unroll
             for (int u = 0; u < EMIT_R; ++u) { const i64 p = b + tid + (i64)u * EMIT_T; cc[u] = p < e ? frag_index[entry_col<PACKED>(t0[u])] : -1; }
+            [[maybe_unused]] float vv[EMIT_R];                          // STAGED: the values, taken here so that t0 dies before the ranks live
+            if constexpr (STAGED) {
+#pragma unroll
+                for (int u = 0; u < EMIT_R; ++u) { const i64 p = b + tid + (i64)u * EMIT_T; vv[u] = p < e ? entry_val<PACKED>(t0[u], w1, p) : 0.0f; }
+            }
             lds_barrier();
 #pragma unroll
             for (int u = 0; u < EMIT_R; ++u) if (cc[u] >= 0) atomicOr(&bitmap[cc[u] >> 5], 1u << (cc[u] & 31));
@@ -543,6 +557,41 @@ __global__ __launch_bounds__(EMIT_T) void k_row_emit(i32 n_frag, i32 W, int self
 #pragma unroll
             for (int u = 0; u < EMIT_R; ++u) asm volatile("" : "+v"(tn[u]));
             asm volatile("" : "+v"(rn)); asm volatile("" : "+v"(bn)); asm volatile("" : "+v"(en));
+            if constexpr (STAGED) {
+                // rank of every register-held entry, kept across the passes; -1: no entry (never inside a window)
+                i32 kk[EMIT_R];
+#pragma unroll
+                for (int u = 0; u < EMIT_R; ++u) {
+                    const i32 c = cc[u];
+                    kk[u] = c >= 0 ? (i32)(prefix[c >> 5] + __popc(bitmap[c >> 5] & ((1u << (c & 31)) - 1u))) : -1;
+                }
+                i32 ks = -1;                                                // the self loop is thread 0's ninth entry
+                if (self_loop && tid == 0) ks = (i32)(prefix[r >> 5] + __popc(bitmap[r >> 5] & ((1u << (r & 31)) - 1u)));
+                i32 total = 0;                                              // entries of the row, the self loop counted in
+#pragma unroll
+                for (int w = 0; w < EMIT_T / HHX_WAVE; ++w) total += (i32)wsum[w];
+                total = __builtin_amdgcn_readfirstlane(total);
+                for (i32 q = 0; q < total; q += S) {
+                    if (q) lds_barrier();                                   // the previous window has been copied out
+#pragma unroll
+                    for (int u = 0; u < EMIT_R; ++u)
+                        if ((u32)(kk[u] - q) < (u32)S) { sj[kk[u] - q] = cc[u]; sx[kk[u] - q] = vv[u]; }
+                    if ((u32)(ks - q) < (u32)S) { sj[ks - q] = r; sx[ks - q] = 1.0f; }      // self loops :362-364
+                    // entries beyond the registers: read again, and ranked again, in every pass (the copy writes whole windows, so
+                    // no position of the row may bypass the staging); in the first pass no store of the row is in front of the loads
+                    for (i64 p = b + tid + (i64)EMIT_R * EMIT_T; p < e; p += EMIT_T) {
+                        const u64 t = w0[p];
+                        const i32 c = frag_index[entry_col<PACKED>(t)];
+                        const i32 k = (i32)(prefix[c >> 5] + __popc(bitmap[c >> 5] & ((1u << (c & 31)) - 1u)));
+                        if ((u32)(k - q) < (u32)S) { sj[k - q] = c; sx[k - q] = entry_val<PACKED>(t, w1, p); }
+                    }
+                    lds_barrier();                                          // (after the last pass's: bitmap and prefix are free for the next row)
+                    const i32 m = min(S, total - q);
+                    for (i32 i = tid; i < m; i += EMIT_T) { oj[ob + q + i] = sj[i]; ox[ob + q + i] = sx[i]; }
+                }
+                if (total == 0) lds_barrier();                              // (never: a linked row has an entry)
+                // no barrier behind the last copy: the next staging write of this workgroup lies behind the barriers of the next row
+            } else {
 #pragma unroll
             for (int u = 0; u < EMIT_R; ++u)
                 if (cc[u] >= 0) {
@@ -564,6 +613,7 @@ __global__ __launch_bounds__(EMIT_T) void k_row_emit(i32 n_frag, i32 W, int self
                 ox[ob + k] = 1.0f;                                  // self loops :362-364
             }
             lds_barrier();
+            }
         } else {
 #pragma unroll
             for (int u = 0; u < EMIT_R; ++u) asm volatile("" : "+v"(tn[u]));
@@ -607,6 +657,19 @@ i32 d2m_lds_frags() {
     const long long v = atoll(e);
     return v <= 0 ? 0 : (i32)std::min<long long>(v, D2M_LDS_MAX_FRAGS);
 }
+
+// positions of a row that the emit kernel stages in LDS per pass at most (HHX_EMIT_STAGE, read at every launch: a test places the pass
+// seams with it; unset: what LDS allows, 0: every entry stored directly from its thread)
+size_t emit_stage_cap() {
+    const char *e = getenv("HHX_EMIT_STAGE");
+    if (!e || !*e) return SIZE_MAX;
+    const long long v = atoll(e);
+    return v <= 0 ? 0 : (size_t)v;
+}
+// workgroups of the emit kernel at most (HHX_EMIT_GRID, read at every launch: a test walks one workgroup through every row); 0: no cap
+i64 emit_grid_cap() { const char *e = getenv("HHX_EMIT_GRID"); return e && atoll(e) > 0 ? atoll(e) : 0; }
+constexpr size_t EMIT_LDS_MAX = 160 * 1024;
+constexpr int EMIT_ROUNDS = 3;
 
 // PACKED: 8-byte entries (see SrcDirectedPacked); returns -2 when a count does not fit 24 bits (the caller takes the 16-byte path)
 template <bool PACKED>
@@ -692,18 +755,40 @@ int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const
     hipError_t e = hipMemcpyAsync(m->indptr.p, indptr.p, sizeof(i32) * ((size_t)shape + 1), hipMemcpyDeviceToDevice, g_stream);
     const i32 W = (shape + 31) / 32;
     const size_t lds = (size_t)W * 8 + (EMIT_T / HHX_WAVE) * 4;
-    if (lds > 160 * 1024) { hhx_csr_free(m); return fail("link matrix: order %d exceeds the LDS bitmap capacity", shape); }
-    static int attr_set = -1;           // the attribute is per device: keyed on the current ordinal
+    if (lds > EMIT_LDS_MAX) { hhx_csr_free(m); return fail("link matrix: order %d exceeds the LDS bitmap capacity", shape); }
+    static int attr_set = -1, n_cu = 0; // the attribute is per device: keyed on the current ordinal
     int attr_dev = 0;
     HHX_HIP(hipGetDevice(&attr_dev));
     if (attr_set != attr_dev) {
-        (void)hipFuncSetAttribute((const void *)k_row_emit<PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void *)k_row_emit<PACKED, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EMIT_LDS_MAX);
+        (void)hipFuncSetAttribute((const void *)k_row_emit<PACKED, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)EMIT_LDS_MAX);
+        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, attr_dev);
         attr_set = attr_dev;
     }
     if (e == hipSuccess && part.n_valid) {
+        // Staging gets the LDS that the resident workgroups of a CU leave over: the count the kernel reaches with the bitmap and
+        // prefix alone (registers, waves) is kept.  The grid is a whole number of rounds of the resident workgroups, rows dealt by a static stride.
+        const size_t want = emit_stage_cap();
+        int resident = 0;
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, (const void *)k_row_emit<PACKED, true>, EMIT_T, lds);
+        if (resident < 1) resident = 1;
+        size_t S = want ? (EMIT_LDS_MAX / (size_t)resident > lds ? (EMIT_LDS_MAX / (size_t)resident - lds) / 8 : 0) : 0;
+        for (int with = 0; S >= (size_t)EMIT_MIN_STAGE; S -= 64) {      // (LDS is handed out in granules: trim until the count holds)
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with, (const void *)k_row_emit<PACKED, true>, EMIT_T, lds + S * 8) != hipSuccess || with >= resident) break;
+        }
+        if (S < (size_t)EMIT_MIN_STAGE) S = 0;                          // no room worth a pass: direct stores
+        else S = std::min(std::min(S, want), (size_t)shape);            // (a row has at most `shape` entries)
+        if (!S) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, (const void *)k_row_emit<PACKED, false>, EMIT_T, lds);
+        // (EMIT_ROUNDS workgroups per resident slot: the dispatcher evens out what the static stride leaves uneven in row lengths)
+        i64 grid = std::min<i64>(n_frag, (i64)std::max(resident, 1) * std::max(n_cu, 1) * EMIT_ROUNDS);
+        if (const i64 cap = emit_grid_cap()) grid = std::min(grid, cap);
         KTimer kt("d2m_emit");
-        k_row_emit<PACKED><<<(unsigned)std::min<i64>(n_frag, 256 * 6), EMIT_T, lds, g_stream>>>(n_frag, W, add_self_loops, part.base.p, part.w0.p,
-                                                                                          (const u64 *)part.w1.p, frag_index.p, indptr.p, m->indices.p, m->data.p);
+        if (S)
+            k_row_emit<PACKED, true><<<(unsigned)grid, EMIT_T, lds + S * 8, g_stream>>>(n_frag, W, (i32)S, add_self_loops, part.base.p, part.w0.p,
+                                                                                      (const u64 *)part.w1.p, frag_index.p, indptr.p, m->indices.p, m->data.p);
+        else
+            k_row_emit<PACKED, false><<<(unsigned)grid, EMIT_T, lds, g_stream>>>(n_frag, W, 0, add_self_loops, part.base.p, part.w0.p,
+                                                                                 (const u64 *)part.w1.p, frag_index.p, indptr.p, m->indices.p, m->data.p);
     }
     if (e == hipSuccess && add_self_loops && shape > (i32)n_linked)
         k_rest_rows<<<grid_for((u64)(shape - (i32)n_linked)), 256, 0, g_stream>>>((i32)n_linked, shape, indptr.p, m->indices.p, m->data.p);
