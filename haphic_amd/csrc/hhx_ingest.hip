@@ -288,14 +288,12 @@ __global__ __launch_bounds__(AG_T) void k_aggregate(AggParams A) {
             u32 slot = (u32)h & (tsize - 1);
             u32 probe = 0;
             for (; probe < tsize; ++probe) {
-                // (a volatile access would lose the LDS address space: a FLAT load, which waits for every outstanding global load)
-                const u64 cur = __hip_atomic_load(&s_key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (cur == key) break;
-                if (cur == EMPTY_KEY) {
-                    const u64 old = atomicCAS((unsigned long long *)&s_key[slot], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-                    wins += old == EMPTY_KEY;
-                    if (old == EMPTY_KEY || old == key) break;
-                }
+                // The CAS is the probe: what it returns says "empty, now mine", "my key" or "another key" — ONE LDS operation a
+                // probe.  (A read in front of it, with the CAS only for a slot read as empty, is two for every new key, and the
+                // insert phase is bound by the number of LDS operations, not by their latency: DESIGN 4.2.)
+                const u64 old = atomicCAS((unsigned long long *)&s_key[slot], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
+                wins += old == EMPTY_KEY;
+                if (old == EMPTY_KEY || old == key) break;
                 slot = (slot + 1) & (tsize - 1);
             }
             if (probe == tsize) { atomicExch(A.overflow, 1u); return; }
