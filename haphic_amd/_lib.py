@@ -145,6 +145,9 @@ SIGNATURES = {
     'hhx_ingest_set_ordinal_base': (C.c_int, [C.c_void_p, C.c_int64]),
     'hhx_ingest_concordance': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_ingest_drop_links': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64p, c_i64p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_allelic_nonmax': (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     c_i32p]),
+    'hhx_lsap_small': (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     'hhx_ingest_link_matrix': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, c_i32p, c_vpp]),
     'hhx_ingest_table_device': (C.c_int, [C.c_void_p, C.c_int, c_i64p, c_vpp, c_vpp, c_vpp, c_vpp, c_vpp]),
     'hhx_ingest_push_table': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -837,6 +840,33 @@ def group_link_sums(frag_i, frag_j, links, group, n_groups):
     first = np.full((len(grp), int(n_groups)), -1, np.int64)
     check(load().hhx_group_link_sums(len(lk), ptr(fi), ptr(fj), ptr(lk), len(grp), ptr(grp), int(n_groups), ptr(sums), ptr(first)))
     return sums, first
+
+
+def allelic_nonmax(ki, kj, kcnt, n_ctg, gptr, gmem):
+    """hhx_allelic_nonmax — the links between non-maximum matches :621-667: (mask uint8 [n_keys], counters int64 [3] = candidates, distinct group
+    pairs, assignment problems), None when an `assert` of :652-659 would fail, NotImplemented when the library does not serve the call (an allele
+    group of more than 8 contigs).  gptr / gmem: the groups in the reference's tuple order as contig ids."""
+    ki, kj = np.ascontiguousarray(ki, np.int32), np.ascontiguousarray(kj, np.int32)
+    kcnt = np.ascontiguousarray(kcnt, np.int64)
+    gptr, gmem = np.ascontiguousarray(gptr, np.int64), np.ascontiguousarray(gmem, np.int32)
+    if not (len(ki) == len(kj) == len(kcnt)) or len(gptr) < 1 or int(gptr[-1]) != len(gmem):
+        raise ValueError('allelic_nonmax: ki, kj, kcnt of one length; gptr[-1] == len(gmem)')
+    mask, counters, bad = np.zeros(len(ki), np.uint8), np.zeros(3, np.int64), C.c_int32(0)
+    rc = load().hhx_allelic_nonmax(len(ki), ptr(ki), ptr(kj), ptr(kcnt), int(n_ctg), len(gptr) - 1, ptr(gptr), ptr(gmem), ptr(mask), ptr(counters), C.byref(bad))
+    if rc == Ingest.UNSUPPORTED:
+        return NotImplemented
+    check(rc)
+    return None if bad.value else (mask, counters)
+
+
+def lsap_small(cost):
+    """hhx_lsap_small: col4row int32 [n, d] of scipy.optimize.linear_sum_assignment on every d x d matrix of cost [n, d, d] (int64, minimised), d <= 8"""
+    cost = np.ascontiguousarray(cost, np.int64)
+    if cost.ndim != 3 or cost.shape[1] != cost.shape[2]:
+        raise ValueError('lsap_small: cost [n, d, d]')
+    out = np.zeros(cost.shape[:2], np.int32)
+    check(load().hhx_lsap_small(cost.shape[0], cost.shape[1], ptr(cost), ptr(out)))
+    return out
 
 
 def row_products(a, b):

@@ -1,17 +1,22 @@
 """remove_allelic_HiC_links() :474-692 on the device tables (--remove_allelic_links, BASELINE.json configs[3]).
 
 The reference walks ctg_coord_dict and full_link_dict key by key; with the array-backed containers of the S5 mirrors
-(containers.py) that walk first thaws three tables into Python dicts.  Here the two halves that touch every key run on the
-device tables (haphic_amd/csrc/hhx_allelic.hip):
+(containers.py) that walk first thaws three tables into Python dicts.  Here everything that touches every key runs on the
+device (haphic_amd/csrc/hhx_allelic.hip):
 
     stage 1   cal_concordance_ratio :419-428 of every eligible key as integer modal counts (hhx_ingest_concordance);
               the ratio is formed here, in float64, by the same two divisions as :428
+    stage 2   the links between non-maximum matches :621-667 (hhx_allelic_nonmax through nonmax_keys_device): the candidate keys times their
+              allele groups, the unique group pairs, their matrices, linear_sum_assignment and the mismatch verdict
     verdict   update_link_dicts :488-509 for both stages at once, and the isolated fragments :678-692 (hhx_ingest_drop_links)
 
-and what lies between stays host code on ARRAYS, with no Python statement per key: the allele groups (networkx cliques on the
-few allelic keys, split_cliques / get_weakest_edge restated from :511-550) and the non-maximum matches (:621-667), where one
-scipy.optimize.linear_sum_assignment call per unique pair of allele groups that more than one key connects is the only per-item call
-left (a pair connected by a single key has one non-zero cell in its matrix, which every optimal assignment contains).
+and the allele groups between stage 1 and 2 stay host code (networkx cliques on the few allelic keys, split_cliques / get_weakest_edge
+restated from :511-550).  Stage 2 must pick scipy's assignment among equal optima: the device solver restates scipy's method step by step, and
+lsap_small() below is the same in Python, its oracle.  nonmax_keys() is the host form of stage 2 — numpy on ARRAYS plus one
+scipy.optimize.linear_sum_assignment call per unique pair of allele groups that more than one key connects (a pair connected by a single
+key has one non-zero cell in its matrix, which every optimal assignment contains).  It is the specification of the device form and serves when
+the engine is not the library's own Ingest (and has no nonmax_keys method of its own), when HAPHIC_ALLELIC_STAGE2=host, and when an allele group
+has more than 8 contigs; STATS['stage2_engine'] says which form ran.
 
 The array path is taken only when the containers are still frozen on one live session and the run is the plain one; every
 other call goes to the reference's own function (`_original`, bound by patch.patch_reference(H, allelic=True)), which thaws as before:
@@ -24,10 +29,12 @@ other call goes to the reference's own function (`_original`, bound by patch.pat
   * no `assert` of :652-659 would fail (then the original raises it).
 """
 import logging
+import os
 import time
 
 import numpy as np
 
+from . import _lib as _hip
 from . import cluster
 
 logger = cluster.logger
@@ -194,6 +201,93 @@ def nonmax_keys(si, sj, scnt, groups, names, ctg_rank, stats=None):
     return out
 
 
+def lsap_small(cost):
+    """scipy.optimize.linear_sum_assignment(cost)[1] of a square integer matrix, restated step by step from scipy 1.15's solver (the shortest
+    augmenting path method with dual variables, Crouse's variant of Jonker-Volgenant), in Python integers: the CPU oracle of the device
+    solver (csrc/hhx_allelic.hip lsap_solve) and the documentation of the order and tie rule that make the result scipy's among equal optima —
+      * the unvisited columns are scanned in the order of `remaining`, which starts as [d-1 .. 0] and loses a visited column by moving its last
+        element into that slot;
+      * a column as cheap as the cheapest so far replaces it only when it is unassigned.
+    Every quantity is a sum or difference of the costs, which scipy's doubles hold exactly below 2^53."""
+    cost = [[int(x) for x in row] for row in np.asarray(cost).tolist()]
+    d = len(cost)
+    inf = None                                                   # +inf of shortestPathCosts: compared, never added to
+    u, v = [0] * d, [0] * d
+    col4row, row4col, path = [-1] * d, [-1] * d, [-1] * d
+    for cur in range(d):
+        remaining = list(range(d - 1, -1, -1))
+        shortest = [inf] * d
+        SR, SC = [False] * d, [False] * d
+        min_val, i, sink = 0, cur, -1
+        while sink == -1:
+            index, lowest = -1, inf
+            SR[i] = True
+            for it, j in enumerate(remaining):
+                r = min_val + cost[i][j] - u[i] - v[j]
+                if shortest[j] is inf or r < shortest[j]:
+                    path[j] = i
+                    shortest[j] = r
+                if lowest is inf or shortest[j] < lowest or (shortest[j] == lowest and row4col[j] == -1):
+                    lowest = shortest[j]
+                    index = it
+            min_val = lowest
+            j = remaining[index]
+            if row4col[j] == -1:
+                sink = j
+            else:
+                i = row4col[j]
+            SC[j] = True
+            remaining[index] = remaining[-1]
+            remaining.pop()
+        u[cur] += min_val
+        for k in range(d):
+            if SR[k] and k != cur:
+                u[k] += min_val - shortest[col4row[k]]
+        for j in range(d):
+            if SC[j]:
+                v[j] -= min_val - shortest[j]
+        j = sink
+        while True:                                              # flip the path back from the sink
+            i = path[j]
+            row4col[j] = i
+            col4row[i], j = j, col4row[i]
+            if i == cur:
+                break
+    return np.asarray(col4row, np.int64)
+
+
+def nonmax_keys_device(si, sj, scnt, groups, names, ctg_rank, stats=None):
+    """nonmax_keys on the device (hhx_allelic_nonmax): the same arguments, the same mask (or None), the same `stats`; NotImplemented when the
+    library does not serve the call (an allele group of more than 8 contigs).  The host part is the group table alone."""
+    stats = {} if stats is None else stats
+    stats.update(candidates=0, group_pairs=0, assignments=0, assignment_s=0.0)
+    cid = {n: k for k, n in enumerate(names)}
+    groups = sorted(groups)                                    # position = rank under tuple comparison :644
+    glen = np.fromiter(map(len, groups), np.int64, len(groups))
+    gmem = np.fromiter((cid[c] for g in groups for c in g), np.int32, int(glen.sum()))
+    gptr = np.concatenate([[0], np.cumsum(glen)]).astype(np.int64)
+    got = _hip.allelic_nonmax(si, sj, scnt, len(names), gptr, gmem)
+    if got is None or got is NotImplemented:
+        return got
+    mask, counters = got
+    stats.update(candidates=int(counters[0]), group_pairs=int(counters[1]), assignments=int(counters[2]))
+    return mask.astype(bool)
+
+
+STAGE2_DEFAULT = 'device'      # what the real engine takes when HAPHIC_ALLELIC_STAGE2 (host / device) does not say
+
+
+def _stage2(engine):
+    """(the function that serves stage 2 with this engine, 'device' / 'host'): a stand-in engine's own nonmax_keys, the device form with the real
+    engine unless the environment says host, else the host form"""
+    own = getattr(engine, 'nonmax_keys', None)
+    if own is not None:
+        return own, 'device'
+    if isinstance(engine, _hip.Ingest) and os.environ.get('HAPHIC_ALLELIC_STAGE2', STAGE2_DEFAULT) != 'host':
+        return nonmax_keys_device, 'device'
+    return nonmax_keys, 'host'
+
+
 def _array_path(fa_dict, ctg_coord_dict, full_link_dict, args, flank_link_dict, filtered_frags, ctg_pair_to_frag, log, engine):
     """the session when the call can run on the arrays, else None"""
     frozen = cluster._frozen
@@ -254,7 +348,11 @@ def remove_allelic_HiC_links(fa_dict, ctg_coord_dict, full_link_dict, args, flan
     # ---- 2) links between non-max matches (:621-667), among the keys that are left
     stats = {}
     left = np.flatnonzero(~allelic)
-    nonmax = nonmax_keys(fi[left], fj[left], cnt[left], groups, names, table.ctg_rank, stats)
+    stage2, stage2_engine = _stage2(engine)
+    nonmax = stage2(fi[left], fj[left], cnt[left], groups, names, table.ctg_rank, stats)
+    if nonmax is NotImplemented:                               # not served there (an allele group beyond the solver's size)
+        stage2_engine = 'host'
+        nonmax = nonmax_keys(fi[left], fj[left], cnt[left], groups, names, table.ctg_rank, stats)
     if nonmax is None:
         return original()
     t_nonmax = time.perf_counter()
@@ -278,7 +376,7 @@ def remove_allelic_HiC_links(fa_dict, ctg_coord_dict, full_link_dict, args, flan
     logger.info('{} fragments removed, {} fragments kept'.format(len(filtered_frags) - len(remaining_frags), len(remaining_frags)))
     t_end = time.perf_counter()
     STATS.clear()
-    STATS.update(stats, keys=int(len(m)), stage1_keys=int(allelic.sum()), allele_groups=len(groups), stage2_keys=int(nonmax.sum()),
+    STATS.update(stats, stage2_engine=stage2_engine, keys=int(len(m)), stage1_keys=int(allelic.sum()), allele_groups=len(groups), stage2_keys=int(nonmax.sum()),
                  concordance_s=t_counts - t_start, groups_s=t_groups - t_counts, stage2_s=t_nonmax - t_groups, drop_s=t_end - t_nonmax,
                  total_s=t_end - t_start)
     return remaining_frags

@@ -2,13 +2,17 @@
 //   hhx_ingest_concordance  record_coord_pairs :454-465 + cal_concordance_ratio :419-428 as integers: per full_link_dict key, the modal
 //                           counts of the diagonal / anti-diagonal windows of its first max_read_pairs read pairs (stream order)
 //   hhx_ingest_drop_links   update_link_dicts :488-509 for a whole verdict at once + the isolated-fragment pass :678-692
-// What lies between them — the cliques of the allele graph and the assignment problems — is host code (haphic_amd/allelic.py).
+//   hhx_allelic_nonmax      the links between non-maximum matches :621-667 (stage 2) on plain host arrays: candidate keys x their allele groups,
+//                           one sort by group pair, one worker per pair (matrix in LDS, linear_sum_assignment's own method and tie rule)
+//   hhx_lsap_small          that solver alone, batched
+// What lies between — the cliques of the allele graph (networkx) — is host code (haphic_amd/allelic.py).
 //
 // The read pairs are grouped by contig pair with the stable key sort the coordinate lists and paired_links.clm already use
-// (hhx::group_pairs, hhx_pairs.hip); the grouped records stay in HBM.  Both entries run on the calling thread's stream and pool arena and
+// (hhx::group_pairs, hhx_pairs.hip); the grouped records stay in HBM.  The two hhx_ingest_ entries run on the calling thread's stream and pool arena and
 // only READ the side records, so a queued paired_links.clm (hhx_ingest_write_clm_async) may be reading them at the same time.
 // hhx_ingest_drop_links changes the tables and therefore first waits for the files queued on this handle.
 #include <algorithm>
+#include <cstdlib>
 
 #include "hhx_ingest.h"
 #include "hhx_sort.h"
@@ -321,5 +325,305 @@ extern "C" int hhx_ingest_drop_links(hhx_ingest *h, const uint8_t *full_drop, co
     HHX_HIP(hipStreamSynchronize(g_stream));
     if (n_full_left) *n_full_left = h->n_full;
     if (n_flank_left) *n_flank_left = h->n_flank;
+    return 0;
+}
+
+// ================================================================================================ stage 2: links between non-maximum matches
+// remove_allelic_HiC_links :621-667.  A key both of whose contigs sit in allele groups yields one combination per (group of ctg_1) x (group of
+// ctg_2); the combinations are sorted by their group pair (ga <= gb, ranks under the reference's tuple order), so the combinations of one pair
+// are one run.  Every non-zero cell of the pair's degree x degree matrix (:552-568) is a key between the two groups, and every such key is
+// a combination of this very run: the worker of a pair fills the matrix from its run, in both roles where a contig sits in both groups.
+namespace {
+
+constexpr int NM_MAXD = 8;             // largest allele group served (ploidy); documented in haphic_hip.h
+constexpr u32 NM_NONE = 0xF;           // "not in the group" / "unassigned" in a 4-bit field
+constexpr i64 NM_INF = INT64_MAX;      // +inf of shortestPathCosts: compared, never added to
+
+__device__ __forceinline__ u32 nib(u32 w, int k) { return (w >> (4 * k)) & 0xFu; }
+__device__ __forceinline__ u32 set_nib(u32 w, int k, u32 x) { return (w & ~(0xFu << (4 * k))) | (x << (4 * k)); }
+
+// workgroups of the stage-2 passes at most (HHX_NONMAX_GRID, read at every launch: a test walks the grid-stride loops on two workgroups)
+inline unsigned nonmax_grid(u64 n, unsigned per) {
+    u64 b = (n + per - 1) / per;
+    if (b < 1) b = 1;
+    if (b > 256 * 16) b = 256 * 16;
+    const char *e = getenv("HHX_NONMAX_GRID");
+    if (e && atoi(e) > 0 && (u64)atoi(e) < b) b = (u64)atoi(e);
+    return (unsigned)b;
+}
+inline size_t nonmax_lds_bytes(int d) { return (size_t)(d * d + 3 * d) * HHX_WAVE * sizeof(i64); }
+
+// scipy.optimize.linear_sum_assignment (1.15: the shortest augmenting path method with dual variables, Crouse's variant of Jonker-Volgenant)
+// on a d x d int64 cost matrix, minimising, with scipy's own scan order and tie rule, so that the assignment is scipy's among equal optima:
+// `remaining` starts as [d-1 .. 0] and a visited column is replaced by the last one; a column as cheap as the cheapest so far takes its place
+// only when it is unassigned.  All quantities are sums and differences of the integer costs (exact in scipy's doubles below 2^53).
+// One problem per lane: cost cell (i, j) at cost[(i * d + j) * 64], u / v / sp element k at [k * 64] (the lane's own LDS column: no two lanes
+// of a wave share a bank); path, row4col, col4row and remaining are 4-bit fields of a register.  Returns col4row.
+__device__ __forceinline__ u32 lsap_solve(int d, const i64 *cost, i64 *u, i64 *v, i64 *sp) {
+    u32 col4row = ~0u, row4col = ~0u;
+    for (int k = 0; k < d; ++k) { u[k * HHX_WAVE] = 0; v[k * HHX_WAVE] = 0; }
+    for (int cur = 0; cur < d; ++cur) {
+        u32 remaining = 0, path = 0, SR = 0, SC = 0;
+        for (int it = 0; it < d; ++it) { remaining |= (u32)(d - 1 - it) << (4 * it); sp[it * HHX_WAVE] = NM_INF; }
+        int num_remaining = d, i = cur, sink = -1;
+        i64 min_val = 0;
+        while (sink < 0 && num_remaining > 0) {                  // (an unassigned column is left while cur < d: the second test never ends the loop)
+            int index = 0;
+            i64 lowest = NM_INF;
+            SR |= 1u << i;
+            const i64 ui = u[i * HHX_WAVE];
+            for (int it = 0; it < num_remaining; ++it) {
+                const int j = (int)nib(remaining, it);
+                const i64 r = min_val + cost[(i * d + j) * HHX_WAVE] - ui - v[j * HHX_WAVE];
+                i64 s = sp[j * HHX_WAVE];
+                if (r < s) { path = set_nib(path, j, (u32)i); s = r; sp[j * HHX_WAVE] = r; }
+                if (s < lowest || (s == lowest && nib(row4col, j) == NM_NONE)) { lowest = s; index = it; }
+            }
+            min_val = lowest;
+            const int j = (int)nib(remaining, index);
+            const u32 owner = nib(row4col, j);
+            if (owner == NM_NONE) sink = j; else i = (int)owner;
+            SC |= 1u << j;
+            --num_remaining;
+            remaining = set_nib(remaining, index, nib(remaining, num_remaining));
+        }
+        if (sink < 0) break;
+        u[cur * HHX_WAVE] += min_val;
+        for (int k = 0; k < d; ++k)
+            if (((SR >> k) & 1u) && k != cur) u[k * HHX_WAVE] += min_val - sp[nib(col4row, k) * HHX_WAVE];     // a visited row other than cur is assigned, its column visited
+        for (int j = 0; j < d; ++j)
+            if ((SC >> j) & 1u) v[j * HHX_WAVE] -= min_val - sp[j * HHX_WAVE];
+        int j = sink;
+        for (int step = 0; step < d; ++step) {                   // flip the path back from the sink (at most d edges)
+            const u32 r = nib(path, j);
+            row4col = set_nib(row4col, j, r);
+            const u32 before = nib(col4row, (int)r);
+            col4row = set_nib(col4row, (int)r, (u32)j);
+            if ((int)r == cur) break;
+            j = (int)before;
+        }
+    }
+    return col4row;
+}
+
+__global__ __launch_bounds__(HHX_WAVE) void k_lsap_small(i64 n, int d, const i64 *__restrict__ cost, i32 *__restrict__ col4row) {
+    extern __shared__ __attribute__((aligned(16))) i64 s_nm[];
+    const int lane = threadIdx.x;
+    i64 *m = s_nm + lane, *u = m + (size_t)d * d * HHX_WAVE, *v = u + d * HHX_WAVE, *sp = v + d * HHX_WAVE;
+    for (i64 p = (i64)blockIdx.x * HHX_WAVE + lane; p < n; p += (i64)gridDim.x * HHX_WAVE) {
+        for (int c = 0; c < d * d; ++c) m[c * HHX_WAVE] = cost[p * d * d + c];
+        const u32 sol = lsap_solve(d, m, u, v, sp);
+        for (int k = 0; k < d; ++k) col4row[p * d + k] = (i32)nib(sol, k);
+    }
+}
+
+// the groups of every contig (ctg_allele_group_dict :624-627): cg_ptr [n_ctg + 1], cg_grp ascending per contig
+__global__ __launch_bounds__(256) void k_nonmax_count(i64 n, const i32 *__restrict__ ki, const i32 *__restrict__ kj, i32 n_ctg, const i32 *__restrict__ cg_ptr,
+                                                      i64 *__restrict__ combos, unsigned long long *__restrict__ counters, unsigned int *__restrict__ flags) {
+    i64 cand = 0;
+    for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (i64)gridDim.x * blockDim.x) {
+        const i32 a = ki[r], b = kj[r];
+        i64 c = 0;
+        if (a < 0 || a >= n_ctg || b < 0 || b >= n_ctg) atomicExch(&flags[1], 1u);
+        else c = (i64)(cg_ptr[a + 1] - cg_ptr[a]) * (i64)(cg_ptr[b + 1] - cg_ptr[b]);      // :639, :642-643
+        combos[r] = c;
+        cand += c > 0;
+    }
+    cand = wave_sum_i64(cand);
+    if (lane_id() == 0 && cand) atomicAdd(&counters[0], (unsigned long long)cand);
+}
+
+// position of contig c in group g (tuple.index), NM_NONE when it is no member
+__device__ __forceinline__ u32 pos_in(const i32 *__restrict__ gptr, const i32 *__restrict__ gmem, i32 g, i32 c) {
+    const i32 b = gptr[g], e = gptr[g + 1];
+    for (i32 t = b; t < e; ++t)
+        if (gmem[t] == c) return (u32)(t - b);
+    return NM_NONE;
+}
+
+// one (key, group_1, group_2) combination per slot: sort key ga * nG + gb, value = key index << 16 | the positions of ctg_1 and ctg_2 in ga and gb
+__global__ __launch_bounds__(256) void k_nonmax_expand(i64 n, const i32 *__restrict__ ki, const i32 *__restrict__ kj, const i64 *__restrict__ off,
+                                                       const i32 *__restrict__ cg_ptr, const i32 *__restrict__ cg_grp, const i32 *__restrict__ gptr,
+                                                       const i32 *__restrict__ gmem, i64 nG, u64 *__restrict__ skey, u64 *__restrict__ sval,
+                                                       unsigned int *__restrict__ flags) {
+    for (i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (i64)gridDim.x * blockDim.x) {
+        i64 at = off[r];
+        if (off[r + 1] == at) continue;
+        const i32 c1 = ki[r], c2 = kj[r];
+        const i32 b1 = cg_ptr[c1], e1 = cg_ptr[c1 + 1], b2 = cg_ptr[c2], e2 = cg_ptr[c2 + 1];
+        for (i32 x = b1; x < e1; ++x)
+            for (i32 y = b2; y < e2; ++y) {
+                const i32 g1 = cg_grp[x], g2 = cg_grp[y];
+                const i32 ga = g1 < g2 ? g1 : g2, gb = g1 < g2 ? g2 : g1;                  // group_pair :644
+                const u32 a1 = pos_in(gptr, gmem, ga, c1), a2 = pos_in(gptr, gmem, ga, c2), p1 = pos_in(gptr, gmem, gb, c1), p2 = pos_in(gptr, gmem, gb, c2);
+                // :652-659 — ctg_1 in group_pair[0] asks for ctg_2 in group_pair[1]; else ctg_2 in group_pair[0] and ctg_1 in group_pair[1]
+                if (a1 != NM_NONE ? p2 == NM_NONE : (a2 == NM_NONE || p1 == NM_NONE)) atomicExch(&flags[0], 1u);
+                skey[at] = (u64)ga * (u64)nG + (u64)gb;
+                sval[at] = ((u64)r << 16) | a1 | (a2 << 4) | (p1 << 8) | (p2 << 12);
+                ++at;
+            }
+    }
+}
+
+// One worker (lane) per group pair: the lane that holds the head of a run walks it.  The matrix holds -count (the reference solves
+// linear_sum_assignment(-matrix) :568) in the lane's LDS column and never goes to global memory.  A run of one combination that fills one
+// cell needs neither matrix nor solver: every optimal assignment contains the only non-zero cell, and its key is the only one that asks.
+__global__ __launch_bounds__(HHX_WAVE) void k_nonmax_pairs(i64 n, const u64 *__restrict__ skey, const u64 *__restrict__ sval, const i64 *__restrict__ kcnt, i64 nG,
+                                                          const i32 *__restrict__ gptr, int dmax, uint8_t *__restrict__ nonmax,
+                                                          unsigned long long *__restrict__ counters) {
+    extern __shared__ __attribute__((aligned(16))) i64 s_nm[];
+    const int lane = threadIdx.x;
+    i64 *m = s_nm + lane, *u = m + (size_t)dmax * dmax * HHX_WAVE, *v = u + dmax * HHX_WAVE, *sp = v + dmax * HHX_WAVE;
+    i64 pairs = 0, solved = 0;
+    for (i64 i = (i64)blockIdx.x * HHX_WAVE + lane; i < n; i += (i64)gridDim.x * HHX_WAVE) {
+        const u64 k = skey[i];
+        if (i > 0 && skey[i - 1] == k) continue;                // not the head of a run
+        ++pairs;
+        i64 e = i + 1;
+        while (e < n && skey[e] == k) ++e;
+        if (e == i + 1) {
+            const u32 w = (u32)sval[i];
+            const bool role_a = nib(w, 0) != NM_NONE && nib(w, 3) != NM_NONE, role_b = nib(w, 1) != NM_NONE && nib(w, 2) != NM_NONE;
+            if (!(role_a && role_b)) continue;
+        }
+        const i32 ga = (i32)(k / (u64)nG), gb = (i32)(k % (u64)nG);
+        const int la = gptr[ga + 1] - gptr[ga], lb = gptr[gb + 1] - gptr[gb];
+        const int d = la > lb ? la : lb;                        // :553 (<= dmax: the host sized the LDS by the largest group)
+        for (int c = 0; c < d * d; ++c) m[c * HHX_WAVE] = 0;
+        for (i64 t = i; t < e; ++t) {
+            const u64 val = sval[t];
+            const u32 w = (u32)val;
+            const i64 links = kcnt[val >> 16];
+            const u32 a1 = nib(w, 0), a2 = nib(w, 1), p1 = nib(w, 2), p2 = nib(w, 3);
+            if (a1 != NM_NONE && p2 != NM_NONE) m[(a1 * d + p2) * HHX_WAVE] = -links;       // ctg_1 a row of group_pair[0], ctg_2 a column of group_pair[1]
+            if (a2 != NM_NONE && p1 != NM_NONE) m[(a2 * d + p1) * HHX_WAVE] = -links;       // ... and the other way round
+        }
+        int cells = 0;
+        for (int c = 0; c < d * d; ++c) cells += m[c * HHX_WAVE] != 0;
+        if (cells <= 1) continue;
+        ++solved;
+        const u32 sol = lsap_solve(d, m, u, v, sp);
+        for (i64 t = i; t < e; ++t) {
+            const u64 val = sval[t];
+            const u32 w = (u32)val;
+            const bool first = nib(w, 0) != NM_NONE;                                        // :652
+            const u32 index_1 = first ? nib(w, 0) : nib(w, 1), index_2 = first ? nib(w, 3) : nib(w, 2);
+            if (index_1 != NM_NONE && index_2 != NM_NONE && nib(sol, (int)index_1) != index_2) nonmax[val >> 16] = 1;      // :661 (idempotent byte store)
+        }
+    }
+    pairs = wave_sum_i64(pairs); solved = wave_sum_i64(solved);
+    if (lane == 0) {
+        if (pairs) atomicAdd(&counters[1], (unsigned long long)pairs);
+        if (solved) atomicAdd(&counters[2], (unsigned long long)solved);
+    }
+}
+
+}  // namespace
+
+extern "C" int hhx_lsap_small(int64_t n, int32_t d, const int64_t *cost, int32_t *col4row) {
+    if (n < 0 || d < 1 || d > NM_MAXD) return fail("hhx_lsap_small: n >= 0 and 1 <= d <= %d", NM_MAXD);
+    if (n == 0) return 0;
+    if (!cost || !col4row) return fail("hhx_lsap_small: null pointer");
+    const size_t cells = (size_t)n * d * d, outs = (size_t)n * d;
+    DevBuf<i64> dc;
+    DevBuf<i32> ds;
+    if (dc.alloc(cells) || ds.alloc(outs)) return 1;
+    HHX_HIP(hipMemcpyAsync(dc.p, cost, sizeof(i64) * cells, hipMemcpyHostToDevice, g_stream));
+    {
+        KTimer kt("lsap_small");
+        k_lsap_small<<<nonmax_grid((u64)n, HHX_WAVE), HHX_WAVE, nonmax_lds_bytes(d), g_stream>>>(n, d, dc.p, ds.p);
+        HHX_LAUNCH_CHECK();
+    }
+    HHX_HIP(hipMemcpyAsync(col4row, ds.p, sizeof(i32) * outs, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+extern "C" int hhx_allelic_nonmax(int64_t n_keys, const int32_t *ki, const int32_t *kj, const int64_t *kcnt, int32_t n_ctg, int32_t n_groups,
+                                  const int64_t *gptr, const int32_t *gmem, uint8_t *nonmax, int64_t *counters, int32_t *assert_failed) {
+    if (n_keys < 0 || n_ctg < 0 || n_groups < 0) return fail("hhx_allelic_nonmax: bad arguments");
+    if (!counters || !assert_failed || (n_keys && (!ki || !kj || !kcnt || !nonmax)) || (n_groups && (!gptr || !gmem))) return fail("hhx_allelic_nonmax: null pointer");
+    counters[0] = counters[1] = counters[2] = 0;
+    *assert_failed = 0;
+    // ---- the groups (few and small: host work): checked, then turned round into the groups of every contig
+    int dmax = 0;
+    const i64 n_mem = n_groups ? gptr[n_groups] : 0;
+    if (n_groups && gptr[0] != 0) return fail("hhx_allelic_nonmax: gptr[0] must be 0");
+    for (i32 g = 0; g < n_groups; ++g) {
+        const i64 len = gptr[g + 1] - gptr[g];
+        if (len < 0 || gptr[g + 1] > INT32_MAX) return fail("hhx_allelic_nonmax: gptr must ascend and fit 32 bits");
+        if (len > NM_MAXD) { fail("hhx_allelic_nonmax: an allele group of %lld contigs is beyond the %d a lane solves in LDS", (long long)len, NM_MAXD); return HHX_UNSUPPORTED; }
+        dmax = std::max(dmax, (int)len);
+    }
+    for (i64 t = 0; t < n_mem; ++t)
+        if (gmem[t] < 0 || gmem[t] >= n_ctg) return fail("hhx_allelic_nonmax: group member %d is no contig id", (int)gmem[t]);
+    if (n_keys) memset(nonmax, 0, (size_t)n_keys);
+    if (n_keys == 0 || n_groups == 0 || n_mem == 0) return 0;
+    std::vector<i32> h_gptr((size_t)n_groups + 1), cg_ptr((size_t)n_ctg + 1, 0), cg_grp((size_t)n_mem);
+    for (i32 g = 0; g <= n_groups; ++g) h_gptr[g] = (i32)gptr[g];
+    for (i64 t = 0; t < n_mem; ++t) ++cg_ptr[gmem[t] + 1];
+    for (i32 c = 0; c < n_ctg; ++c) cg_ptr[c + 1] += cg_ptr[c];
+    {
+        std::vector<i32> fill(cg_ptr.begin(), cg_ptr.end() - 1);
+        for (i32 g = 0; g < n_groups; ++g)
+            for (i32 t = h_gptr[g]; t < h_gptr[g + 1]; ++t) cg_grp[fill[gmem[t]]++] = g;       // ascending group per contig
+    }
+    DevBuf<i32> d_ki, d_kj, d_gptr, d_gmem, d_cgp, d_cgg;
+    DevBuf<i64> d_cnt, combos, off;
+    DevBuf<unsigned long long> d_counters;
+    DevBuf<unsigned int> flags;
+    DevBuf<uint8_t> d_out;
+    const size_t n = (size_t)n_keys;
+    if (d_ki.alloc(n) || d_kj.alloc(n) || d_cnt.alloc(n) || combos.alloc(n + 1) || off.alloc(n + 2) || d_gptr.alloc(h_gptr.size()) || d_gmem.alloc((size_t)n_mem) ||
+        d_cgp.alloc(cg_ptr.size()) || d_cgg.alloc(cg_grp.size()) || d_counters.alloc(3) || flags.alloc(2) || d_out.alloc(n)) return 1;
+    HHX_HIP(hipMemcpyAsync(d_ki.p, ki, sizeof(i32) * n, hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemcpyAsync(d_kj.p, kj, sizeof(i32) * n, hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemcpyAsync(d_cnt.p, kcnt, sizeof(i64) * n, hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemcpyAsync(d_gptr.p, h_gptr.data(), sizeof(i32) * h_gptr.size(), hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemcpyAsync(d_gmem.p, gmem, sizeof(i32) * (size_t)n_mem, hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemcpyAsync(d_cgp.p, cg_ptr.data(), sizeof(i32) * cg_ptr.size(), hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemcpyAsync(d_cgg.p, cg_grp.data(), sizeof(i32) * cg_grp.size(), hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemsetAsync(d_counters.p, 0, sizeof(unsigned long long) * 3, g_stream));
+    HHX_HIP(hipMemsetAsync(flags.p, 0, sizeof(unsigned int) * 2, g_stream));
+    HHX_HIP(hipMemsetAsync(d_out.p, 0, n, g_stream));
+    KTimer kt("allelic_nonmax");
+    // ---- 1) the combinations of every key: count, scan, expand
+    k_nonmax_count<<<nonmax_grid((u64)n_keys, 256), 256, 0, g_stream>>>(n_keys, d_ki.p, d_kj.p, n_ctg, d_cgp.p, combos.p, d_counters.p, flags.p);
+    HHX_LAUNCH_CHECK();
+    i64 n_combos = 0;
+    HHX_TRY(exclusive_scan_i64(combos.p, off.p, n_keys, &n_combos));
+    unsigned int hf[2] = {0, 0};
+    HHX_HIP(hipMemcpyAsync(hf, flags.p, sizeof hf, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    if (hf[1]) return fail("hhx_allelic_nonmax: a key names a contig outside [0, n_ctg)");
+    unsigned long long hc[3] = {0, 0, 0};
+    if (n_combos > 0) {
+        DevBuf<u64> skey, sval, okey, oval;
+        if (skey.alloc((size_t)n_combos) || sval.alloc((size_t)n_combos) || okey.alloc((size_t)n_combos) || oval.alloc((size_t)n_combos)) return 1;
+        k_nonmax_expand<<<nonmax_grid((u64)n_keys, 256), 256, 0, g_stream>>>(n_keys, d_ki.p, d_kj.p, off.p, d_cgp.p, d_cgg.p, d_gptr.p, d_gmem.p, (i64)n_groups,
+                                                                             skey.p, sval.p, flags.p);
+        HHX_LAUNCH_CHECK();
+        HHX_HIP(hipMemcpyAsync(hf, flags.p, sizeof hf, hipMemcpyDeviceToHost, g_stream));
+        HHX_HIP(hipStreamSynchronize(g_stream));
+        if (hf[0]) {                                             // an assert of :652-659 would fail: the caller lets the reference raise it
+            *assert_failed = 1;
+            HHX_HIP(hipMemcpyAsync(hc, d_counters.p, sizeof hc, hipMemcpyDeviceToHost, g_stream));
+            HHX_HIP(hipStreamSynchronize(g_stream));
+            counters[0] = (i64)hc[0];
+            return 0;
+        }
+        // ---- 2) by group pair: only the bits ga * nG + gb can have
+        int bits = 1;
+        while (bits < 64 && (((u64)n_groups * (u64)n_groups - 1) >> bits) != 0) ++bits;
+        HHX_TRY(stable_sort_pairs_u64(skey.p, okey.p, sval.p, oval.p, n_combos, bits));
+        // ---- 3) one worker per pair
+        k_nonmax_pairs<<<nonmax_grid((u64)n_combos, HHX_WAVE), HHX_WAVE, nonmax_lds_bytes(dmax), g_stream>>>(n_combos, okey.p, oval.p, d_cnt.p, (i64)n_groups, d_gptr.p,
+                                                                                                           dmax, d_out.p, d_counters.p);
+        HHX_LAUNCH_CHECK();
+        HHX_HIP(hipMemcpyAsync(nonmax, d_out.p, n, hipMemcpyDeviceToHost, g_stream));
+    }
+    HHX_HIP(hipMemcpyAsync(hc, d_counters.p, sizeof hc, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    for (int k = 0; k < 3; ++k) counters[k] = (i64)hc[k];
     return 0;
 }

@@ -493,8 +493,9 @@ int hhx_ingest_fetch_ht_order(hhx_ingest *h, int64_t *first);
 int hhx_ingest_keep_frag_pairs(hhx_ingest *h, int on);
 int hhx_ingest_fetch_frag_pairs(hhx_ingest *h, int64_t *n_pairs, int32_t *frag_i, int32_t *frag_j);
 
-/* --remove_allelic_links on the device tables (remove_allelic_HiC_links :474-692, haphic_amd/csrc/hhx_allelic.hip).  Both entries take a
- * finalized handle; a return value of HHX_UNSUPPORTED (hhx_last_error() says why) means "not served here, take the reference's loop" and
+/* --remove_allelic_links on the device tables (remove_allelic_HiC_links :474-692, haphic_amd/csrc/hhx_allelic.hip): stage 1 and the drop of
+ * the verdict on a finalized handle, stage 2 (hhx_allelic_nonmax, below them) on host arrays; only the allele groups (networkx cliques) are
+ * host code.  The two hhx_ingest_ entries take a finalized handle; a return value of HHX_UNSUPPORTED (hhx_last_error() says why) means "not served here, take the reference's loop" and
  * leaves the handle untouched.
  *
  * hhx_ingest_concordance: record_coord_pairs :454-465 + cal_concordance_ratio :419-428 as integers.  For every full_link_dict key, in dict
@@ -526,6 +527,25 @@ int hhx_ingest_concordance(hhx_ingest *h, int64_t max_read_pairs, int64_t min_re
                            int32_t *anti);
 int hhx_ingest_drop_links(hhx_ingest *h, const uint8_t *full_drop, const uint8_t *in_set, int64_t *n_full_left, int64_t *n_flank_left,
                           uint8_t *flank_dropped, uint8_t *remaining, int64_t *first_row);
+/* Stage 2 of the same function, the links between non-maximum matches :621-667, on plain host arrays (no handle; like hhx_group_link_sums).
+ *   ki, kj, kcnt [n_keys]: the keys of full_link_dict that survive stage 1, in dict order, as contig ids and counts;
+ *   gptr [n_groups + 1], gmem: the allele groups as contig ids, group index = rank of the group under the reference's comparison of name tuples
+ *   (tuple(sorted([group_1, group_2])) :644), members in tuple order (position = .index()).
+ * A key is a candidate when both contigs are in a group (:639); it yields one combination per (group of ctg_1) x (group of ctg_2); the matrix of
+ * a pair of groups (:552-568, degree = the longer group) is filled from the combinations of that pair, and a combination is a mismatch when the
+ * matrix has more than one non-zero cell and linear_sum_assignment(-matrix)[1][index_1] != index_2 (:661).  nonmax [n_keys]: 1 = some
+ * combination of the key mismatches.  counters [3]: candidates, distinct group pairs, pairs whose matrix has more than one non-zero cell.
+ * *assert_failed = 1: an `assert` of :652-659 would fail for some combination; nonmax is then unspecified.  The assignments are scipy's own,
+ * ties included: the solver restates scipy 1.15's shortest-augmenting-path method step by step in 64-bit integers (haphic_amd/allelic.py
+ * lsap_small is the same in Python).  One sort of the combinations by group pair, then one lane per pair with its matrix in LDS; groups of up
+ * to 8 contigs are served, a longer one returns HHX_UNSUPPORTED.  The passes are grid-stride; the environment variable HHX_NONMAX_GRID (read at
+ * every launch) caps their workgroups.
+ *
+ * hhx_lsap_small: that solver alone on n square problems: cost [n][d][d] int64 row-major (minimised; |sums of d costs| below 2^62),
+ * col4row [n][d], 1 <= d <= 8. */
+int hhx_allelic_nonmax(int64_t n_keys, const int32_t *ki, const int32_t *kj, const int64_t *kcnt, int32_t n_ctg, int32_t n_groups,
+                       const int64_t *gptr, const int32_t *gmem, uint8_t *nonmax, int64_t *counters, int32_t *assert_failed);
+int hhx_lsap_small(int64_t n, int32_t d, const int64_t *cost, int32_t *col4row);
 int hhx_ingest_destroy(hhx_ingest *h);
 
 /* Multi-GPU exchange step (ingest).  The aggregated table of a finalized handle, device
