@@ -25,6 +25,12 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              also hands a call back to the reference's function when the containers were already thawed, flank_link_dict is
                              empty, --remove_concentrated_links or ultra-long reads (--ul) are on, the log level is DEBUG (the per-key debug
                              lines), a contig is shorter than --nwindows bp, or --max_read_pairs exceeds 4096
+  --keep-reference-statistics  cluster only: leave output_statistics :2279-2478 (the *_statistics.txt files and statistics.pdf of every inflation) to the
+                             reference's per-contig loop over ctg_group_link_dict, which is rebuilt as Python dicts once per inflation.  Without the
+                             flag a one-rank job takes the per-contig numbers of all inflations from one device call on the frozen full_link_dict
+                             (haphic_amd/statistics.py) and writes the same bytes; under --gpus N > 1 or torchrun the reference's loop runs whatever
+                             the flag says.  The device path also hands the call back when full_link_dict was thawed or holds float values
+                             (--remove_concentrated_links, GFA phasing) or a contig has no RE site
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
@@ -82,6 +88,7 @@ def main(argv=None):
     device = int(_take(argv, '--device', True) or 0)
     keep_ingest = bool(_take(argv, '--keep-reference-ingest', False))
     keep_allelic = bool(_take(argv, '--keep-reference-allelic', False))
+    keep_statistics = bool(_take(argv, '--keep-reference-statistics', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
     scripts = _reference_scripts(ref)
     if stub:
@@ -120,7 +127,8 @@ def main(argv=None):
         S.run(S.parse_arguments(), 'HapHiC_sort.log')               # == HapHiC_sort.main() :962-967
         return 0
     import HapHiC_cluster as H                                      # the unmodified reference module
-    patch.patch_reference(H, ingest=not keep_ingest, allelic=not keep_allelic and ctx is None)      # the allelic seam: one-rank jobs only
+    patch.patch_reference(H, ingest=not keep_ingest, allelic=not keep_allelic and ctx is None,      # the allelic and statistics seams: one-rank jobs only
+                          statistics=not keep_statistics and ctx is None)
     sys.argv = ['haphic cluster'] + argv
     return ranks.run_rank(lambda: H.run(H.parse_arguments(), 'HapHiC_cluster.log'))      # == HapHiC_cluster.main() :2962-2967
 

@@ -148,6 +148,10 @@ SIGNATURES = {
     'hhx_allelic_nonmax': (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      c_i32p]),
     'hhx_lsap_small': (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    'hhx_ingest_group_stats': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    'hhx_group_stats': (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_ingest_link_matrix': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, c_i32p, c_vpp]),
     'hhx_ingest_table_device': (C.c_int, [C.c_void_p, C.c_int, c_i64p, c_vpp, c_vpp, c_vpp, c_vpp, c_vpp]),
     'hhx_ingest_push_table': (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -842,6 +846,37 @@ def group_link_sums(frag_i, frag_j, links, group, n_groups):
     return sums, first
 
 
+def _group_stats_args(group, n_groups, group_re, ctg_re):
+    grp = np.ascontiguousarray(group, np.int32)
+    if grp.ndim != 2:
+        raise ValueError('group_stats: group is [n_sets, n_ctg]')
+    ng = np.ascontiguousarray(n_groups, np.int32)
+    gre, cre = np.ascontiguousarray(group_re, np.int64), np.ascontiguousarray(ctg_re, np.int64)
+    if ng.shape != (grp.shape[0],) or cre.shape != (grp.shape[1],) or gre.shape != (int(ng.sum()),):
+        raise ValueError('group_stats: n_groups per set, group_re for all groups of all sets, ctg_re per contig')
+    out = (np.zeros(grp.shape, np.int32), np.zeros(grp.shape, np.int64), np.full(grp.shape, -1, np.int32), np.zeros(grp.shape, np.float64))
+    return grp, ng, gre, cre, out
+
+
+GROUP_STATS_UNSUPPORTED = 2       # HHX_UNSUPPORTED
+
+
+def group_stats(frag_i, frag_j, links, group, n_groups, group_re, ctg_re, sum_mode=0):
+    """hhx_group_stats — what output_statistics :2279-2478 keeps of ctg_group_link_dict, for every set (group assignment) at once: keys
+    (frag_i, frag_j, links) in dict order, group int32 [n_sets, n_ctg] (-1 = ungrouped), n_groups [n_sets], group_re = the sets' group_RE values
+    one set after the other, ctg_re [n_ctg].  Returns (n_cells, max_links, max_group, other_sum), each [n_sets, n_ctg] (include/haphic_hip.h),
+    or None when the library does not serve the call.  sum_mode 0: plain sum, 1: CPython >= 3.12's compensated sum()."""
+    fi, fj = np.ascontiguousarray(frag_i, np.int32), np.ascontiguousarray(frag_j, np.int32)
+    lk = np.ascontiguousarray(links, np.int64)
+    grp, ng, gre, cre, out = _group_stats_args(group, n_groups, group_re, ctg_re)
+    rc = load().hhx_group_stats(len(lk), ptr(fi), ptr(fj), ptr(lk), 0, grp.shape[1], grp.shape[0], ptr(grp), ptr(ng), ptr(gre), ptr(cre), int(sum_mode),
+                                *[ptr(a) for a in out])
+    if rc == GROUP_STATS_UNSUPPORTED:
+        return None
+    check(rc)
+    return out
+
+
 def allelic_nonmax(ki, kj, kcnt, n_ctg, gptr, gmem):
     """hhx_allelic_nonmax — the links between non-maximum matches :621-667: (mask uint8 [n_keys], counters int64 [3] = candidates, distinct group
     pairs, assignment problems), None when an `assert` of :652-659 would fail, NotImplemented when the library does not serve the call (an allele
@@ -1350,6 +1385,18 @@ class Ingest:
         self.n_full, self.n_flank = a.value, b.value
         self.first_row = first_row
         return self.n_full, self.n_flank, gone, remaining
+
+    def group_stats(self, group, n_groups, group_re, ctg_re, sum_mode=0):
+        """group_stats (above) on the contig-pair table of this handle as it is now (hhx_ingest_group_stats): the keys of full_link_dict never
+        leave the device.  group is [n_sets, n_ctg] over the contig ids of the handle.  None: not served."""
+        if self.n_full is None:
+            self.finalize()
+        grp, ng, gre, cre, out = _group_stats_args(group, n_groups, group_re, ctg_re)
+        rc = load().hhx_ingest_group_stats(self.h, grp.shape[0], ptr(grp), ptr(ng), ptr(gre), ptr(cre), int(sum_mode), *[ptr(a) for a in out])
+        if rc == self.UNSUPPORTED:
+            return None
+        check(rc)
+        return out
 
     def keep_frag_pairs(self, on=True):
         check(load().hhx_ingest_keep_frag_pairs(self.h, int(on)))

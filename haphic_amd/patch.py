@@ -6,7 +6,7 @@
 
 Nothing under /root/reference is edited; the reference resolves these names at call time through its
 module globals, so `setattr` on the module is all that is needed."""
-from . import allelic, cluster, correct
+from . import allelic, cluster, correct, statistics
 
 # seam -> (reference line, replacement)
 SEAMS = {
@@ -63,6 +63,12 @@ _NEEDS_ORIGINAL = ('detect_break_points', 'break_and_update_ctgs')
 ALLELIC_SEAMS = {
     'remove_allelic_HiC_links': ('HapHiC_cluster.py:474-692', allelic.remove_allelic_HiC_links),
 }
+# output_statistics on the device tables (haphic_amd/statistics.py).  OPT-IN for the same reason: the mirror takes the per-contig numbers of every
+# inflation from one call on the frozen full_link_dict's table; with the seam unbound the reference's function runs on the parse_link_dict seam above
+# (cluster.group_link_dict), which also stays bound underneath for the calls the mirror hands back.
+STATISTICS_SEAMS = {
+    'output_statistics': ('HapHiC_cluster.py:2279-2478', statistics.output_statistics),
+}
 
 
 # position of `dense_matrix` in the reference signatures: --dense_matrix (:2723) is the reference's own numpy mode, which
@@ -115,9 +121,10 @@ def _run_then_join(original):
     return run
 
 
-def patch_reference(H, ingest=True, matrix_build=True, allelic=False):
+def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics=False):
     """H: the imported reference module (HapHiC_cluster).  Returns {name: original} so the caller can undo.  allelic=True (together with
-    ingest): remove_allelic_HiC_links :474-692 is re-bound too (ALLELIC_SEAMS); `python -m haphic_amd cluster` asks for it on one-rank jobs."""
+    ingest): remove_allelic_HiC_links :474-692 is re-bound too (ALLELIC_SEAMS); `python -m haphic_amd cluster` asks for it on one-rank jobs.
+    statistics=True (together with ingest): output_statistics :2279-2478 likewise (STATISTICS_SEAMS)."""
     from . import _lib
     _lib.load()                          # fail loudly here if the HIP library is missing
     saved = {}
@@ -134,9 +141,11 @@ def patch_reference(H, ingest=True, matrix_build=True, allelic=False):
         seams.update(CORRECTION_SEAMS)
     if ingest and allelic:
         seams.update(ALLELIC_SEAMS)
+    if ingest and statistics:
+        seams.update(STATISTICS_SEAMS)
     for name, (_cite, fn) in seams.items():
         saved[name] = getattr(H, name, None)
-        if name in CONTAINER_SEAMS or name in _NEEDS_ORIGINAL or name in ALLELIC_SEAMS:
+        if name in CONTAINER_SEAMS or name in _NEEDS_ORIGINAL or name in ALLELIC_SEAMS or name in STATISTICS_SEAMS:
             fn = _with_original(fn, saved[name])
         setattr(H, name, _dense_dispatch(fn, saved[name], DENSE_ARG[name]) if name in DENSE_ARG else fn)
     if ingest and getattr(H, 'run', None) is not None:

@@ -70,7 +70,9 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * the two implementations sum in another order, so the blocks' x agrees within the spread the reference's bnewt shows under a permutation,
  * step counts equal); "plotnorm_chunk_cells" = cells per upload / apply chunk of hhx_plotnorm (default 2^24, at least 1: one row per chunk;
  * same bits); "sort_lds_shape" = the largest new shape whose re-aggregation of hhx_sort_graph_aggregate accumulates in LDS, clamped to [0, 192]
- * (default 192; 0: always global atomics; same bits).  value INT64_MIN: back to the default.  Unset knobs fall back to the
+ * (default 192; 0: always global atomics; same bits); "groupstats_lds_slots" = slots of the per-workgroup LDS table of hhx_group_stats /
+ * hhx_ingest_group_stats (40 bytes each), rounded down to a power of two in [16, 2048] (default 2048; a contig with more distinct groups than slots takes
+ * the table in HBM; same bits).  value INT64_MIN: back to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
 int hhx_profile_enable(int on);
@@ -546,6 +548,33 @@ int hhx_ingest_drop_links(hhx_ingest *h, const uint8_t *full_drop, const uint8_t
 int hhx_allelic_nonmax(int64_t n_keys, const int32_t *ki, const int32_t *kj, const int64_t *kcnt, int32_t n_ctg, int32_t n_groups,
                        const int64_t *gptr, const int32_t *gmem, uint8_t *nonmax, int64_t *counters, int32_t *assert_failed);
 int hhx_lsap_small(int64_t n, int32_t d, const int64_t *cost, int32_t *col4row);
+
+/* ---------------------------------------------------------------- output_statistics :2279-2478: the per-contig group statistics
+ * (haphic_amd/csrc/hhx_groupstats.hip; parse_link_dict :2252-2268, sorted :2365, cal_link_density :2271-2276, sum :2376).  One "set" is one
+ * group assignment (one inflation): group [n_sets][n_ctg] (host; -1 = 'ungrouped'), n_groups [n_sets], group_re = the sets' group_RE_dict
+ * values one set after the other (sum of n_groups entries), ctg_re [n_ctg].  Every key (ctg_i, ctg_j) of full_link_dict contributes
+ * (ctg_i, group[ctg_j], links, pos = 2k) and (ctg_j, group[ctg_i], links, pos = 2k + 1), k its dict position; a partner group of -1 is
+ * skipped.  The cells of a contig are its distinct groups with sum (int64, exact) and first (smallest pos), ordered by sum descending, then
+ * first ascending: the order of the reference's stable sorted(..., reverse=True).  Outputs (host, [n_sets][n_ctg]):
+ *   n_cells    number of cells (0: the contig is not in ctg_group_link_dict; max_group is -1 then)
+ *   max_links, max_group   the first cell
+ *   other_sum  the float64 sum of links / den over the other cells, den = group_re[g] when g is the contig's own group, else
+ *              group_re[g] + ctg_re - 1, the quotients added one by one in that order from 0.0.  sum_mode 0: the plain sum (CPython <= 3.11);
+ *              1: Neumaier's compensated sum with the final "add the compensation if it is non-zero and finite" of CPython >= 3.12's sum().
+ * The sums and denominators are converted to float64 before the division, which is Python's int / int while both stay below 2^53.  The last
+ * divisions of :2372-2381 (max_links / den, other_sum / (n_groups - 1), their ratio) are elementwise and left to the caller.
+ * The table is turned into a symmetric adjacency by contig once per call; one workgroup per (contig, set) accumulates the cells in LDS
+ * (hhx_tune "groupstats_lds_slots"), a contig with more distinct groups than slots is redone on a per-workgroup table in HBM.
+ * hhx_ingest_group_stats works on the contig-pair table of a finalized handle (the rows of hhx_ingest_table_device(h, 0, ...); a row whose
+ * full ordinal is UINT64_MAX is no key, e.g. after hhx_ingest_drop_links; pos = 2 * ordinal + side): nothing of the table crosses PCIe, the
+ * handle is only read.  hhx_group_stats takes the keys as arrays in dict order (host, or device with on_device), like hhx_group_link_sums.
+ * HHX_UNSUPPORTED (hhx_last_error() says why): a sum_mode other than 0 / 1, n_ctg * n_sets of 2^31 and more. */
+int hhx_ingest_group_stats(hhx_ingest *h, int32_t n_sets, const int32_t *group_host, const int32_t *n_groups, const int64_t *group_re_host,
+                           const int64_t *ctg_re_host, int sum_mode, int32_t *n_cells, int64_t *max_links, int32_t *max_group,
+                           double *other_sum);
+int hhx_group_stats(int64_t n_keys, const int32_t *frag_i, const int32_t *frag_j, const int64_t *links, int on_device, int32_t n_ctg,
+                    int32_t n_sets, const int32_t *group_host, const int32_t *n_groups, const int64_t *group_re_host,
+                    const int64_t *ctg_re_host, int sum_mode, int32_t *n_cells, int64_t *max_links, int32_t *max_group, double *other_sum);
 int hhx_ingest_destroy(hhx_ingest *h);
 
 /* Multi-GPU exchange step (ingest).  The aggregated table of a finalized handle, device

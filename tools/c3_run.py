@@ -8,6 +8,8 @@
 
 The reference module does not exist on the GPU box, so run()'s own glue (argparse, logging set-up), parse_fasta (the assembly is synthetic: fa_dict is
 synthesised in the shape parse_fasta returns) and output_statistics :2279 are not part of the figure (tools/c1_run.py says the same for C1).
+output_statistics runs as a leg of its own after whole_job_s (haphic_amd/statistics.py on the still-frozen full_link_dict; --no-statistics leaves it out):
+output_statistics_s, and whole_job_with_statistics_s = the figure with the step in it.
 The `.pairs` text itself is produced beforehand, untimed, from the synthetic read pairs in HBM (hhx_pairs_format) — the same model and seeds bench.py samples.
 
     python tools/c3_run.py [--contigs 100000] [--pairs 500000000] [--dir /dev/shm] [--keep]          one JSON object on stdout
@@ -114,7 +116,7 @@ def write_pairs_file(path, gen, id1, p1, id2, p2, slice_pairs=16_000_000, writer
     return at, n
 
 
-def run_sequence(pairs_path, gen, nchrs, workdir, sweep=True, log=None):
+def run_sequence(pairs_path, gen, nchrs, workdir, sweep=True, log=None, statistics=False):
     """the seam sequence of run() :2829-2945 in `workdir`; returns the per-stage wall clocks and what was written"""
     import logging
     from haphic_amd import _lib, cluster
@@ -208,6 +210,16 @@ def run_sequence(pairs_path, gen, nchrs, workdir, sweep=True, log=None):
         out['timeline_s_filesqueued_freeGB'] = timeline[::4] if len(timeline) > 40 else timeline[::2]
         t['whole_job_s'] = time.perf_counter() - t0
         out['files_still_queued_when_the_clustering_ended'] = pend_at_end
+        if statistics and sweep and res:
+            # output_statistics :2279 (called at :2956, the last step of run()) on the still-frozen full_link_dict: haphic_amd/statistics.py.  A leg of its
+            # own after whole_job_s, which keeps its meaning; whole_job_with_statistics_s is the figure that leaves nothing of run() out
+            from haphic_amd import statistics as stats_mirror
+            ts = time.perf_counter()
+            stats_mirror.output_statistics(fa_dict, full, res)
+            t['output_statistics_s'] = time.perf_counter() - ts
+            t['whole_job_with_statistics_s'] = time.perf_counter() - t0
+            out['output_statistics_split_s'] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in stats_mirror.STATS.items()}
+            out['full_link_dict_frozen_after_the_statistics'] = bool(full.frozen)
         del full
         out['files'] = {f: os.path.getsize(f) for f in ('HT_links.pkl', 'paired_links.clm', 'full_links.pkl', 'alignments.bed') if os.path.exists(f)}
         out['inflation_dirs'] = len([d for d in os.listdir('.') if d.startswith('inflation_')])
@@ -219,7 +231,8 @@ def run_sequence(pairs_path, gen, nchrs, workdir, sweep=True, log=None):
         lg.setLevel(level)
 
 
-def run_job(contigs=100000, pairs=500_000_000, nchrs=24, mean_len=30_000, where=None, keep=False, sweep=True, device='cuda:0', arrays=None, gen=None):
+def run_job(contigs=100000, pairs=500_000_000, nchrs=24, mean_len=30_000, where=None, keep=False, sweep=True, device='cuda:0', arrays=None, gen=None,
+            statistics=False):
     """generate the .pairs file (untimed), run the sequence, clean up.  arrays: (id1, p1, id2, p2) torch tensors already on the device (bench.py)"""
     import torch
     from haphic_amd import _lib, synth
@@ -256,7 +269,7 @@ def run_job(contigs=100000, pairs=500_000_000, nchrs=24, mean_len=30_000, where=
         torch.cuda.empty_cache()
         gen_s = time.perf_counter() - tg
         os.makedirs(os.path.join(d, 'run'))
-        out = run_sequence(path, gen, nchrs, os.path.join(d, 'run'), sweep=sweep)
+        out = run_sequence(path, gen, nchrs, os.path.join(d, 'run'), sweep=sweep, statistics=statistics)
         s = out['seconds']
         out.update(contigs=int(gen.n), pairs=int(lines), pairs_file_bytes=int(size), directory=where, pairs_file_written_in_s_untimed=gen_s,
                    pairs_per_s_link_matrix_ready=lines / s['link_matrix_ready_s'], pairs_text_GBs=size / s['pairs_text_to_containers_s'] / 1e9,
@@ -264,7 +277,8 @@ def run_job(contigs=100000, pairs=500_000_000, nchrs=24, mean_len=30_000, where=
                    what='run() :2829-2945 through haphic_amd.cluster from the .pairs FILE on one MI355X: stat_fragments -> pairs_generator_inter_ctgs (+ alignments.bed) -> '
                         'parse_alignments_for_ctgs -> output_pickle(HT) -> output_clm -> filter_fragments -> output_pickle(full) -> dict_to_matrix [link_matrix_ready_s] -> '
                         'run_mcl_clustering (20 inflations, every file written) -> files joined [whole_job_s]; the three writers only queue their file '
-                        '(library thread), *_call_s is what the caller waits; fa_dict synthesised (no FASTA), output_statistics :2279 not included')
+                        '(library thread), *_call_s is what the caller waits; fa_dict synthesised (no FASTA), output_statistics :2279 not included in whole_job_s: '
+                        'output_statistics_s / whole_job_with_statistics_s when the leg was asked for')
         try:
             with open('/sys/fs/cgroup/memory.peak') as f:
                 out['cgroup_memory_peak'] = int(f.read())
@@ -285,13 +299,14 @@ def main():
     ap.add_argument('--dir', default=None, help='where the .pairs file and the run directory go (default: /dev/shm if the memory cgroup has the room, else the temporary directory)')
     ap.add_argument('--no-sweep', action='store_true', help='stop when the link matrix is ready (--skip_clustering :2943)')
     ap.add_argument('--keep', action='store_true')
+    ap.add_argument('--no-statistics', action='store_true', help='leave out the output_statistics leg (:2279, haphic_amd/statistics.py) that follows the sweep')
     ap.add_argument('--sync-files', action='store_true', help='HAPHIC_SYNC_FILES=1: the three writers on the caller\'s thread, as before round 6')
     args = ap.parse_args()
     if args.sync_files:
         os.environ['HAPHIC_SYNC_FILES'] = '1'
     from haphic_amd import _lib
     _lib.check(_lib.load().hhx_set_device(0))
-    out = run_job(args.contigs, args.pairs, args.nchrs, args.mean_len, where=args.dir, keep=args.keep, sweep=not args.no_sweep)
+    out = run_job(args.contigs, args.pairs, args.nchrs, args.mean_len, where=args.dir, keep=args.keep, sweep=not args.no_sweep, statistics=not args.no_statistics)
     print(json.dumps(out))
 
 
