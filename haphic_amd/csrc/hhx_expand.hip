@@ -19,8 +19,10 @@
 // (q = float(p / S) >= float32(pruning), first row maximum restored, second L1 normalisation) and the
 // survivors are bump-allocated; a final pass packs the rows into CSR order.
 #include <chrono>
+#include <climits>
 
 #include "hhx_common.h"
+#include "hhx_internal.h"
 #include "hhx_sort.h"
 
 using namespace hhx;
@@ -30,9 +32,6 @@ struct ExpandDemand { i64 out = 0, cand = 0; };
 thread_local ExpandDemand g_expand_hint, g_expand_demand;
 void hhx_expand_set_hint(i64 out, i64 cand) { g_expand_hint.out = out; g_expand_hint.cand = cand; }
 void hhx_expand_last_demand(i64 *out, i64 *cand) { *out = g_expand_demand.out; *cand = g_expand_demand.cand; }
-
-int hhx_csr_alloc_internal(i32 n_rows, i32 n_cols, i64 nnz, hhx_csr **out);
-namespace hhx { i64 pool_cached_bytes(); }
 
 namespace {
 
@@ -2353,445 +2352,591 @@ static int pack_rows_to_csr(i32 n_rows, i32 n_cols, const i32 *row_cnt, i32 *ind
     return 0;
 }
 
-int hhx_expand_impl(const hhx_csr *a, const hhx_csr *b, const CodedOperand &coded, int fx_shift, double inflation, double pruning,
-                    hhx_csr **out, i64 *n_products, i64 *nnz_expanded) {
-    const bool dense = coded.dense_out != nullptr;
-    if (!a || !b || (!out && !dense)) return fail("null pointer");
+// ---- the kernel shapes of the window class: one table per family.  A shape is added or removed by its row here (and its tests) ------
+typedef int (*WindowLauncher)(const ExParams &P, const i32 *rows, i32 n_list, i32 cap, size_t lds, unsigned grid);
+typedef int (*GroupLauncher)(const ExParams &P, const GroupOp &op, i32 cap, size_t lds, unsigned grid);
+
+// block tiles (pass_blocks), tune "block_tiles": the value of the knob -> (UX, G, AM)
+struct BlockTileShape { int selector; WindowLauncher launch; };
+#define HHX_BLK(UXV, GV, AMV) launch_window_fx<0, UXV, GV, AMV, false, EX_T_WIN, true>
+static const BlockTileShape k_block_tile_shapes[] = {
+    {15, HHX_BLK(4, 5, 1)},         // groups of 20 blocks, one 32-bit offset per block
+    {5, HHX_BLK(4, 5, 0)},          // ... a scalar base per block (streams of 2^30 slots and more)
+    {11, HHX_BLK(4, 4, 1)},         // measured beside them (C3 tail at 1.1: 5.06 / 5.15 / 5.23 s against 5.01 / 5.17 s; tiles per segment: 5.81 s)
+    {1, HHX_BLK(4, 4, 0)},
+    {31, HHX_BLK(4, 4, 3)},         // the loads written by hand (no VALU instruction for an address): 4.92 s — 1.7 % for loads the compiler cannot see: not the default
+    {2, HHX_BLK(8, 3, 0)},
+};
+#undef HHX_BLK
+// tiles per segment: UX x 64 entries per explicit tile -> (UX, RX).  ux >= 8 takes the first row, a ux that is not listed the last one
+struct SegmentTileShape { int ux; WindowLauncher launch; };
+static const SegmentTileShape k_segment_tile_shapes[] = {
+    {8, launch_window<0, 8, 3, 3>}, {4, launch_window<0, 4, 4, 3>}, {3, launch_window<0, 3, 8, 3>}, {2, launch_window<0, 2, 8, 3>}, {1, launch_window<0, 1, 8, 3>},
+};
+// re-use kernel: R rows per group x the tile -> (R, UX, G); the first row of its R whose ux_min the tile reaches
+struct GroupShape { int R, ux_min; GroupLauncher launch; };
+static const GroupShape k_group_shapes[] = {
+    {4, 4, launch_group<4, 4, 4>}, {4, 2, launch_group<4, 2, 8>}, {4, INT_MIN, launch_group<4, 1, 8>},
+    {2, 4, launch_group<2, 4, 4>}, {2, 2, launch_group<2, 2, 8>}, {2, INT_MIN, launch_group<2, 1, 8>},
+};
+
+// the launcher of the one-row-per-workgroup window kernel for this call; nullptr: block_tiles names no shape
+static WindowLauncher pick_window_shape(int block_tiles, int ux) {
+#ifdef HHX_PROBE_BUILD              // measurement build only (-DHHX_PROBE_BUILD): the atomics switched off, results are garbage
+    if (tune_get("probe", 0) == 1) return ux >= 4 ? launch_window<1, 8, 3, 3> : launch_window<1, 3, 8, 3>;
+#endif
+    if (block_tiles) {
+        for (const BlockTileShape &s : k_block_tile_shapes) if (s.selector == block_tiles) return s.launch;
+        return nullptr;
+    }
+    for (const SegmentTileShape &s : k_segment_tile_shapes) if (s.ux == std::min(ux, 8)) return s.launch;
+    return std::end(k_segment_tile_shapes)[-1].launch;
+}
+static GroupLauncher pick_group_shape(int R, int ux) {
+    for (const GroupShape &s : k_group_shapes) if (s.R == R && ux >= s.ux_min) return s.launch;
+    return nullptr;
+}
+
+// ---- the host driver of the fused iteration: a plan, the builds a call makes once, one step per row class, the report -----------------
+namespace {
+
+static bool expand_debug() {
+    static const bool debug = getenv("HHX_DEBUG") != nullptr;
+    return debug;
+}
+
+// The per-row table and the candidate / survivor pools (col, value) of one expansion or of one inflation of a dense epilogue pass.
+// How large the pools start and how they grow after an overflow stays with each driver (hhx_expand_impl; DenseInfl below): the two
+// differ on purpose.
+struct RowPools {
+    DevBuf<i32> row_cnt, indptr, g_win_cnt, cand_col, out_col;
+    DevBuf<i64> row_off, g_win_off;
+    DevBuf<float> cand_val, out_val;
+    DevBuf<double> s_run;
+    DevBuf<unsigned long long> cursors;
+    i64 pool_cap = 0, cand_cap = 0;
+    int alloc_table(i32 n_rows, i32 n_win) {       // n_win: the most column windows a launch of the call may use
+        return row_cnt.alloc((size_t)n_rows + 1) || indptr.alloc((size_t)n_rows + 1) || row_off.alloc((size_t)n_rows + 1) || cursors.alloc(12) ||
+               s_run.alloc((size_t)n_rows + 1) || g_win_off.alloc((size_t)n_rows * n_win + 1) || g_win_cnt.alloc((size_t)n_rows * n_win + 1);
+    }
+    int alloc_pools() {                 // (the pools of an overflowed attempt go back first: the new ones may take their blocks)
+        release_pools();
+        return cand_col.alloc((size_t)cand_cap) || cand_val.alloc((size_t)cand_cap) || out_col.alloc((size_t)pool_cap) || out_val.alloc((size_t)pool_cap);
+    }
+    void release_pools() { cand_col.release(); cand_val.release(); out_col.release(); out_val.release(); }
+    int zero_cursors() {
+        HHX_HIP(hipMemsetAsync(cursors.p, 0, 12 * sizeof(unsigned long long), g_stream));
+        return 0;
+    }
+    void fill(ExParams &P) const {
+        P.cand_col = cand_col.p; P.cand_val = cand_val.p; P.cand_cap = cand_cap;
+        P.out_col = out_col.p; P.out_val = out_val.p; P.out_cap = pool_cap;
+        P.cursors = cursors.p; P.row_off = row_off.p; P.row_cnt = row_cnt.p;
+        P.s_run = s_run.p; P.g_win_off = g_win_off.p; P.g_win_cnt = g_win_cnt.p;
+    }
+};
+
+// What a call settles from its arguments and its knobs alone, once, before anything is launched
+struct ExPlan {
+    bool dense;                         // the rows go to coded.dense_out as float32; no CSR result (the inflation sweep)
+    bool raw;                           // plain product (hhx_spgemm's fast path)
+    bool use_cls;                       // the right operand is streamed regrouped by link count (the class stream)
+    bool fx;                            // ... and in the integer arithmetic of the link matrix: every row through the window class
+    bool sym_whole;                     // symmetric mode over all rows: the mirror image is written here too
+    bool all_window;                    // every row takes the window class
+    bool self;                          // a == b (an iteration of mcl()): the rows of the window class may be grouped / ordered by their patterns
+    int fx_shift;
+    i32 n_rows, n_cols, W;              // W: 32-bit words of a bitmap of the columns
+    i32 n_classes;                      // link counts 1..n_classes are streamed as columns only
+    i32 cap_win, n_win; size_t lds_win; // window class: columns per window, windows, dynamic LDS
+    i32 cap_cmp; size_t lds_cmp;        // compact class: accumulators per rank window, dynamic LDS
+    size_t lds_hash; bool hash_fits; i64 hash_max;      // hash class: rows of at most hash_max products (0: off, -1: no class but the window class)
+    i64 window_min;                     // window class: rows of at least this many products
+    int reuse_R; i32 cap_g, n_win_g;    // re-use kernel: rows per group (0: off) and its column-window plan
+    i32 n_win_tab;                      // windows per row of the (row, window) table: the larger of the two plans
+};
+
+static int expand_plan(const hhx_csr *a, const hhx_csr *b, const CodedOperand &coded, hhx_csr **out, double inflation, int fx_shift, ExPlan &pl) {
+    pl.dense = coded.dense_out != nullptr;
+    if (!a || !b || (!out && !pl.dense)) return fail("null pointer");
     if (a->n_cols != b->n_rows) return fail("expand shape mismatch");
     if (!(inflation > 0)) return fail("inflation must be positive");
     if (b->nnz > (i64)INT32_MAX - 4096) return fail("expand: right operand has %lld entries; the tile cursors need 4096 below 2^31", (long long)b->nnz);
-    if (fx_shift < 0 || fx_shift > 52) fx_shift = 52;        // the exact-double accumulation holds 52 fractional bits
-    const auto t_enter = std::chrono::steady_clock::now();
-    const i32 n_rows = a->n_rows, n_cols = b->n_cols;
-    const i32 W = (n_cols + 31) / 32;
-    // ---- plans
-    const bool use_cls = coded.n16 != nullptr && !coded.raw && tune_get("cls", 1) != 0;
-    const bool fx = use_cls && coded.W != nullptr;           // integer arithmetic of the link matrix: every row through the window class
-    if (coded.W && !fx) return fail("expand: the integer arithmetic needs the class stream");
-    if (coded.sym && !(dense && fx)) return fail("expand: the symmetric mode needs the dense integer mode");
-    const bool sym_whole = coded.sym && a->n_rows == b->n_rows;          // all rows here: the mirror image is written here too
+    pl.fx_shift = (fx_shift < 0 || fx_shift > 52) ? 52 : fx_shift;       // the exact-double accumulation holds 52 fractional bits
+    pl.raw = coded.raw != 0;
+    pl.self = a == b;
+    const i32 n_cols = pl.n_cols = b->n_cols;
+    pl.n_rows = a->n_rows;
+    pl.W = (n_cols + 31) / 32;
+    pl.use_cls = coded.n16 != nullptr && !coded.raw && tune_get("cls", 1) != 0;
+    pl.fx = pl.use_cls && coded.W != nullptr;           // integer arithmetic of the link matrix: every row through the window class
+    if (coded.W && !pl.fx) return fail("expand: the integer arithmetic needs the class stream");
+    if (coded.sym && !(pl.dense && pl.fx)) return fail("expand: the symmetric mode needs the dense integer mode");
+    pl.sym_whole = coded.sym && a->n_rows == b->n_rows;          // all rows here: the mirror image is written here too
     // link counts 1..n_classes are streamed as columns only.  Measured at n = 100k (profiles/r02_expand_probe_c3.jsonl): counts 1-3
     // move 17 % fewer bytes than count 1 alone but run 20 % longer (the count-2 / count-3 sub-segments are a few dozen entries:
     // tiles of 128 that are mostly empty), so the default is 1
-    const i32 n_classes = fx ? 1 : (i32)std::min<i64>(3, std::max<i64>(1, tune_get("cls_nc", 1)));
-    const size_t fixed_win = win_fixed_bytes(), fixed_cmp = ex_fixed_bytes(W, MAX_WIN);
+    pl.n_classes = pl.fx ? 1 : (i32)std::min<i64>(3, std::max<i64>(1, tune_get("cls_nc", 1)));
+    const size_t fixed_win = win_fixed_bytes(), fixed_cmp = ex_fixed_bytes(pl.W, MAX_WIN);
     // window class: the column window must fit LDS (8 B per column).  Measured on MI355X (n = 100k, 330M
     // entries): the fewest, widest windows win — 6 windows 1.41 s, 13 windows 1.54 s, 27 windows 2.24 s —
     // because the per-segment cost grows faster than the Infinity Cache hit rate of a narrower column slice
     // B[:, w].  tune "cache_slice_mb" (MB of B per slice) forces more windows for experiments.
-    i32 cap_win = 0, n_win = 0;
-    window_plan(n_cols, b->nnz, &cap_win, &n_win);
+    window_plan(n_cols, b->nnz, &pl.cap_win, &pl.n_win);
     if (coded.tri && !(coded.sym && a->n_rows == b->n_rows && coded.sym_row0 == 0)) return fail("expand: the triangle storage needs the symmetric mode over all rows");
     size_t budget_cmp = 64 * 1024;
     if (fixed_cmp + 2048 * 8 > budget_cmp) budget_cmp = 160 * 1024;
     if (fixed_cmp + 1024 * 8 > budget_cmp) return fail("expand: %d columns exceed the LDS bitmap capacity", n_cols);
-    const i32 cap_cmp = (i32)((budget_cmp - fixed_cmp) / 8) & ~63;
-    if (n_cols / 2 / cap_cmp + 2 > MAX_WIN - 1) return fail("expand: %d columns need too many LDS rank windows", n_cols);
-    const size_t lds_win = (size_t)cap_win * 8 + fixed_win, lds_cmp = (size_t)cap_cmp * 8 + fixed_cmp;
-    HHX_TRY((raise_dynamic_lds<k_expand_compact>()));
-    static const bool debug = getenv("HHX_DEBUG") != nullptr;
-    const int probe = (int)tune_get("probe", 0);
-    (void)probe;
+    pl.cap_cmp = (i32)((budget_cmp - fixed_cmp) / 8) & ~63;
+    if (n_cols / 2 / pl.cap_cmp + 2 > MAX_WIN - 1) return fail("expand: %d columns need too many LDS rank windows", n_cols);
+    pl.lds_win = (size_t)pl.cap_win * 8 + fixed_win;
+    pl.lds_cmp = (size_t)pl.cap_cmp * 8 + fixed_cmp;
     // rows whose product count is well above the number of accumulator slots a dense sweep touches
     static const double wfac = getenv("HHX_WINDOW_FACTOR") ? atof(getenv("HHX_WINDOW_FACTOR")) : 0.5;
-    const bool all_window = dense || fx;
-    const i64 window_min = all_window ? 0 : std::max<i64>(4096, (i64)((double)n_cols * wfac));
-    DevBuf<i32> list_w, list_c, list_t, list_h, row_cnt, indptr, g_win_cnt;
-    DevBuf<i64> row_off, g_win_off, row_f;
+    pl.all_window = pl.dense || pl.fx;
+    pl.window_min = pl.all_window ? 0 : std::max<i64>(4096, (i64)((double)n_cols * wfac));
     // hash class: rows of at most hash_max products (tune "hash_max", 0 = off); needs the bitmap next to a 64 KB table
-    const size_t lds_hash = hash_lds_bytes(W);
+    pl.lds_hash = hash_lds_bytes(pl.W);
     // off when B's rows are longer than the table can hold distinct columns anyway (iteration 0: the link matrix itself)
-    const bool hash_fits = lds_hash <= 160 * 1024 && b->n_rows > 0 && b->nnz / b->n_rows <= HASH_LIMIT / 2;
+    pl.hash_fits = pl.lds_hash <= 160 * 1024 && b->n_rows > 0 && b->nnz / b->n_rows <= HASH_LIMIT / 2;
     // ... and only for rows the window class would not serve faster.  Measured on the tails of the low inflations at n = 100k
     // (profiles/r04_tail_probe.jsonl): the hash kernel walks 3.4-5.3e11 products/s whatever the row, the window kernel 1.1e12 /s plus
     // ~0.6 us per row of sweeping its n accumulators — the hash class wins below ~4.5 n products per row, not up to 4 M
     // (at inflation 1.3, iterations 3-6: 312 ms through the hash class for 1.1e11 products that the window class walks in ~160)
     const i64 hash_dflt = std::min<i64>(4000000, std::max<i64>(65536, (i64)(4.5 * (double)n_cols)));
-    const i64 hash_max = all_window ? -1 : (hash_fits ? std::max<i64>(0, tune_get("hash_max", hash_dflt)) : 0);
-    DevBuf<int2> bjx;
-    DevBuf<double> s_run;
-    DevBuf<unsigned int> counts;
-    DevBuf<unsigned long long> cursors;
+    pl.hash_max = pl.all_window ? -1 : (pl.hash_fits ? std::max<i64>(0, tune_get("hash_max", hash_dflt)) : 0);
     // re-use of B rows across output rows (k_expand_group): R rows of one attractor per workgroup, column windows R times narrower.
     // Generic stream only (iterations >= 1 of mcl(), hhx_spgemm excluded); tune "reuse": 0 off (the default), 2 or 4 rows per group.
     // OFF by default: measured (tools/lowtails.py --reuse-ab, profiles/r05_lowtails_reuse.jsonl) it streams 3.5-3.9 x fewer bytes, gives
     // the same bits, and is no faster — the per-product path of distinct 64-bit addends caps at ~1.1e12 products/s, the rate the
     // fabric-bound one-row kernel already reaches
-    int reuse_R = (!use_cls && !dense && !coded.raw && a == b) ? (int)tune_get("reuse", 0) : 0;
-    if (reuse_R != 2 && reuse_R != 4) reuse_R = 0;
-    i32 cap_g = 0, n_win_g = 0;
-    if (reuse_R) {
+    pl.reuse_R = (!pl.use_cls && !pl.dense && !pl.raw && pl.self) ? (int)tune_get("reuse", 0) : 0;
+    if (pl.reuse_R != 2 && pl.reuse_R != 4) pl.reuse_R = 0;
+    pl.cap_g = 0; pl.n_win_g = 0;
+    if (pl.reuse_R) {
         static_assert(win_fixed_bytes() == 784, "GroupStride assumes the window kernel's fixed LDS bytes");
-        const i32 cols_max = (reuse_R == 4 ? GroupStride<4>::value : GroupStride<2>::value) - N_DUMMY;      // columns of a member's window
+        const i32 cols_max = (pl.reuse_R == 4 ? GroupStride<4>::value : GroupStride<2>::value) - N_DUMMY;      // columns of a member's window
         for (i64 wn = std::max<i64>(1, ((i64)n_cols + cols_max - 1) / cols_max);; ++wn) {
             const i32 c = (i32)((((i64)n_cols + wn - 1) / wn + 63) & ~63);
-            if (c <= cols_max) { cap_g = c; n_win_g = (n_cols + c - 1) / c; break; }
+            if (c <= cols_max) { pl.cap_g = c; pl.n_win_g = (n_cols + c - 1) / c; break; }
         }
-        if (cap_g < 1024) reuse_R = 0;                      // windows too narrow to be worth a launch each
+        if (pl.cap_g < 1024) pl.reuse_R = 0;                // windows too narrow to be worth a launch each
     }
-    const i32 n_win_tab = std::max(n_win, n_win_g);
-    if (list_w.alloc((size_t)n_rows + 1) || list_c.alloc((size_t)n_rows + 1) || list_t.alloc((size_t)n_rows + 1) ||
-        list_h.alloc((size_t)n_rows + 1) || row_f.alloc((size_t)n_rows + 1) || row_cnt.alloc((size_t)n_rows + 1) ||
-        indptr.alloc((size_t)n_rows + 1) || row_off.alloc((size_t)n_rows + 1) || counts.alloc(4) || cursors.alloc(12) ||
-        s_run.alloc((size_t)n_rows + 1) || g_win_off.alloc((size_t)n_rows * n_win_tab + 1) || g_win_cnt.alloc((size_t)n_rows * n_win_tab + 1))
-        return 1;
-    DevBuf<i32> grp_rows, Gp, Gj;
-    DevBuf<float> Gx;
-    i32 n_groups = 0;
-    i64 group_entries = 0;              // entries of the union rows
-    // Rows of the window class in the order of (min-hash of the pattern, row) — tune "row_order", 1 unless switched off.  The rows a launch has in flight together (one per
-    // workgroup, 256 at a time) then walk largely the SAME rows of B, which they find in the Infinity Cache instead of HBM: the heavy iterations of a low-inflation tail
-    // run at 1.31-1.37e12 products/s instead of 1.15-1.18e12 (C3, inflation 1.1: 7.39 -> 6.74 s).  The order of the rows changes no bit of the result.
-    auto order_rows = [&](DevBuf<i32> &list, i64 nl) -> int {
-        if (dense || coded.raw || a != b || !tune_get("row_order", 1)) return 0;
-        KTimer kt("row_order");
-        DevBuf<u64> key, val, skey, sval;
-        if (key.alloc((size_t)nl) || val.alloc((size_t)nl) || skey.alloc((size_t)nl) || sval.alloc((size_t)nl)) return 1;
-        k_row_minhash<<<(unsigned)std::min<i64>((nl + 3) / 4, 4096), 256, 0, g_stream>>>((i32)nl, list.p, a->indptr.p, a->indices.p, key.p, val.p);
+    pl.n_win_tab = std::max(pl.n_win, pl.n_win_g);
+    if (pl.cap_win + N_DUMMY > 65536) return fail("expand: column window wider than 16 bits");
+    return 0;
+}
+
+// The pools of the first attempt.  Candidate pool: early windows test against a partial row sum and admit more than finally survive.
+// Inside mcl()'s loop (hhx_mcl.hip) the iteration before says what this one will need: its demand + 50 % instead of 4 and 8 entries per entry of
+// A.  The guess made the tail at inflation 1.1 of a 100k-contig matrix ask for 22 GB of pools per iteration, of sizes that change every
+// iteration — 67-97 GB of FRESH device memory per tail, 1.2-1.8 s of its 7.4 s on the caller's thread (tools/tail_alloc_probe.py,
+// profiles/r06_tail_alloc_probe.json).  An overflow costs one retry of the iteration with the exact demand, as before.
+// (The plain product sizes its pools from the product count instead: hhx_expand_impl.)
+static void expand_pool_sizes(const ExPlan &pl, const hhx_csr *a, RowPools &tab) {
+    tab.pool_cap = pl.dense ? 64 : std::max<i64>(4 * a->nnz + 16 * (i64)pl.n_rows, (i64)1 << 22);
+    tab.cand_cap = pl.dense ? 64 : (pl.n_win > 1 ? 2 * tab.pool_cap : tab.pool_cap);
+    if (pl.dense || pl.raw) return;
+    if (g_expand_hint.out > 0) {
+        tab.pool_cap = std::max<i64>(g_expand_hint.out + g_expand_hint.out / 2 + 16 * (i64)pl.n_rows, (i64)1 << 22);
+        tab.cand_cap = std::max<i64>(g_expand_hint.cand + g_expand_hint.cand / 2 + 16 * (i64)pl.n_rows, (i64)1 << 22);
+    }
+    g_expand_hint = ExpandDemand();
+}
+
+// what every launch of a call shares; the pools (RowPools::fill) and the operand stream are set per attempt
+static ExParams expand_params(const ExPlan &pl, const hhx_csr *a, const hhx_csr *b, const CodedOperand &coded, double inflation, double pruning) {
+    ExParams P;
+    memset(&P, 0, sizeof P);
+    P.Ap = a->indptr.p; P.Aj = a->indices.p; P.Ax = a->data.p;
+    P.Bp = b->indptr.p; P.Bj = b->indices.p; P.Bx = b->data.p;
+    P.n_rows = pl.n_rows; P.n_cols = pl.n_cols;
+    P.scale = ldexp(1.0, pl.fx_shift - 52); P.inv_scale = ldexp(1.0, 52 - pl.fx_shift);
+    P.r = (double)(float)inflation; P.square = inflation == 2.0; P.thr = (float)pruning;
+    P.raw = coded.raw;
+    P.n_win = pl.n_win;
+    P.dense = coded.dense_out; P.dense_ld = coded.dense_ld ? coded.dense_ld : (i64)pl.n_cols;
+    P.W = pl.fx ? coded.W : nullptr; P.A16 = coded.a16; P.row_div = coded.a_row_sum; P.fx_inv = ldexp(1.0, -coded.shift);
+    P.sym = coded.sym; P.sym_row0 = coded.sym_row0;
+    P.tri = coded.tri; P.tri_ldn = (i64)pl.n_win * pl.cap_win;
+    P.Sc16 = nullptr; P.Sx = nullptr; P.rec = nullptr; P.Bjx = nullptr; P.narrow_classes = 0; P.wb = WB_MAX;
+    return P;
+}
+
+// ---- classification: the rows of a by class
+struct RowLists {
+    DevBuf<i32> w, c, t, h;             // rows of the window / compact / tiny / hash class (the hash kernel hands rows on to w and c)
+    DevBuf<i64> row_f;                  // products of every row
+    DevBuf<unsigned int> counts;        // [4] rows per class, in that order
+    int alloc(i32 n_rows) {
+        return w.alloc((size_t)n_rows + 1) || c.alloc((size_t)n_rows + 1) || t.alloc((size_t)n_rows + 1) || h.alloc((size_t)n_rows + 1) ||
+               row_f.alloc((size_t)n_rows + 1) || counts.alloc(4);
+    }
+};
+struct ClassCounts {
+    unsigned int classified[4];         // rows per class as k_classify decided, before the hash kernel hands rows back
+    unsigned int hc[4];                 // rows per class now: window, compact, tiny, hash
+    unsigned long long hw[2];           // products / A entries of the window class
+};
+static int read_class_counts(const RowLists &L, const RowPools &tab, ClassCounts &cc) {
+    HHX_HIP(hipMemcpyAsync(cc.hc, L.counts.p, sizeof cc.hc, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipMemcpyAsync(cc.hw, tab.cursors.p + 5, sizeof cc.hw, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    return 0;
+}
+// clears the class counters and the cursors and sorts the rows into the lists; cc == nullptr: the caller reads what it wants itself
+static int classify(const hhx_csr *a, const hhx_csr *b, i64 window_min, i64 hash_max, i64 tiny_max, RowLists &L, RowPools &tab, ClassCounts *cc) {
+    HHX_HIP(hipMemsetAsync(L.counts.p, 0, 4 * sizeof(unsigned int), g_stream));
+    HHX_TRY(tab.zero_cursors());
+    k_classify<<<(unsigned)std::max<i64>(1, std::min<i64>(((i64)a->n_rows + 63) / 64, 4096)), 256, 0, g_stream>>>(
+        a->n_rows, a->indptr.p, a->indices.p, b->indptr.p, window_min, hash_max, tiny_max, L.w.p, L.c.p, L.t.p, L.h.p, L.row_f.p, L.counts.p, tab.cursors.p);
+    HHX_LAUNCH_CHECK();
+    if (!cc) return 0;
+    HHX_TRY(read_class_counts(L, tab, *cc));
+    memcpy(cc->classified, cc->hc, sizeof cc->hc);
+    return 0;
+}
+
+// ---- hash class.  It runs first: it may add rows to the window / compact lists (cc is read again)
+static int run_hash_class(const ExPlan &pl, const hhx_csr *b, ExParams &P, RowLists &L, const RowPools &tab, DevBuf<int2> &bjx, ClassCounts &cc) {
+    if (!bjx.p) {                                     // B as 8-byte (column, value) words, built once per call
+        if (bjx.alloc((size_t)b->nnz + 4)) return 1;
+        k_pack_jx<<<(unsigned)std::max<i64>(1, std::min<i64>((b->nnz + 255) / 256, 256 * 16)), 256, 0, g_stream>>>(b->nnz, b->indices.p, b->data.p, bjx.p);
         HHX_LAUNCH_CHECK();
+    }
+    P.Bjx = bjx.p;
+    HHX_TRY((raise_dynamic_lds<k_expand_hash>()));
+    {
+        KTimer kt("expand_hash");
+        const unsigned per_cu = pl.lds_hash > 80 * 1024 ? 1 : 2;
+        k_expand_hash<<<std::min<unsigned>(cc.hc[3], 256 * per_cu * 4), HASH_T, pl.lds_hash, g_stream>>>(P, L.h.p, (i32)cc.hc[3], pl.W, L.row_f.p, pl.window_min,
+                                                                                                     L.w.p, L.c.p, L.counts.p);
+#ifdef HHX_HASH_STATS
+        {
+            unsigned long long hs[4] = {0, 0, 0, 0};
+            (void)hipStreamSynchronize(g_stream);
+            (void)hipMemcpyFromSymbol(hs, HIP_SYMBOL(g_hash_stats), sizeof hs);
+            fprintf(stderr, "[hash stats] rows %u: consumes %llu, leftovers %llu (%.2f per consume of 512), sum of per-consume maxima %llu (%.2f per consume)\n", cc.hc[3], hs[0], hs[1],
+                    hs[0] ? (double)hs[1] / hs[0] : 0.0, hs[2], hs[0] ? (double)hs[2] / hs[0] : 0.0);
+            unsigned long long z[4] = {0, 0, 0, 0};
+            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hash_stats), z, sizeof z);
+        }
+#endif
+    }
+    HHX_LAUNCH_CHECK();
+    return read_class_counts(L, tab, cc);
+}
+
+// ---- rows of a list in the order of (key, row): one (key, row) pair per row, sorted by row and then, stably, by key — the order
+// does not depend on the list's (the classification appends by wave)
+struct KeyedRows {
+    DevBuf<u64> key, val, skey, sval;   // key / val: filled by the caller, sorted by sort(); skey / sval: scratch
+    int alloc(i64 nl) { return key.alloc((size_t)nl) || val.alloc((size_t)nl) || skey.alloc((size_t)nl) || sval.alloc((size_t)nl); }
+    int sort(i64 nl, i32 n_rows, int key_bits) {
         int rbits = 1;
         while (rbits < 31 && (n_rows >> rbits)) ++rbits;
         HHX_TRY(stable_sort_pairs_u64(val.p, sval.p, key.p, skey.p, nl, rbits));              // by row ...
-        HHX_TRY(stable_sort_pairs_u64(skey.p, key.p, sval.p, val.p, nl, 32));                 // ... then, stably, by min-hash: the order does not depend on the list's
-        k_rows_from_sorted<<<(unsigned)std::min<i64>((nl + 255) / 256, 4096), 256, 0, g_stream>>>((i32)nl, val.p, list.p);
-        HHX_LAUNCH_CHECK();
-        HHX_HIP(hipStreamSynchronize(g_stream));                                              // the sort buffers die with this scope
+        HHX_TRY(stable_sort_pairs_u64(skey.p, key.p, sval.p, val.p, nl, key_bits));           // ... then, stably, by key
         return 0;
-    };
-    int group_mode = -1;                // -1: not decided yet (first attempt), 0: one row per workgroup, 1: groups
-    DevBuf<int4> rec;                   // window kernel: records + stream of the right operand, built once per call
+    }
+};
+
+// ---- rows of the window class grouped by attractor (k_expand_group).  Decided on the first attempt of a call; a retry classifies the rows
+// again, so groups that are in use are built again from the new list (and may be given up)
+struct RowGroups {
+    DevBuf<i32> rows, Gp, Gj;
+    DevBuf<float> Gx;
+    i32 n = 0;
+    i64 entries = 0;                    // entries of the union rows
+    bool on = false;                    // the window class of this call runs on the groups
+};
+static int build_groups(const ExPlan &pl, const hhx_csr *a, const RowLists &L, const ClassCounts &cc, RowGroups &g) {
+    g.on = false;
+    g.n = 0;
+    const int R = pl.reuse_R;
+    const double a_len0 = cc.hc[0] ? (double)cc.hw[1] / (double)cc.hc[0] : 0.0;
+    if (!R || cc.hc[0] < 1024 || a_len0 < 128.0) return 0;
+    KTimer kt("group_build");
+    const i64 nl = (i64)cc.hc[0];
+    KeyedRows kr;
+    if (kr.alloc(nl)) return 1;
+    k_row_attractor<<<(unsigned)std::min<i64>((nl + 3) / 4, 4096), 256, 0, g_stream>>>((i32)nl, L.w.p, a->indptr.p, a->indices.p, a->data.p, kr.key.p, kr.val.p);
+    HHX_LAUNCH_CHECK();
+    int cbits = 1;
+    while (cbits < 31 && (pl.n_cols >> cbits)) ++cbits;
+    HHX_TRY(kr.sort(nl, pl.n_rows, cbits));                // by (attractor, row)
+    std::vector<u64> h_att((size_t)nl), h_row((size_t)nl);
+    HHX_HIP(hipMemcpyAsync(h_att.data(), kr.key.p, 8 * (size_t)nl, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipMemcpyAsync(h_row.data(), kr.val.p, 8 * (size_t)nl, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    std::vector<i32> h_grp;
+    h_grp.reserve((size_t)nl + (size_t)R);
+    for (i64 p0 = 0; p0 < nl;) {
+        i64 p1 = p0 + 1;
+        while (p1 < nl && p1 - p0 < R && h_att[(size_t)p1] == h_att[(size_t)p0]) ++p1;
+        for (i64 q = p0; q < p0 + R; ++q) h_grp.push_back(q < p1 ? (i32)h_row[(size_t)q] : -1);
+        p0 = p1;
+    }
+    g.n = (i32)(h_grp.size() / (size_t)R);
+    if ((i64)g.n * 2 > nl) return 0;                       // on average two rows or more per group, or the walk is not shared
+    const i32 Wb = (pl.n_cols + 31) / 32;
+    const size_t lds_u = (size_t)Wb * 8 + 64;
+    DevBuf<i32> gcnt;
+    if (g.rows.alloc(h_grp.size()) || gcnt.alloc((size_t)g.n + 1) || g.Gp.alloc((size_t)g.n + 2)) return 1;
+    HHX_HIP(hipMemcpyAsync(g.rows.p, h_grp.data(), sizeof(i32) * h_grp.size(), hipMemcpyHostToDevice, g_stream));
+    HHX_TRY((raise_dynamic_lds<k_group_union<false>, k_group_union<true>>()));
+    if (lds_u > 160 * 1024) return 0;
+    const unsigned ggrid = (unsigned)std::min<i32>(g.n, 256 * 8);
+    k_group_union<false><<<ggrid, 256, lds_u, g_stream>>>(g.n, R, g.rows.p, a->indptr.p, a->indices.p, a->data.p, Wb, gcnt.p, nullptr, nullptr, nullptr);
+    HHX_LAUNCH_CHECK();
+    i64 union_nnz = 0;
+    HHX_TRY(exclusive_scan_i32(gcnt.p, g.Gp.p, g.n, &union_nnz));
+    if (union_nnz >= (i64)INT32_MAX / 8) return 0;
+    if (g.Gj.alloc((size_t)union_nnz + 1) || g.Gx.alloc((size_t)union_nnz * (size_t)R + 1)) return 1;
+    k_group_union<true><<<ggrid, 256, lds_u, g_stream>>>(g.n, R, g.rows.p, a->indptr.p, a->indices.p, a->data.p, Wb, nullptr, g.Gp.p, g.Gj.p, g.Gx.p);
+    HHX_LAUNCH_CHECK();
+    HHX_HIP(hipStreamSynchronize(g_stream));              // h_grp and the scratch die with this scope
+    g.on = true;
+    g.entries = union_nnz;
+    if (expand_debug()) fprintf(stderr, "[hhx expand] re-use: %lld rows in %d groups of <= %d, union rows hold %lld entries (the rows: %llu)\n",
+                                (long long)nl, g.n, R, (long long)union_nnz, cc.hw[1]);
+    return 0;
+}
+
+// Rows of the window class in the order of (min-hash of the pattern, row) — tune "row_order", 1 unless switched off.  The rows a launch has in flight together (one per
+// workgroup, 256 at a time) then walk largely the SAME rows of B, which they find in the Infinity Cache instead of HBM: the heavy iterations of a low-inflation tail
+// run at 1.31-1.37e12 products/s instead of 1.15-1.18e12 (C3, inflation 1.1: 7.39 -> 6.74 s).  The order of the rows changes no bit of the result.
+static int order_rows(const ExPlan &pl, const hhx_csr *a, DevBuf<i32> &list, i64 nl) {
+    if (pl.dense || pl.raw || !pl.self || !tune_get("row_order", 1)) return 0;
+    KTimer kt("row_order");
+    KeyedRows kr;
+    if (kr.alloc(nl)) return 1;
+    k_row_minhash<<<(unsigned)std::min<i64>((nl + 3) / 4, 4096), 256, 0, g_stream>>>((i32)nl, list.p, a->indptr.p, a->indices.p, kr.key.p, kr.val.p);
+    HHX_LAUNCH_CHECK();
+    HHX_TRY(kr.sort(nl, pl.n_rows, 32));
+    k_rows_from_sorted<<<(unsigned)std::min<i64>((nl + 255) / 256, 4096), 256, 0, g_stream>>>((i32)nl, kr.val.p, list.p);
+    HHX_LAUNCH_CHECK();
+    HHX_HIP(hipStreamSynchronize(g_stream));                                              // the sort buffers die with this scope
+    return 0;
+}
+
+// ---- window kernel: records + stream of the right operand (ExParams::rec), built once per call for the column-window plan (cap, n_win) in use
+struct OperandStream {
+    DevBuf<int4> rec;
     DevBuf<unsigned short> c16;
-    DevBuf<float> cls_x;
+    DevBuf<float> x;
     double explicit_frac = 1.0;         // share of B's entries outside the value-uniform sub-segments
-    i64 stream_slots = 0;               // slots of the operand stream (prefix included)
-    if (cap_win + N_DUMMY > 65536) return fail("expand: column window wider than 16 bits");
-    // candidate pool: early windows test against a partial row sum and admit more than finally survive
-    i64 pool_cap = dense ? 64 : std::max<i64>(4 * a->nnz + 16 * (i64)n_rows, (i64)1 << 22);
-    i64 cand_cap = dense ? 64 : (n_win > 1 ? 2 * pool_cap : pool_cap);
-    // Inside mcl()'s loop (hhx_mcl.hip) the iteration before says what this one will need: its demand + 50 % instead of 4 and 8 entries per entry of
-    // A.  The guess above made the tail at inflation 1.1 of a 100k-contig matrix ask for 22 GB of pools per iteration, of sizes that change every
-    // iteration — 67-97 GB of FRESH device memory per tail, 1.2-1.8 s of its 7.4 s on the caller's thread (tools/tail_alloc_probe.py,
-    // profiles/r06_tail_alloc_probe.json).  An overflow costs one retry of the iteration with the exact demand, as before.
-    if (!dense && !coded.raw) {
-        if (g_expand_hint.out > 0) {
-            pool_cap = std::max<i64>(g_expand_hint.out + g_expand_hint.out / 2 + 16 * (i64)n_rows, (i64)1 << 22);
-            cand_cap = std::max<i64>(g_expand_hint.cand + g_expand_hint.cand / 2 + 16 * (i64)n_rows, (i64)1 << 22);
-        }
-        g_expand_hint = ExpandDemand();
+    i64 slots = 0;                      // slots of the stream (prefix included)
+};
+static int build_stream(const ExPlan &pl, const hhx_csr *b, const CodedOperand &coded, i32 cap, i32 n_win, OperandStream &s) {
+    const i64 segs = (i64)b->n_rows * n_win;
+    DevBuf<int4> cnt4;
+    DevBuf<i64> sizes, offs;
+    DevBuf<unsigned long long> n_uni;
+    if (s.rec.alloc(2 * (size_t)segs + 2) || cnt4.alloc((size_t)segs + 1) || sizes.alloc((size_t)segs + 1) || offs.alloc((size_t)segs + 2) ||
+        n_uni.alloc(1)) return 1;
+    HHX_HIP(hipMemsetAsync(n_uni.p, 0, sizeof(unsigned long long), g_stream));
+    const unsigned lgrid = (unsigned)std::max<i64>(1, std::min<i64>((segs + 3) / 4, 65536));
+    const int fxi = pl.fx ? 1 : 0;
+    KTimer kt("class_layout");
+    k_layout_sizes<<<lgrid, 256, 0, g_stream>>>(b->n_rows, n_win, cap, pl.n_classes, b->indptr.p, b->indices.p, pl.use_cls ? coded.n16 : nullptr,
+                                                cnt4.p, sizes.p, n_uni.p);
+    HHX_LAUNCH_CHECK();
+    i64 slots = 0;
+    HHX_TRY(exclusive_scan_i64(sizes.p, offs.p, segs, &slots));
+    if (slots > (i64)INT32_MAX - 4096) return fail("expand: the padded operand stream needs %lld slots (int32 cursors)", (long long)slots);
+    unsigned long long h = 0;
+    HHX_HIP(hipMemcpyAsync(&h, n_uni.p, sizeof h, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    s.explicit_frac = b->nnz ? 1.0 - (double)h / (double)b->nnz : 1.0;
+    // slack: a wide tile reads up to 8 entries past a sub-segment end, an exhausted cursor entry 0
+    if (slots + STREAM_PREFIX > (i64)INT32_MAX - 4096) return fail("expand: the padded operand stream needs %lld slots (int32 cursors)", (long long)slots);
+    // + a tile of slack: a masked lane of an explicit tile reads the first entry of its block, whatever lies there (xtile_fetch)
+    if (s.c16.alloc((size_t)slots + STREAM_PREFIX + 8 * HHX_WAVE + 64) || s.x.alloc((size_t)slots + STREAM_PREFIX + 8 * HHX_WAVE + 64)) return 1;
+    s.slots = slots + STREAM_PREFIX;
+    if (pl.use_cls && tune_get("cls_balance", 1))
+        k_layout_write<true><<<lgrid, 256, 0, g_stream>>>(b->n_rows, n_win, cap, pl.n_classes, b->indptr.p, b->indices.p, b->data.p, coded.n16,
+                                                          coded.row_sum, cnt4.p, offs.p, s.c16.p, s.x.p, s.rec.p, fxi);
+    else
+        k_layout_write<false><<<lgrid, 256, 0, g_stream>>>(b->n_rows, n_win, cap, pl.n_classes, b->indptr.p, b->indices.p, b->data.p,
+                                                           pl.use_cls ? coded.n16 : nullptr, pl.use_cls ? coded.row_sum : nullptr, cnt4.p, offs.p, s.c16.p, s.x.p, s.rec.p, fxi);
+    HHX_LAUNCH_CHECK();
+    HHX_HIP(hipStreamSynchronize(g_stream));         // cnt4 / sizes / offs die here
+    return 0;
+}
+
+// ---- window class: the tile heuristics, the launches of every column window, the mirror image of the symmetric mode, the rows finished
+struct WindowRun {                      // what the report says about it
+    double seg_len = 0.0;               // mean length of a B-row segment inside one column window
+    bool long_segments = false;         // iteration 0 (the link matrix is the operand) vs the pruned iterations: timed apart
+    int tile_u = 0;
+};
+static int run_window_class(const ExPlan &pl, const CodedOperand &coded, ExParams &P, const RowLists &L, const ClassCounts &cc, const RowGroups &g,
+                            const OperandStream &s, i32 cap_use, i32 n_win_use, WindowRun &wr) {
+    const i32 n_list = (i32)cc.hc[0];
+    const unsigned grid = std::min<unsigned>(cc.hc[0], 256);
+    // mean length of a B-row segment inside one column window: tiles of 2 / 4 / 8 entries per lane
+    const int tile_env = (int)tune_get("tile_u", 0);
+    wr.seg_len = cc.hw[1] ? (double)cc.hw[0] / (double)cc.hw[1] / (double)n_win_use : 0.0;
+    wr.long_segments = wr.seg_len >= 192.0;
+    P.Sc16 = s.c16.p; P.Sx = s.x.p; P.rec = s.rec.p;
+    P.narrow_classes = pl.use_cls ? (pl.n_classes > 1 ? 1 : 0) : -1;
+    // batches: 32 A entries per wave draw when the rows are long; for the few-hundred-entry rows of the later iterations
+    // 8, so that all sixteen waves of the workgroup get work out of one row
+    const double a_len = g.on ? (double)g.entries / (double)std::max(g.n, 1) : (double)cc.hw[1] / (double)cc.hc[0];
+    P.wb = (i32)tune_get("win_batch", a_len >= 1536.0 ? 32 : (a_len >= 512.0 ? 16 : 8));
+    if (P.wb < 1 || P.wb > WB_MAX) P.wb = WB_MAX;
+    // block tiles (pass_blocks): the general operand only — no uniform sub-segments, float values, the padding written by k_layout_write
+    int block_tiles = (!pl.use_cls && !pl.fx && !g.on) ? (int)tune_get("block_tiles", 15) : 0;
+    if (block_tiles >= 10 && block_tiles < 20 && s.slots >= ((i64)1 << 30) - 4096) block_tiles -= 10;      // 32-bit byte offsets of the float32 values
+    // explicit tiles: UX x 64 entries, sized to the mean explicit sub-segment (a tile costs its 2 UX loads and UX
+    // LDS atomics per lane whether filled or not); tune "tile_u" overrides
+    const double xlen = wr.seg_len * s.explicit_frac;
+    const int ux = tile_env ? tile_env : (xlen > 288.0 ? 8 : (xlen > 200.0 ? 4 : (xlen > 136.0 ? 3 : (xlen > 68.0 ? 2 : 1))));
+    wr.tile_u = ux;
+    if (g.on) {
+        KTimer kt("expand_group", n_win_use);
+        const GroupOp op{g.rows.p, g.Gp.p, g.Gj.p, g.Gx.p, g.n};
+        const size_t lds_g = (size_t)pl.reuse_R * (pl.reuse_R == 4 ? GroupStride<4>::value : GroupStride<2>::value) * 8 + win_fixed_bytes();
+        HHX_TRY(pick_group_shape(pl.reuse_R, ux)(P, op, cap_use, lds_g, (unsigned)std::min<i32>(g.n, 256)));
+    } else {
+        KTimer kt(wr.long_segments ? "expand_window" : "expand_window_short", pl.n_win);
+        if (block_tiles && prof_enabled()) prof_count("expand_block_tile_launches", pl.n_win);
+        const WindowLauncher launch = pick_window_shape(block_tiles, ux);
+        if (!launch) return fail("expand: block_tiles %d is not a shape", block_tiles);
+        HHX_TRY(launch(P, L.w.p, n_list, pl.cap_win, pl.lds_win, grid));
     }
-    if (coded.plan_out) { coded.plan_out[0] = cap_win; coded.plan_out[1] = n_win; }
-    if (coded.raw) {                    // every entry is kept: at most dense, and at most one entry per product
-        HHX_HIP(hipMemsetAsync(counts.p, 0, 4 * sizeof(unsigned int), g_stream));
-        HHX_HIP(hipMemsetAsync(cursors.p, 0, 12 * sizeof(unsigned long long), g_stream));
-        k_classify<<<(unsigned)std::max<i64>(1, std::min<i64>(((i64)n_rows + 63) / 64, 4096)), 256, 0, g_stream>>>(
-            n_rows, a->indptr.p, a->indices.p, b->indptr.p, window_min, (i64)0, (i64)TINY_MAX, list_w.p, list_c.p, list_t.p, list_h.p, row_f.p, counts.p, cursors.p);
+    HHX_LAUNCH_CHECK();
+    if (pl.sym_whole && pl.n_win > 1 && !coded.tri) {
+        KTimer kt("dense_transpose");
+        const unsigned tiles = (unsigned)(pl.cap_win / 64), pairs = (unsigned)(pl.n_win * (pl.n_win - 1) / 2);
+        k_transpose_lower<<<dim3(tiles, tiles, pairs), 256, 0, g_stream>>>(coded.dense_out, coded.dense_ld ? coded.dense_ld : (i64)pl.n_cols, pl.n_cols, pl.cap_win);
         HHX_LAUNCH_CHECK();
+    }
+    if (!pl.dense) {
+        KTimer kt("expand_finalize");
+        k_expand_window_finalize<<<std::min<unsigned>(cc.hc[0], 256 * 8), EX_T_CMP, ex_fixed_bytes(0, 0), g_stream>>>(P, L.w.p, n_list);
+    }
+    return 0;
+}
+
+// ---- the end of an attempt: the HHX_DEBUG line; once the attempt stands (no pool overflowed) the profile counters — the tests and bench.py
+// assert from them which classes and shapes ran
+static void report(const ExPlan &pl, const hhx_csr *a, const hhx_csr *b, const RowPools &tab, const ClassCounts &cc, const RowGroups &g, const WindowRun &wr,
+                   i32 n_win_use, const unsigned long long *cur, int attempt, std::chrono::steady_clock::time_point t_enter) {
+    if (expand_debug())
+        fprintf(stderr, "[hhx expand] %d x %d, nnzA %lld nnzB %lld: window rows %u (n_win %d x %d cols, lds %zu), hash rows %u, compact rows %u; "
+                "candidates %llu / %lld, survivors %llu / %lld, tile %d (segments of %.0f), %.1f ms since entry%s\n", pl.n_rows, pl.n_cols, (long long)a->nnz, (long long)b->nnz, cc.hc[0], pl.n_win,
+                pl.cap_win, pl.lds_win, cc.hc[3], cc.hc[1], cur[0], (long long)tab.cand_cap, cur[1], (long long)tab.pool_cap, wr.tile_u, wr.seg_len,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count(), cur[2] ? "  OVERFLOW -> retry" : "");
+    if (cur[2] && !pl.dense) return;
+    // per-class row counts of the attempt
+    auto count_classes = [&]() {
+        if (!prof_enabled()) return;
+        prof_count("expand_rows_window", (i64)cc.classified[0]);
+        prof_count("expand_rows_compact", (i64)cc.classified[1]);
+        prof_count("expand_rows_tiny", (i64)cc.classified[2]);
+        prof_count("expand_rows_hash", (i64)cc.classified[3]);
+        prof_count("expand_rows_hash_to_window", (i64)cc.hc[0] - (i64)cc.classified[0]);
+        prof_count("expand_rows_hash_to_compact", (i64)cc.hc[1] - (i64)cc.classified[1]);
+        if (cc.hc[0]) prof_count("expand_window_n_win", n_win_use);
+    };
+    const i64 explicit_bytes = (i64)(pl.fx ? 4 : 6) * ((i64)cur[8] - (pl.use_cls ? (i64)cur[7] : 0));
+    if (pl.dense) {
+        count_classes();
+        if (prof_enabled()) {                      // what the launches actually walked (the symmetric mode skips the blocks J < I)
+            prof_count("expand_window_products", (i64)cur[8]);
+            prof_count("expand_window_a_reads", (i64)cur[9]);
+            if (pl.use_cls) prof_count("expand_window_uniform_products", (i64)cur[7]);
+            prof_count("expand_window_explicit_bytes", explicit_bytes);
+        }
+        return;
+    }
+    if (prof_enabled() && cc.hc[0] && g.on) {
+        prof_count("expand_group_loaded_entries", (i64)cur[8]);           // entries of B streamed (each serves up to R products)
+        prof_count("expand_group_products", (i64)cc.hw[0]);               // products of the rows of the class
+        prof_count("expand_group_a_reads", (i64)cur[9]);
+    } else if (prof_enabled() && cc.hc[0]) {
+        const bool longseg = wr.long_segments;
+        prof_count(longseg ? "expand_window_products" : "expand_window_short_products", (i64)cur[8]);
+        prof_count(longseg ? "expand_window_a_reads" : "expand_window_short_a_reads", (i64)cur[9]);
+        if (longseg) prof_count("expand_window_explicit_bytes", explicit_bytes);
+        if (pl.use_cls) prof_count("expand_window_uniform_products", (i64)cur[7]);
+    }
+    if (attempt) prof_count("expand_pool_retries", attempt);
+    count_classes();
+}
+
+}  // namespace
+
+int hhx_expand_impl(const hhx_csr *a, const hhx_csr *b, const CodedOperand &coded, int fx_shift, double inflation, double pruning,
+                    hhx_csr **out, i64 *n_products, i64 *nnz_expanded) {
+    const auto t_enter = std::chrono::steady_clock::now();
+    ExPlan plan;
+    HHX_TRY(expand_plan(a, b, coded, out, inflation, fx_shift, plan));
+    const ExPlan &pl = plan;
+    HHX_TRY((raise_dynamic_lds<k_expand_compact>()));
+    RowLists lists;
+    RowPools tab;
+    if (lists.alloc(pl.n_rows) || tab.alloc_table(pl.n_rows, pl.n_win_tab)) return 1;
+    expand_pool_sizes(pl, a, tab);
+    if (coded.plan_out) { coded.plan_out[0] = pl.cap_win; coded.plan_out[1] = pl.n_win; }
+    ClassCounts cc;
+    if (pl.raw) {                       // every entry is kept: at most dense, and at most one entry per product
+        HHX_TRY(classify(a, b, pl.window_min, (i64)0, (i64)TINY_MAX, lists, tab, nullptr));
         unsigned long long products = 0;
-        HHX_HIP(hipMemcpyAsync(&products, cursors.p + 4, sizeof products, hipMemcpyDeviceToHost, g_stream));
+        HHX_HIP(hipMemcpyAsync(&products, tab.cursors.p + 4, sizeof products, hipMemcpyDeviceToHost, g_stream));
         HHX_HIP(hipStreamSynchronize(g_stream));
-        const i64 dense = (i64)n_rows * n_cols;
-        pool_cap = cand_cap = std::min<i64>(dense, (i64)products) + n_rows;
+        tab.pool_cap = tab.cand_cap = std::min<i64>((i64)pl.n_rows * pl.n_cols, (i64)products) + pl.n_rows;
     }
+    const ExParams shared = expand_params(pl, a, b, coded, inflation, pruning);
+    DevBuf<int2> bjx;                   // the builds of the call: made by the first attempt that needs them
+    RowGroups groups;
+    OperandStream stream;
     for (int attempt = 0; attempt < 6; ++attempt) {
-        DevBuf<i32> cand_col, out_col;
-        DevBuf<float> cand_val, out_val;
-        if (cand_col.alloc((size_t)cand_cap) || cand_val.alloc((size_t)cand_cap) || out_col.alloc((size_t)pool_cap) ||
-            out_val.alloc((size_t)pool_cap)) return 1;
-        HHX_HIP(hipMemsetAsync(counts.p, 0, 4 * sizeof(unsigned int), g_stream));
-        HHX_HIP(hipMemsetAsync(cursors.p, 0, 12 * sizeof(unsigned long long), g_stream));
-        k_classify<<<(unsigned)std::max<i64>(1, std::min<i64>(((i64)n_rows + 63) / 64, 4096)), 256, 0, g_stream>>>(
-            n_rows, a->indptr.p, a->indices.p, b->indptr.p, window_min, hash_max, all_window ? (i64)-1 : (i64)TINY_MAX, list_w.p, list_c.p, list_t.p, list_h.p, row_f.p,
-            counts.p, cursors.p);
-        HHX_LAUNCH_CHECK();
-        unsigned int hc[4];
-        unsigned long long hw[2];                            // products / A entries of the window class
-        HHX_HIP(hipMemcpyAsync(hc, counts.p, sizeof hc, hipMemcpyDeviceToHost, g_stream));
-        HHX_HIP(hipMemcpyAsync(hw, cursors.p + 5, sizeof hw, hipMemcpyDeviceToHost, g_stream));
-        HHX_HIP(hipStreamSynchronize(g_stream));
-        const unsigned cls_rows[4] = {hc[0], hc[1], hc[2], hc[3]};      // what k_classify decided, before the hash kernel hands rows back
-        ExParams P;
-        P.Ap = a->indptr.p; P.Aj = a->indices.p; P.Ax = a->data.p;
-        P.Bp = b->indptr.p; P.Bj = b->indices.p; P.Bx = b->data.p;
-        P.n_rows = n_rows; P.n_cols = n_cols;
-        P.scale = ldexp(1.0, fx_shift - 52); P.inv_scale = ldexp(1.0, 52 - fx_shift);
-        P.r = (double)(float)inflation; P.square = inflation == 2.0; P.thr = (float)pruning;
-        P.raw = coded.raw;
-        P.cand_col = cand_col.p; P.cand_val = cand_val.p; P.cand_cap = cand_cap;
-        P.out_col = out_col.p; P.out_val = out_val.p; P.out_cap = pool_cap;
-        P.cursors = cursors.p; P.row_off = row_off.p; P.row_cnt = row_cnt.p;
-        P.n_win = n_win;
-        P.s_run = s_run.p; P.g_win_off = g_win_off.p; P.g_win_cnt = g_win_cnt.p;
-        P.dense = coded.dense_out; P.dense_ld = coded.dense_ld ? coded.dense_ld : (i64)n_cols;
-        P.W = fx ? coded.W : nullptr; P.A16 = coded.a16; P.row_div = coded.a_row_sum; P.fx_inv = ldexp(1.0, -coded.shift);
-        P.sym = coded.sym; P.sym_row0 = coded.sym_row0;
-        P.tri = coded.tri; P.tri_ldn = (i64)n_win * cap_win;
-        P.Sc16 = nullptr; P.Sx = nullptr; P.rec = nullptr; P.Bjx = nullptr; P.narrow_classes = 0; P.wb = WB_MAX;
-        if (hc[3]) {                                      // hash class first: it may add rows to the window / compact lists
-            if (!bjx.p) {                                 // B as 8-byte (column, value) words, built once per call
-                if (bjx.alloc((size_t)b->nnz + 4)) return 1;
-                k_pack_jx<<<(unsigned)std::max<i64>(1, std::min<i64>((b->nnz + 255) / 256, 256 * 16)), 256, 0, g_stream>>>(b->nnz, b->indices.p, b->data.p, bjx.p);
-                HHX_LAUNCH_CHECK();
-            }
-            P.Bjx = bjx.p;
-            HHX_TRY((raise_dynamic_lds<k_expand_hash>()));
-            {
-                KTimer kt("expand_hash");
-                const unsigned per_cu = lds_hash > 80 * 1024 ? 1 : 2;
-                k_expand_hash<<<std::min<unsigned>(hc[3], 256 * per_cu * 4), HASH_T, lds_hash, g_stream>>>(P, list_h.p, (i32)hc[3], W, row_f.p, window_min,
-                                                                                                      list_w.p, list_c.p, counts.p);
-#ifdef HHX_HASH_STATS
-                {
-                    unsigned long long hs[4] = {0, 0, 0, 0};
-                    (void)hipStreamSynchronize(g_stream);
-                    (void)hipMemcpyFromSymbol(hs, HIP_SYMBOL(g_hash_stats), sizeof hs);
-                    fprintf(stderr, "[hash stats] rows %u: consumes %llu, leftovers %llu (%.2f per consume of 512), sum of per-consume maxima %llu (%.2f per consume)\n", hc[3], hs[0], hs[1],
-                            hs[0] ? (double)hs[1] / hs[0] : 0.0, hs[2], hs[0] ? (double)hs[2] / hs[0] : 0.0);
-                    unsigned long long z[4] = {0, 0, 0, 0};
-                    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hash_stats), z, sizeof z);
-                }
-#endif
-            }
-            HHX_LAUNCH_CHECK();
-            HHX_HIP(hipMemcpyAsync(hc, counts.p, sizeof hc, hipMemcpyDeviceToHost, g_stream));
-            HHX_HIP(hipMemcpyAsync(hw, cursors.p + 5, sizeof hw, hipMemcpyDeviceToHost, g_stream));
-            HHX_HIP(hipStreamSynchronize(g_stream));
-        }
-        const unsigned n_hash_rows = hc[3];
-        // per-class row counts of this attempt (profile counters, reported once the attempt stands): the tests assert which classes ran
-        auto count_classes = [&](i32 n_win_launch) {
-            if (!prof_enabled()) return;
-            prof_count("expand_rows_window", (i64)cls_rows[0]);
-            prof_count("expand_rows_compact", (i64)cls_rows[1]);
-            prof_count("expand_rows_tiny", (i64)cls_rows[2]);
-            prof_count("expand_rows_hash", (i64)cls_rows[3]);
-            prof_count("expand_rows_hash_to_window", (i64)hc[0] - (i64)cls_rows[0]);
-            prof_count("expand_rows_hash_to_compact", (i64)hc[1] - (i64)cls_rows[1]);
-            if (hc[0]) prof_count("expand_window_n_win", n_win_launch);
-        };
-        // ---- rows of the window class grouped by attractor (k_expand_group): decided once per call
-        if (group_mode < 0 || (group_mode == 1 && attempt > 0)) {
-            group_mode = 0;
-            n_groups = 0;
-            const double a_len0 = hc[0] ? (double)hw[1] / (double)hc[0] : 0.0;
-            if (reuse_R && hc[0] >= 1024 && a_len0 >= 128.0) {
-                KTimer kt("group_build");
-                const i64 nl = (i64)hc[0];
-                DevBuf<u64> key, val, skey, sval;
-                if (key.alloc((size_t)nl) || val.alloc((size_t)nl) || skey.alloc((size_t)nl) || sval.alloc((size_t)nl)) return 1;
-                k_row_attractor<<<(unsigned)std::min<i64>((nl + 3) / 4, 4096), 256, 0, g_stream>>>((i32)nl, list_w.p, a->indptr.p, a->indices.p, a->data.p, key.p, val.p);
-                HHX_LAUNCH_CHECK();
-                // rows in list order are not ascending (the classification appends by wave): sort by (attractor, row)
-                int rbits = 1;
-                while (rbits < 31 && (n_rows >> rbits)) ++rbits;
-                int cbits = 1;
-                while (cbits < 31 && (n_cols >> cbits)) ++cbits;
-                HHX_TRY(stable_sort_pairs_u64(val.p, sval.p, key.p, skey.p, nl, rbits));              // by row ...
-                HHX_TRY(stable_sort_pairs_u64(skey.p, key.p, sval.p, val.p, nl, cbits));              // ... then, stably, by attractor
-                std::vector<u64> h_att((size_t)nl), h_row((size_t)nl);
-                HHX_HIP(hipMemcpyAsync(h_att.data(), key.p, 8 * (size_t)nl, hipMemcpyDeviceToHost, g_stream));
-                HHX_HIP(hipMemcpyAsync(h_row.data(), val.p, 8 * (size_t)nl, hipMemcpyDeviceToHost, g_stream));
-                HHX_HIP(hipStreamSynchronize(g_stream));
-                std::vector<i32> h_grp;
-                h_grp.reserve((size_t)nl + (size_t)reuse_R);
-                for (i64 p0 = 0; p0 < nl;) {
-                    i64 p1 = p0 + 1;
-                    while (p1 < nl && p1 - p0 < reuse_R && h_att[(size_t)p1] == h_att[(size_t)p0]) ++p1;
-                    for (i64 q = p0; q < p0 + reuse_R; ++q) h_grp.push_back(q < p1 ? (i32)h_row[(size_t)q] : -1);
-                    p0 = p1;
-                }
-                n_groups = (i32)(h_grp.size() / (size_t)reuse_R);
-                if ((i64)n_groups * 2 <= nl) {                // on average two rows or more per group: the walk is shared
-                    const i32 Wb = (n_cols + 31) / 32;
-                    const size_t lds_u = (size_t)Wb * 8 + 64;
-                    DevBuf<i32> gcnt;
-                    if (grp_rows.alloc(h_grp.size()) || gcnt.alloc((size_t)n_groups + 1) || Gp.alloc((size_t)n_groups + 2)) return 1;
-                    HHX_HIP(hipMemcpyAsync(grp_rows.p, h_grp.data(), sizeof(i32) * h_grp.size(), hipMemcpyHostToDevice, g_stream));
-                    HHX_TRY((raise_dynamic_lds<k_group_union<false>, k_group_union<true>>()));
-                    if (lds_u <= 160 * 1024) {
-                        const unsigned ggrid = (unsigned)std::min<i32>(n_groups, 256 * 8);
-                        k_group_union<false><<<ggrid, 256, lds_u, g_stream>>>(n_groups, reuse_R, grp_rows.p, a->indptr.p, a->indices.p, a->data.p, Wb, gcnt.p, nullptr, nullptr, nullptr);
-                        HHX_LAUNCH_CHECK();
-                        i64 union_nnz = 0;
-                        HHX_TRY(exclusive_scan_i32(gcnt.p, Gp.p, n_groups, &union_nnz));
-                        if (union_nnz < (i64)INT32_MAX / 8) {
-                            if (Gj.alloc((size_t)union_nnz + 1) || Gx.alloc((size_t)union_nnz * (size_t)reuse_R + 1)) return 1;
-                            k_group_union<true><<<ggrid, 256, lds_u, g_stream>>>(n_groups, reuse_R, grp_rows.p, a->indptr.p, a->indices.p, a->data.p, Wb, nullptr, Gp.p, Gj.p, Gx.p);
-                            HHX_LAUNCH_CHECK();
-                            HHX_HIP(hipStreamSynchronize(g_stream));      // h_grp dies with this scope
-                            group_mode = 1;
-                            group_entries = union_nnz;
-                            if (debug) fprintf(stderr, "[hhx expand] re-use: %lld rows in %d groups of <= %d, union rows hold %lld entries (the rows: %llu)\n",
-                                               (long long)nl, n_groups, reuse_R, (long long)union_nnz, hw[1]);
-                        }
-                    }
-                }
-            }
-        }
-        if (group_mode == 0 && attempt == 0 && hc[0] >= 1024) HHX_TRY(order_rows(list_w, (i64)hc[0]));
-        const i32 cap_use = group_mode == 1 ? cap_g : cap_win;
-        const i32 n_win_use = group_mode == 1 ? n_win_g : n_win;
+        HHX_TRY(tab.alloc_pools());
+        HHX_TRY(classify(a, b, pl.window_min, pl.hash_max, pl.all_window ? (i64)-1 : (i64)TINY_MAX, lists, tab, &cc));
+        ExParams P = shared;
+        tab.fill(P);
+        if (cc.hc[3]) HHX_TRY(run_hash_class(pl, b, P, lists, tab, bjx, cc));
+        if (attempt == 0 || groups.on) HHX_TRY(build_groups(pl, a, lists, cc, groups));
+        // (a retry classifies the rows again and leaves them in list order: the min-hash order is the first attempt's alone)
+        if (!groups.on && attempt == 0 && cc.hc[0] >= 1024) HHX_TRY(order_rows(pl, a, lists.w, (i64)cc.hc[0]));
+        const i32 cap_use = groups.on ? pl.cap_g : pl.cap_win, n_win_use = groups.on ? pl.n_win_g : pl.n_win;
         P.n_win = n_win_use;
-        // mean length of a B-row segment inside one column window: tiles of 2 / 4 / 8 entries per lane
-        const int tile_env = (int)tune_get("tile_u", 0);
-        const double seg_len = hw[1] ? (double)hw[0] / (double)hw[1] / (double)n_win_use : 0.0;
-        int tile_u = 0;
-        const bool long_segments = seg_len >= 192.0;          // iteration 0 (the link matrix is the operand) vs the pruned iterations: timed apart
-        if (hc[0]) {
-            const unsigned grid = std::min<unsigned>(hc[0], 256);
-            if (!rec.p) {                                 // the operand stream of b, built once per call
-                const i64 segs = (i64)b->n_rows * n_win_use;
-                DevBuf<int4> cnt4;
-                DevBuf<i64> sizes, offs;
-                DevBuf<unsigned long long> n_uni;
-                if (rec.alloc(2 * (size_t)segs + 2) || cnt4.alloc((size_t)segs + 1) || sizes.alloc((size_t)segs + 1) || offs.alloc((size_t)segs + 2) ||
-                    n_uni.alloc(1)) return 1;
-                HHX_HIP(hipMemsetAsync(n_uni.p, 0, sizeof(unsigned long long), g_stream));
-                const unsigned lgrid = (unsigned)std::max<i64>(1, std::min<i64>((segs + 3) / 4, 65536));
-                KTimer kt("class_layout");
-                k_layout_sizes<<<lgrid, 256, 0, g_stream>>>(b->n_rows, n_win_use, cap_use, n_classes, b->indptr.p, b->indices.p, use_cls ? coded.n16 : nullptr,
-                                                            cnt4.p, sizes.p, n_uni.p);
-                HHX_LAUNCH_CHECK();
-                i64 slots = 0;
-                HHX_TRY(exclusive_scan_i64(sizes.p, offs.p, segs, &slots));
-                if (slots > (i64)INT32_MAX - 4096) return fail("expand: the padded operand stream needs %lld slots (int32 cursors)", (long long)slots);
-                unsigned long long h = 0;
-                HHX_HIP(hipMemcpyAsync(&h, n_uni.p, sizeof h, hipMemcpyDeviceToHost, g_stream));
-                HHX_HIP(hipStreamSynchronize(g_stream));
-                explicit_frac = b->nnz ? 1.0 - (double)h / (double)b->nnz : 1.0;
-                // slack: a wide tile reads up to 8 entries past a sub-segment end, an exhausted cursor entry 0
-                if (slots + STREAM_PREFIX > (i64)INT32_MAX - 4096) return fail("expand: the padded operand stream needs %lld slots (int32 cursors)", (long long)slots);
-                // + a tile of slack: a masked lane of an explicit tile reads the first entry of its block, whatever lies there (xtile_fetch)
-                if (c16.alloc((size_t)slots + STREAM_PREFIX + 8 * HHX_WAVE + 64) || cls_x.alloc((size_t)slots + STREAM_PREFIX + 8 * HHX_WAVE + 64)) return 1;
-                stream_slots = slots + STREAM_PREFIX;
-                if (use_cls && tune_get("cls_balance", 1))
-                    k_layout_write<true><<<lgrid, 256, 0, g_stream>>>(b->n_rows, n_win_use, cap_use, n_classes, b->indptr.p, b->indices.p, b->data.p, coded.n16,
-                                                                      coded.row_sum, cnt4.p, offs.p, c16.p, cls_x.p, rec.p, fx ? 1 : 0);
-                else
-                    k_layout_write<false><<<lgrid, 256, 0, g_stream>>>(b->n_rows, n_win_use, cap_use, n_classes, b->indptr.p, b->indices.p, b->data.p,
-                                                                       use_cls ? coded.n16 : nullptr, use_cls ? coded.row_sum : nullptr, cnt4.p, offs.p, c16.p, cls_x.p, rec.p, fx ? 1 : 0);
-                HHX_LAUNCH_CHECK();
-                HHX_HIP(hipStreamSynchronize(g_stream));         // cnt4 / sizes / offs die here
-            }
-            P.Sc16 = c16.p; P.Sx = cls_x.p; P.rec = rec.p;
-            P.narrow_classes = use_cls ? (n_classes > 1 ? 1 : 0) : -1;
-            // batches: 32 A entries per wave draw when the rows are long; for the few-hundred-entry rows of the later iterations
-            // 8, so that all sixteen waves of the workgroup get work out of one row
-            const double a_len = group_mode == 1 ? (double)group_entries / (double)std::max(n_groups, 1) : (hc[0] ? (double)hw[1] / (double)hc[0] : 0.0);
-            P.wb = (i32)tune_get("win_batch", a_len >= 1536.0 ? 32 : (a_len >= 512.0 ? 16 : 8));
-            if (P.wb < 1 || P.wb > WB_MAX) P.wb = WB_MAX;
-            // explicit tiles: UX x 64 entries, sized to the mean explicit sub-segment (a tile costs its 2 UX loads and UX
-            // LDS atomics per lane whether filled or not); tune "tile_u" overrides
-            // block tiles (pass_blocks): the general operand only — no uniform sub-segments, float values, the padding written by k_layout_write
-            int block_tiles = (!use_cls && !fx && P.narrow_classes == -1 && group_mode != 1) ? (int)tune_get("block_tiles", 15) : 0;
-            if (block_tiles >= 10 && block_tiles < 20 && stream_slots >= ((i64)1 << 30) - 4096) block_tiles -= 10;      // 32-bit byte offsets of the float32 values
-            const double xlen = seg_len * explicit_frac;
-            const int ux = tile_env ? tile_env : (xlen > 288.0 ? 8 : (xlen > 200.0 ? 4 : (xlen > 136.0 ? 3 : (xlen > 68.0 ? 2 : 1))));
-            tile_u = ux;
-            if (group_mode == 1) {
-                KTimer kt("expand_group", n_win_use);
-                GroupOp op{grp_rows.p, Gp.p, Gj.p, Gx.p, n_groups};
-                const size_t lds_g = (size_t)reuse_R * (reuse_R == 4 ? GroupStride<4>::value : GroupStride<2>::value) * 8 + fixed_win;
-                const unsigned ggrid = (unsigned)std::min<i32>(n_groups, 256);
-                if (reuse_R == 4) {
-                    if (ux >= 4) HHX_TRY((launch_group<4, 4, 4>(P, op, cap_use, lds_g, ggrid)));
-                    else if (ux >= 2) HHX_TRY((launch_group<4, 2, 8>(P, op, cap_use, lds_g, ggrid)));
-                    else HHX_TRY((launch_group<4, 1, 8>(P, op, cap_use, lds_g, ggrid)));
-                } else {
-                    if (ux >= 4) HHX_TRY((launch_group<2, 4, 4>(P, op, cap_use, lds_g, ggrid)));
-                    else if (ux >= 2) HHX_TRY((launch_group<2, 2, 8>(P, op, cap_use, lds_g, ggrid)));
-                    else HHX_TRY((launch_group<2, 1, 8>(P, op, cap_use, lds_g, ggrid)));
-                }
-            } else {
-                KTimer kt(long_segments ? "expand_window" : "expand_window_short", n_win);
-#ifdef HHX_PROBE_BUILD             // measurement build only (-DHHX_PROBE_BUILD): the atomics switched off, results are garbage
-                if (probe == 1 && ux >= 4) HHX_TRY((launch_window<1, 8, 3, 3>(P, list_w.p, (i32)hc[0], cap_win, lds_win, grid)));
-                else if (probe == 1) HHX_TRY((launch_window<1, 3, 8, 3>(P, list_w.p, (i32)hc[0], cap_win, lds_win, grid)));
-                else
-#endif
-#define HHX_BLK(UXV, GV, AMV) HHX_TRY((launch_window_fx<0, UXV, GV, AMV, false, EX_T_WIN, true>(P, list_w.p, (i32)hc[0], cap_win, lds_win, grid)))
-                if (block_tiles && prof_enabled()) prof_count("expand_block_tile_launches", n_win);
-                if (block_tiles == 15) HHX_BLK(4, 5, 1);          // groups of 20 blocks, one 32-bit offset per block
-                else if (block_tiles == 5) HHX_BLK(4, 5, 0);      // ... a scalar base per block (streams of 2^30 slots and more)
-                else if (block_tiles == 11) HHX_BLK(4, 4, 1);     // measured beside them (C3 tail at 1.1: 5.06 / 5.15 / 5.23 s against 5.01 / 5.17 s; tiles per segment: 5.81 s)
-                else if (block_tiles == 1) HHX_BLK(4, 4, 0);
-                else if (block_tiles == 31) HHX_BLK(4, 4, 3);     // the loads written by hand (no VALU instruction for an address): 4.92 s — 1.7 % for loads the compiler cannot see: not the default
-                else if (block_tiles == 2) HHX_BLK(8, 3, 0);
-                else if (block_tiles) return fail("expand: block_tiles %d is not a shape", block_tiles);
-#undef HHX_BLK
-                else if (ux >= 8) HHX_TRY((launch_window<0, 8, 3, 3>(P, list_w.p, (i32)hc[0], cap_win, lds_win, grid)));
-                else if (ux == 4) HHX_TRY((launch_window<0, 4, 4, 3>(P, list_w.p, (i32)hc[0], cap_win, lds_win, grid)));
-                else if (ux == 3) HHX_TRY((launch_window<0, 3, 8, 3>(P, list_w.p, (i32)hc[0], cap_win, lds_win, grid)));
-                else if (ux == 2) HHX_TRY((launch_window<0, 2, 8, 3>(P, list_w.p, (i32)hc[0], cap_win, lds_win, grid)));
-                else HHX_TRY((launch_window<0, 1, 8, 3>(P, list_w.p, (i32)hc[0], cap_win, lds_win, grid)));
-            }
-            HHX_LAUNCH_CHECK();
-            if (sym_whole && n_win > 1 && !coded.tri) {
-                KTimer kt("dense_transpose");
-                const unsigned tiles = (unsigned)(cap_win / 64), pairs = (unsigned)(n_win * (n_win - 1) / 2);
-                k_transpose_lower<<<dim3(tiles, tiles, pairs), 256, 0, g_stream>>>(coded.dense_out, coded.dense_ld ? coded.dense_ld : (i64)n_cols, n_cols, cap_win);
-                HHX_LAUNCH_CHECK();
-            }
-            if (!dense) {
-                KTimer kt("expand_finalize");
-                k_expand_window_finalize<<<std::min<unsigned>(hc[0], 256 * 8), EX_T_CMP, ex_fixed_bytes(0, 0), g_stream>>>(P, list_w.p, (i32)hc[0]);
-            }
+        WindowRun wr;
+        if (cc.hc[0]) {
+            if (!stream.rec.p) HHX_TRY(build_stream(pl, b, coded, cap_use, n_win_use, stream));
+            HHX_TRY(run_window_class(pl, coded, P, lists, cc, groups, stream, cap_use, n_win_use, wr));
         }
         HHX_LAUNCH_CHECK();
-        if (hc[2]) {
+        if (cc.hc[2]) {
             KTimer kt("expand_tiny");
-            k_expand_tiny<<<(unsigned)std::max<i64>(1, std::min<i64>(((i64)hc[2] + 255) / 256, 4096)), 256, 0, g_stream>>>(P, list_t.p, (i32)hc[2]);
+            k_expand_tiny<<<(unsigned)std::max<i64>(1, std::min<i64>(((i64)cc.hc[2] + 255) / 256, 4096)), 256, 0, g_stream>>>(P, lists.t.p, (i32)cc.hc[2]);
         }
         HHX_LAUNCH_CHECK();
-        if (hc[1]) {
+        if (cc.hc[1]) {
             KTimer kt("expand_compact");
-            const unsigned per_cu = lds_cmp > 80 * 1024 ? 1 : 2;
-            k_expand_compact<<<std::min<unsigned>(hc[1], 256 * per_cu * 4), EX_T_CMP, lds_cmp, g_stream>>>(P, list_c.p, (i32)hc[1], cap_cmp, W);
+            const unsigned per_cu = pl.lds_cmp > 80 * 1024 ? 1 : 2;
+            k_expand_compact<<<std::min<unsigned>(cc.hc[1], 256 * per_cu * 4), EX_T_CMP, pl.lds_cmp, g_stream>>>(P, lists.c.p, (i32)cc.hc[1], pl.cap_cmp, pl.W);
         }
         HHX_LAUNCH_CHECK();
         unsigned long long cur[12];
-        HHX_HIP(hipMemcpyAsync(cur, cursors.p, sizeof cur, hipMemcpyDeviceToHost, g_stream));
+        HHX_HIP(hipMemcpyAsync(cur, tab.cursors.p, sizeof cur, hipMemcpyDeviceToHost, g_stream));
         HHX_HIP(hipStreamSynchronize(g_stream));
-        if (debug)
-            fprintf(stderr, "[hhx expand] %d x %d, nnzA %lld nnzB %lld: window rows %u (n_win %d x %d cols, lds %zu), hash rows %u, compact rows %u; "
-                    "candidates %llu / %lld, survivors %llu / %lld, tile %d (segments of %.0f), %.1f ms since entry%s\n", n_rows, n_cols, (long long)a->nnz, (long long)b->nnz, hc[0], n_win,
-                    cap_win, lds_win, n_hash_rows, hc[1], cur[0], (long long)cand_cap, cur[1], (long long)pool_cap, tile_u, seg_len,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count(), cur[2] ? "  OVERFLOW -> retry" : "");
-        if (dense) {                                   // the rows are in coded.dense_out; nothing to pack
-            if (hc[0] != (unsigned)n_rows) return fail("expand (dense): %u of %d rows took the window class", hc[0], n_rows);
-            count_classes(n_win_use);
-            if (prof_enabled()) {                      // what the launches actually walked (the symmetric mode skips the blocks J < I)
-                prof_count("expand_window_products", (i64)cur[8]);
-                prof_count("expand_window_a_reads", (i64)cur[9]);
-                if (use_cls) prof_count("expand_window_uniform_products", (i64)cur[7]);
-                prof_count("expand_window_explicit_bytes", (i64)(fx ? 4 : 6) * ((i64)cur[8] - (use_cls ? (i64)cur[7] : 0)));
-            }
-            if (n_products) *n_products = (i64)cur[4];
-            if (nnz_expanded) *nnz_expanded = (i64)cur[3];
-            return 0;
-        }
-        if (cur[2]) {                                  // a pool overflowed: grow and redo the launches
-            if ((i64)cur[0] > cand_cap) cand_cap = std::max<i64>(cand_cap * 2, (i64)cur[0] + (i64)n_rows);
-            if ((i64)cur[1] > pool_cap) pool_cap = std::max<i64>(pool_cap * 2, (i64)cur[1] + (i64)n_rows);
+        if (pl.dense && cc.hc[0] != (unsigned)pl.n_rows) return fail("expand (dense): %u of %d rows took the window class", cc.hc[0], pl.n_rows);
+        report(pl, a, b, tab, cc, groups, wr, n_win_use, cur, attempt, t_enter);
+        if (cur[2] && !pl.dense) {                     // a pool overflowed: grow and redo the launches
+            if ((i64)cur[0] > tab.cand_cap) tab.cand_cap = std::max<i64>(tab.cand_cap * 2, (i64)cur[0] + (i64)pl.n_rows);
+            if ((i64)cur[1] > tab.pool_cap) tab.pool_cap = std::max<i64>(tab.pool_cap * 2, (i64)cur[1] + (i64)pl.n_rows);
             continue;
-        }
-        if (prof_enabled() && hc[0] && group_mode == 1) {
-            prof_count("expand_group_loaded_entries", (i64)cur[8]);           // entries of B streamed (each serves up to R products)
-            prof_count("expand_group_products", (i64)hw[0]);                  // products of the rows of the class
-            prof_count("expand_group_a_reads", (i64)cur[9]);
-        } else if (prof_enabled() && hc[0]) {
-            const bool longseg = long_segments;
-            prof_count(longseg ? "expand_window_products" : "expand_window_short_products", (i64)cur[8]);
-            prof_count(longseg ? "expand_window_a_reads" : "expand_window_short_a_reads", (i64)cur[9]);
-            if (longseg) prof_count("expand_window_explicit_bytes", (i64)(fx ? 4 : 6) * ((i64)cur[8] - (use_cls ? (i64)cur[7] : 0)));
-            if (use_cls) prof_count("expand_window_uniform_products", (i64)cur[7]);
         }
         if (n_products) *n_products = (i64)cur[4];
         if (nnz_expanded) *nnz_expanded = (i64)cur[3];
+        if (pl.dense) return 0;                        // the rows are in coded.dense_out; nothing to pack
         g_expand_demand.out = (i64)cur[1];
         g_expand_demand.cand = (i64)cur[0];
-        if (attempt) prof_count("expand_pool_retries", attempt);
-        count_classes(n_win_use);
-        return pack_rows_to_csr(n_rows, n_cols, row_cnt.p, indptr.p, row_off.p, out_col.p, out_val.p, out);
+        return pack_rows_to_csr(pl.n_rows, pl.n_cols, tab.row_cnt.p, tab.indptr.p, tab.row_off.p, tab.out_col.p, tab.out_val.p, out);
     }
     return fail("expand: survivor pool kept overflowing");
 }
@@ -2879,19 +3024,9 @@ int hhx_expand_dense_impl(const hhx_csr *a, const hhx_csr *b, const hhx_links_op
 
 // ---- the host side of a dense epilogue pass, shared by the one-inflation and the multi-inflation driver -----------------------------
 namespace {
-// One inflation of a pass: its per-row table, its candidate and survivor pools
-struct DenseInfl {
-    DevBuf<i32> row_cnt, indptr, g_win_cnt, cand_col, out_col;
-    DevBuf<i64> row_off, g_win_off;
-    DevBuf<float> cand_val, out_val;
-    DevBuf<double> s_run;
-    DevBuf<unsigned long long> cursors;
-    i64 pool_cap = 0, cand_cap = 0;
+// One inflation of a pass: its per-row table, its candidate and survivor pools (RowPools), and how this driver sizes and grows them
+struct DenseInfl : RowPools {
     bool done = false;                  // packed into its result (pools released)
-    int alloc_table(i32 n_rows, i32 n_win) {
-        return row_cnt.alloc((size_t)n_rows + 1) || indptr.alloc((size_t)n_rows + 1) || row_off.alloc((size_t)n_rows + 1) || cursors.alloc(12) ||
-               s_run.alloc((size_t)n_rows + 1) || g_win_off.alloc((size_t)n_rows * n_win + 1) || g_win_cnt.alloc((size_t)n_rows * n_win + 1);
-    }
     // Pool sizes.  No hint: a pruned row holds at most 1 / pruning entries; an early window tests against a partial row sum and admits
     // more.  With one (a sweep): the demand of the call before.  Survivors and candidates shrink as the inflation grows, so an inflation
     // at or above the one that left the hint gets exactly the hint's size — the block the previous call left in the pool is then re-used
@@ -2905,22 +3040,13 @@ struct DenseInfl {
         pool_cap = d->last_out + (above ? 0 : d->last_out * below_factor / 2) + d->n_rows;
         cand_cap = d->last_cand + (above ? 0 : d->last_cand * below_factor / 2) + d->n_rows;
     }
-    int alloc_pools() {                 // (the pools of an overflowed attempt go back first: the new ones may take their blocks)
-        release_pools();
-        if (cand_col.alloc((size_t)cand_cap) || cand_val.alloc((size_t)cand_cap) || out_col.alloc((size_t)pool_cap) || out_val.alloc((size_t)pool_cap)) return 1;
-        HHX_HIP(hipMemsetAsync(cursors.p, 0, 12 * sizeof(unsigned long long), g_stream));
-        return 0;
+    int start_attempt() {               // the pools at their current sizes, the cursors cleared
+        HHX_TRY(alloc_pools());
+        return zero_cursors();
     }
-    void release_pools() { cand_col.release(); cand_val.release(); out_col.release(); out_val.release(); }
     void grow_after_overflow(const unsigned long long *cur, i32 n_rows) {      // the cursors hold the demand
         if ((i64)cur[0] > cand_cap) cand_cap = (i64)cur[0] + (i64)n_rows;
         if ((i64)cur[1] > pool_cap) pool_cap = std::max<i64>(pool_cap * 2, (i64)cur[1] + (i64)n_rows);
-    }
-    void fill(ExParams &P) const {
-        P.cand_col = cand_col.p; P.cand_val = cand_val.p; P.cand_cap = cand_cap;
-        P.out_col = out_col.p; P.out_val = out_val.p; P.out_cap = pool_cap;
-        P.cursors = cursors.p; P.row_off = row_off.p; P.row_cnt = row_cnt.p;
-        P.s_run = s_run.p; P.g_win_off = g_win_off.p; P.g_win_cnt = g_win_cnt.p;
     }
 };
 }  // namespace
@@ -3001,7 +3127,7 @@ extern "C" int hhx_dense_inflate_prune(const hhx_dense *d, double inflation, dou
     q.size_from_hint(d, inflation, 1);                 // a sweep: room for a neighbouring inflation
     static const int use_sw = getenv("HHX_DENSE_EPI_SW") ? atoi(getenv("HHX_DENSE_EPI_SW")) : 1;
     for (int attempt = 0; attempt < 4; ++attempt) {
-        HHX_TRY(q.alloc_pools());
+        HHX_TRY(q.start_attempt());
         ExParams P = dense_epi_params(d, pruning);
         P.r = (double)(float)inflation; P.square = inflation == 2.0;
         q.fill(P);
@@ -3109,7 +3235,7 @@ static int dense_inflate_prune_multi_impl(const hhx_dense *d, int K, const doubl
         memset(mo, 0, sizeof mo);
         for (size_t t = 0; t < todo.size(); ++t) {
             DenseInfl &q = pk[(size_t)todo[t]];
-            HHX_TRY(q.alloc_pools());
+            HHX_TRY(q.start_attempt());
             mo[t].r = (double)(float)inflations[todo[t]]; mo[t].square = inflations[todo[t]] == 2.0;
             mo[t].to = {q.cand_col.p, q.cand_val.p, q.cand_cap, q.cursors.p, q.g_win_off.p, q.g_win_cnt.p};
             mo[t].s_run = q.s_run.p;

@@ -2,6 +2,7 @@
 // and hhx_matrix.hip (tables -> CSR link matrix).
 #pragma once
 #include "hhx_common.h"
+#include "hhx_internal.h"
 
 namespace hhx {
 
@@ -197,8 +198,7 @@ int group_pairs(hhx_ingest *h, PairGroups &G, const char *who);
 int hhx_link_matrix_from_run(const hhx::LinkRun *run, i32 n_frag, u64 ord_limit, const uint8_t *in_set_host, i32 n_rest, int add_self_loops,
                              i32 *frag_index_host, i32 *n_linked_out, hhx_csr **out);
 
-// hhx_pairs.hip: paired_links.clm into an open file descriptor (closed there); hhx_ingest.hip: the dict-ordered tables (made on first use)
+// hhx_pairs.hip: paired_links.clm into an open file descriptor (closed there)
 namespace hhx {
 int ingest_write_clm_fd(hhx_ingest *h, int fd, const uint8_t *names_blob, const i64 *name_off, i64 *n_lines, i64 *n_bytes);
 }
-int hhx_ingest_ordered_full_device(hhx_ingest *h, const i32 **fi, const i32 **fj);

@@ -18,8 +18,6 @@
 
 using namespace hhx;
 
-int hhx_csr_alloc_internal(i32 n_rows, i32 n_cols, i64 nnz, hhx_csr **out);
-
 namespace {
 
 struct RowsView {           // insertion-ordered arrays

@@ -6,18 +6,9 @@
 // so that a wave reads 256 contiguous bytes of indices / values per instruction; row sums are
 // wave-level double reductions in a fixed tree (deterministic for a given row).
 #include "hhx_common.h"
+#include "hhx_internal.h"
 
 using namespace hhx;
-
-int hhx_csr_alloc_internal(i32 n_rows, i32 n_cols, i64 nnz, hhx_csr **out);
-int hhx_expand_class_stream(const hhx_csr *a, const hhx_csr *b, const hhx_links_operand *lk, int fx_shift,
-                     double inflation, double pruning, hhx_csr **out, i64 *n_products, i64 *nnz_expanded);
-int hhx_expand_dense_impl(const hhx_csr *a, const hhx_csr *b, const hhx_links_operand *lk, int fx_shift, hhx_dense **out, i64 *n_products,
-                          i64 *nnz_expanded);
-void hhx_expand_set_hint(i64 out, i64 cand);            // hhx_expand.hip: the pools of the next fused iteration sized from the one before
-void hhx_expand_last_demand(i64 *out, i64 *cand);
-int hhx_dense_layout(i32 n_rows, i32 n_cols, i64 nnz_b);
-namespace hhx { i64 pool_cached_bytes(); }
 
 namespace {
 

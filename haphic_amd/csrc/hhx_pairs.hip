@@ -193,8 +193,6 @@ int hhx_side_records_push(hhx_ingest *h, i64 n_pairs, const i32 *id1, const POS 
 template int hhx_side_records_push<i32>(hhx_ingest *, i64, const i32 *, const i32 *, const i32 *, const i32 *);
 template int hhx_side_records_push<i64>(hhx_ingest *, i64, const i32 *, const i64 *, const i32 *, const i64 *);
 
-int hhx_ingest_ordered_full_device(hhx_ingest *h, const i32 **fi, const i32 **fj);   // hhx_ingest.hip
-
 // the kept read pairs grouped by contig pair (PairGroups, hhx_ingest.h)
 int hhx::group_pairs(hhx_ingest *h, PairGroups &G, const char *who) {
     if (h->links_dropped) return fail("%s: keys left the link tables (hhx_ingest_drop_links): the kept read pairs no longer match them", who);

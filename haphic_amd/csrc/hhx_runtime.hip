@@ -2,6 +2,7 @@
 #include <chrono>
 
 #include "hhx_common.h"
+#include "hhx_internal.h"
 
 namespace hhx {
 

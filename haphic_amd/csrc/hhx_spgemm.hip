@@ -16,11 +16,9 @@
 // Rows whose output does not fit the LDS accumulator window are processed in several windows
 // (products outside the current window are skipped), so any row length is handled.
 #include "hhx_common.h"
+#include "hhx_internal.h"
 
 using namespace hhx;
-
-int hhx_csr_alloc_internal(i32 n_rows, i32 n_cols, i64 nnz, hhx_csr **out);
-int hhx_expand_raw(const hhx_csr *a, const hhx_csr *b, int fx_shift, hhx_csr **out, i64 *n_products);   // hhx_expand.hip
 
 namespace {
 
