@@ -31,6 +31,11 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              (haphic_amd/statistics.py) and writes the same bytes; under --gpus N > 1 or torchrun the reference's loop runs whatever
                              the flag says.  The device path also hands the call back when full_link_dict was thawed or holds float values
                              (--remove_concentrated_links, GFA phasing) or a contig has no RE site
+  --keep-reference-dense     cluster only: leave --dense_matrix (:2723; the reference's numpy mode of prune / mcl / interpret_result / run_mcl_clustering, with its
+                             own convergence rule allclose :2051) to the reference's numpy code on the host.  Without the flag a one-rank job with
+                             --dense_matrix runs that recurrence on the device (float32 MFMA products, csrc/hhx_densemcl.hip): same round counts and
+                             clusters, the n x n matrix never leaves HBM; under --gpus N > 1 or torchrun the numpy code runs whatever the flag says.
+                             Without --dense_matrix the flag changes nothing
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
@@ -89,6 +94,7 @@ def main(argv=None):
     keep_ingest = bool(_take(argv, '--keep-reference-ingest', False))
     keep_allelic = bool(_take(argv, '--keep-reference-allelic', False))
     keep_statistics = bool(_take(argv, '--keep-reference-statistics', False))
+    keep_dense = bool(_take(argv, '--keep-reference-dense', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
     scripts = _reference_scripts(ref)
     if stub:
@@ -127,8 +133,8 @@ def main(argv=None):
         S.run(S.parse_arguments(), 'HapHiC_sort.log')               # == HapHiC_sort.main() :962-967
         return 0
     import HapHiC_cluster as H                                      # the unmodified reference module
-    patch.patch_reference(H, ingest=not keep_ingest, allelic=not keep_allelic and ctx is None,      # the allelic and statistics seams: one-rank jobs only
-                          statistics=not keep_statistics and ctx is None)
+    patch.patch_reference(H, ingest=not keep_ingest, allelic=not keep_allelic and ctx is None,      # the allelic, statistics and dense seams: one-rank jobs only
+                          statistics=not keep_statistics and ctx is None, dense=not keep_dense and ctx is None)
     sys.argv = ['haphic cluster'] + argv
     return ranks.run_rank(lambda: H.run(H.parse_arguments(), 'HapHiC_cluster.log'))      # == HapHiC_cluster.main() :2962-2967
 

@@ -213,6 +213,18 @@ SIGNATURES = {
     'hhx_sort_graph_fetch_dense': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     'hhx_sort_graph_stats': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_sort_graph_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_dmat_from_host': (C.c_int, [C.c_int32, C.c_void_p, c_vpp]),
+    'hhx_dmat_from_csr': (C.c_int, [C.c_void_p, c_vpp]),
+    'hhx_dmat_to_host': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_dmat_to_csr': (C.c_int, [C.c_void_p, c_vpp]),
+    'hhx_dmat_copy': (C.c_int, [C.c_void_p, c_vpp]),
+    'hhx_dmat_shape': (C.c_int, [C.c_void_p, c_i32p, c_i64p, c_i64p]),
+    'hhx_dmat_free': (C.c_int, [C.c_void_p]),
+    'hhx_dmat_gemm': (C.c_int, [C.c_void_p, C.c_void_p, c_vpp]),
+    'hhx_dmat_normalize_l1': (C.c_int, [C.c_void_p]),
+    'hhx_dmat_prune': (C.c_int, [C.c_void_p, C.c_double, c_vpp]),
+    'hhx_dmat_power': (C.c_int, [C.c_void_p, C.c_int, c_vpp]),
+    'hhx_dmat_mcl': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, c_vpp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -371,6 +383,101 @@ class DeviceCSR:
             self.free()
         except Exception:
             pass
+
+
+class DenseMatrix:
+    """Device-resident n x n float32 matrix M of the --dense_matrix mode (hhx_dmat handle; stored transposed and padded, every array in and
+    out is M as the reference has it)."""
+
+    def __init__(self, handle):
+        self.h = C.c_void_p(handle) if not isinstance(handle, C.c_void_p) else handle
+
+    @classmethod
+    def from_numpy(cls, m):
+        m = np.ascontiguousarray(m, np.float32)
+        if m.ndim != 2 or m.shape[0] != m.shape[1]:
+            raise ValueError('the dense mode needs a square matrix, got shape {}'.format(m.shape))
+        out = C.c_void_p()
+        check(load().hhx_dmat_from_host(m.shape[0], ptr(m), C.byref(out)))
+        return cls(out)
+
+    @classmethod
+    def from_csr(cls, t):
+        """t: DeviceCSR, CSR(T) == CSC(M); densified on the device"""
+        out = C.c_void_p()
+        check(load().hhx_dmat_from_csr(t.h, C.byref(out)))
+        return cls(out)
+
+    @property
+    def shape(self):
+        n = C.c_int32()
+        check(load().hhx_dmat_shape(self.h, C.byref(n), None, None))
+        return n.value, n.value
+
+    @property
+    def nbytes(self):
+        b = C.c_int64()
+        check(load().hhx_dmat_shape(self.h, None, None, C.byref(b)))
+        return b.value
+
+    def to_numpy(self):
+        n = self.shape[0]
+        out = np.empty((n, n), np.float32)
+        check(load().hhx_dmat_to_host(self.h, ptr(out)))
+        return out
+
+    def to_csr(self):
+        out = C.c_void_p()
+        check(load().hhx_dmat_to_csr(self.h, C.byref(out)))
+        return DeviceCSR(out)
+
+    def copy(self):
+        out = C.c_void_p()
+        check(load().hhx_dmat_copy(self.h, C.byref(out)))
+        return DenseMatrix(out)
+
+    def free(self):
+        if self.h is not None and self.h.value:
+            load().hhx_dmat_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def dmat_gemm(a, b):
+    """a @ b of two DenseMatrix (float32 in, float32 accumulate, k ascending)"""
+    out = C.c_void_p()
+    check(load().hhx_dmat_gemm(a.h, b.h, C.byref(out)))
+    return DenseMatrix(out)
+
+
+def dmat_normalize_l1(m):
+    check(load().hhx_dmat_normalize_l1(m.h))
+    return m
+
+
+def dmat_prune(m, pruning):
+    out = C.c_void_p()
+    check(load().hhx_dmat_prune(m.h, float(pruning), C.byref(out)))
+    return DenseMatrix(out)
+
+
+def dmat_power(m, expansion):
+    out = C.c_void_p()
+    check(load().hhx_dmat_power(m.h, int(expansion), C.byref(out)))
+    return DenseMatrix(out)
+
+
+def dmat_mcl(pre_expanded, expansion, inflation, max_iter, pruning, done=0):
+    """mcl(..., dense_matrix=True) :2026-2062 -> (DenseMatrix, rounds, converged); done = k, max_iter = k + 1: exactly round k"""
+    out, n_iter, conv = C.c_void_p(), C.c_int(0), C.c_int(0)
+    check(load().hhx_dmat_mcl(pre_expanded.h, int(done), int(expansion), float(inflation), int(max_iter), float(pruning), C.byref(out),
+                              C.byref(n_iter), C.byref(conv)))
+    return DenseMatrix(out), n_iter.value, bool(conv.value)
 
 
 # ---------------------------------------------------------------- thin functional wrappers

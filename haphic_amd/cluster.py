@@ -549,10 +549,33 @@ def normalize(matrix, norm='l1', axis=0):
         m.free()
 
 
+def _to_dense_device(matrix):
+    """the operand of a dense call on the device: an ndarray is uploaded, a ResidentMatrix / DeviceCSR (CSR(T) in HBM) is densified there"""
+    if isinstance(matrix, ResidentMatrix):
+        dev = matrix.take_device()
+        try:
+            return _lib.DenseMatrix.from_csr(dev)
+        finally:
+            dev.free()
+    if isinstance(matrix, _lib.DeviceCSR):
+        return _lib.DenseMatrix.from_csr(matrix)
+    if hasattr(matrix, 'toarray'):
+        matrix = matrix.toarray()
+    return _lib.DenseMatrix.from_numpy(np.asarray(matrix))
+
+
 def prune(matrix, pruning, dense_matrix=False):
-    """prune() :1987-2014"""
+    """prune() :1987-2014 (dense_matrix: the numpy branch :2003-2005, ndarray in and out)"""
     if dense_matrix:
-        raise ValueError('dense_matrix mode is not on the MI355X path; use the reference function')
+        m = _to_dense_device(matrix)
+        try:
+            out = _lib.dmat_prune(m, pruning)
+            try:
+                return out.to_numpy()
+            finally:
+                out.free()
+        finally:
+            m.free()
     m = _to_device(matrix)
     try:
         return _lib.prune(m, pruning).to_scipy_csc()
@@ -582,6 +605,13 @@ def mcl_device(pre_expanded, expansion, inflation, iters, pruning, links=False):
     """mcl() on a device-resident pre-expanded matrix (links=True: on the raw link matrix, normalisation and
     pre-expansion fused into iteration 0); logs like the reference (:2047 :2058)."""
     res, n_iter, converged = _lib.mcl(pre_expanded, expansion, inflation, iters, pruning, links=links)
+    _log_mcl(n_iter, converged, expansion, inflation, iters, pruning)
+    return res
+
+
+def mcl_dense_device(pre_expanded, expansion, inflation, iters, pruning):
+    """mcl(..., dense_matrix=True) on a device-resident pre-expanded _lib.DenseMatrix; logs like the reference (:2052 :2058)"""
+    res, n_iter, converged = _lib.dmat_mcl(pre_expanded, expansion, inflation, iters, pruning)
     _log_mcl(n_iter, converged, expansion, inflation, iters, pruning)
     return res
 
@@ -760,9 +790,18 @@ def mcl_resume_device(first, expansion, inflation, iters, pruning):
 
 
 def mcl(matrix, expansion, inflation, iters, pruning, dense_matrix=False):
-    """mcl() :2026-2062 — scipy CSC in, scipy CSC out; every iteration stays in HBM."""
+    """mcl() :2026-2062 — scipy CSC in, scipy CSC out (dense_matrix: ndarray in, ndarray out, the numpy recurrence with allclose :2051);
+    every iteration stays in HBM."""
     if dense_matrix:
-        raise ValueError('dense_matrix mode is not on the MI355X path; use the reference function')
+        pre = _to_dense_device(matrix)
+        try:
+            res = mcl_dense_device(pre, expansion, inflation, iters, pruning)
+            try:
+                return res.to_numpy()
+            finally:
+                res.free()
+        finally:
+            pre.free()
     pre = _to_device(matrix)
     try:
         res = mcl_device(pre, expansion, inflation, iters, pruning)
@@ -825,9 +864,17 @@ def interpret_result_device(result):
 
 
 def interpret_result(result_matrix, dense_matrix=False):
-    """interpret_result() :2065-2095"""
+    """interpret_result() :2065-2095 (dense_matrix: the branch :2080 — the non-zero entries of the ndarray, compacted on the device)"""
     if dense_matrix:
-        raise ValueError('dense_matrix mode is not on the MI355X path; use the reference function')
+        d = _to_dense_device(result_matrix)
+        try:
+            m = d.to_csr()
+        finally:
+            d.free()
+        try:
+            return interpret_result_device(m)
+        finally:
+            m.free()
     m = _to_device(result_matrix)
     try:
         return interpret_result_device(m)
@@ -836,6 +883,9 @@ def interpret_result(result_matrix, dense_matrix=False):
 
 
 # ------------------------------------------------------------------ S4: dict_to_matrix
+DENSE_SEAM_BOUND = False      # patch.patch_reference(H, dense=True): dense_matrix=True calls of prune / mcl / interpret_result / run_mcl_clustering come here
+
+
 class ResidentMatrix:
     """What dict_to_matrix returns for a link table that never left the device: the CSR(T) handle (== the reference's CSC(M)
     triple) for run_mcl_clustering, which takes it over without a host round trip.  Anything else that is asked of it is
@@ -884,7 +934,7 @@ def dict_to_matrix(link_dict, frag_set, dense_matrix=True, add_self_loops=False,
     """dict_to_matrix() :310-373.  Returns (matrix, frag_index_dict); the matrix is scipy CSC (an ndarray with dense_matrix)
     unless _device=True (then a DeviceCSR).  A flank table that is still frozen (containers.LinkTable: run() has only passed it
     through the seams) is turned into the matrix where it lies, in HBM (hhx_ingest_link_matrix), and comes back as a
-    ResidentMatrix."""
+    ResidentMatrix — in sparse mode, and for the clustering matrix of the dense mode when the dense seam is bound (DENSE_SEAM_BOUND)."""
     if _frozen(link_dict, 'flank'):
         session = link_dict._session
         id_names = session.table.frag_names
@@ -896,7 +946,9 @@ def dict_to_matrix(link_dict, frag_set, dense_matrix=True, add_self_loops=False,
             frag_index_dict = _index_dict(id_names, fidx, n_linked, rest)
             if _device:
                 return m, frag_index_dict
-            if dense_matrix:
+            if dense_matrix and not (DENSE_SEAM_BOUND and add_self_loops):
+                # (with the dense seam bound, the clustering matrix of run() :2934 — the one call that adds self loops — stays the ResidentMatrix
+                # of the sparse mode: run_mcl_clustering densifies it in HBM instead of a download followed by an n^2 upload)
                 try:
                     return m.to_scipy_csc().toarray(), frag_index_dict
                 finally:
@@ -1689,20 +1741,32 @@ def run_mcl_clustering(link_matrix, bin_set, frag_len_dict, frag_index_dict, exp
     (sharded.sweep_sharded: one expansion across the ranks, the heavy iterations of the low inflations row-sharded, the light
     remainders dealt by predicted cost; expansion != 2: whole inflations dealt round-robin, sharded.inflation_sweep); every rank
     gets all results, rank 0 writes the files.  _engine: the arithmetic behind sharded.py (default: the HIP library on the
-    current device; CPU tests pass an oracle-backed one)."""
-    if dense_matrix:
-        raise ValueError('dense_matrix mode is not on the MI355X path; use the reference function')
+    current device; CPU tests pass an oracle-backed one).  dense_matrix=True (--dense_matrix :2723): link_matrix is an ndarray or a
+    ResidentMatrix, and the sweep is the reference's numpy recurrence (matrix_power :2149, allclose :2051) on dense float32 blocks in HBM
+    (mcl_dense_device); the cluster read-out and everything from :2167 on is the code both modes share."""
     logger.info('Performing Markov clustering...')
     index_frag = {i: f for f, i in frag_index_dict.items()}
-    if isinstance(link_matrix, ResidentMatrix):                      # straight from dict_to_matrix, still in HBM
+    dense_pre = None
+    if dense_matrix:
+        # --dense_matrix (:2723): the numpy recurrence on the device.  The link matrix (an ndarray, or the CSR(T) of a ResidentMatrix densified in
+        # HBM) is L1-normalised (:2144) and pre-expanded with matrix_power (:2149) ONCE; every inflation restarts from that block (:2155-2158),
+        # its result is compacted on the device and read out like a sparse one.  Nothing leaves the device in between.
+        m = None
+        link_dense = _to_dense_device(link_matrix)
+        try:
+            _lib.dmat_normalize_l1(link_dense)
+            dense_pre = _lib.dmat_power(link_dense, expansion)
+        finally:
+            link_dense.free()
+    elif isinstance(link_matrix, ResidentMatrix):                    # straight from dict_to_matrix, still in HBM
         m = link_matrix.take_device()
     elif isinstance(link_matrix, _lib.DeviceCSR):
         m = link_matrix.copy()
     else:
         m = _to_device(link_matrix)
-    n = m.shape3[0]
+    n = m.shape3[0] if m is not None else dense_pre.shape[0]
     from . import ranks
-    if dist is None and ranks.active():                              # a multi-rank job: the other ranks join the sweep (ranks.py, phase `sweep`)
+    if dist is None and ranks.active() and not dense_matrix:         # a multi-rank job: the other ranks join the sweep (ranks.py, phase `sweep`)
         dist = ranks.share_sweep(m, dict(bin_set=bin_set, frag_len_dict=frag_len_dict, frag_index_dict=frag_index_dict, expansion=expansion,
                                          min_inflation=min_inflation, max_inflation=max_inflation, inflation_step=inflation_step,
                                          max_iter=max_iter, pruning=pruning, fa_dict={k: [None, v[1], v[2]] for k, v in fa_dict.items()},
@@ -1713,14 +1777,14 @@ def run_mcl_clustering(link_matrix, bin_set, frag_len_dict, frag_index_dict, exp
     # are kept as float32 row blocks filled by ONE pass over the products (DenseSweep), and iteration 0 of every inflation is the
     # row-local epilogue over them; a single inflation starts from the link matrix with the pre-expansion fused into its
     # iteration 0 (hhx_mcl_links) — same results, the n^2-entry CSR matrix never exists.
-    materialise = expansion > 1 and n * n < 2 ** 31 and not _block_rows
+    materialise = expansion > 1 and n * n < 2 ** 31 and not _block_rows and not dense_matrix
     inflations = _inflation_values(min_inflation, max_inflation, inflation_step)
     pre = None
     sweep = None
     world = dist.get_world_size() if dist is not None else 1
     rank = dist.get_rank() if dist is not None else 0
-    across = world > 1 and expansion == 2 and max_iter >= 1          # the sweep shared out over the ranks (sharded.sweep_sharded)
-    if across:
+    across = world > 1 and expansion == 2 and max_iter >= 1 and not dense_matrix     # the sweep shared out over the ranks (sharded.sweep_sharded)
+    if across or dense_matrix:
         pass
     elif expansion == 2 and not materialise and len(inflations) > 1 and max_iter >= 1:
         sweep = DenseSweep(m, pruning, block_rows=_block_rows)
@@ -1746,7 +1810,13 @@ def run_mcl_clustering(link_matrix, bin_set, frag_len_dict, frag_index_dict, exp
     firsts = sweep.first_iterations(mine) if sweep is not None else None
 
     def run_one(inflation):
-        if sweep is not None:
+        if dense_pre is not None:
+            dense_res = mcl_dense_device(dense_pre, expansion, float(inflation), max_iter, pruning)
+            try:
+                res = dense_res.to_csr()
+            finally:
+                dense_res.free()
+        elif sweep is not None:
             first = next(firsts)
             t_0 = time.perf_counter()
             res = mcl_resume_device(first, expansion, float(inflation), max_iter, pruning)
@@ -1848,7 +1918,10 @@ def run_mcl_clustering(link_matrix, bin_set, frag_len_dict, frag_index_dict, exp
         SWEEP_STAGES.clear()
         SWEEP_STAGES.update(sweep.stage_s)
         sweep.close()
-    m.free()
+    if m is not None:
+        m.free()
+    if dense_pre is not None:
+        dense_pre.free()
     max_nclusters = max([len(rc) for _, rc in result_clusters_list])
     if max_nclusters < nchrs:
         logger.warning('The maximum number of clusters ({}) is even less than the expected number of '

@@ -71,8 +71,11 @@ STATISTICS_SEAMS = {
 }
 
 
-# position of `dense_matrix` in the reference signatures: --dense_matrix (:2723) is the reference's own numpy mode, which
-# stays the reference's code — a seam called with dense_matrix=True is handed back to the original function
+# position of `dense_matrix` in the reference signatures.  --dense_matrix (:2723) is the reference's own numpy mode (also what every
+# install without Intel MKL runs, :2764-2768): its own convergence rule (allclose :2051), float32 trajectory, prune branch (:2003-2005) and
+# interpret_result branch (:2080).  By default a seam called with dense_matrix=True is handed back to the original function
+# (_dense_dispatch); patch_reference(H, dense=True) binds the device mirrors of that mode instead (cluster.prune / mcl / interpret_result /
+# run_mcl_clustering with dense_matrix=True: csrc/hhx_densemcl.hip) — OPT-IN like `allelic` and `statistics`.
 DENSE_ARG = {'mcl': 5, 'prune': 2, 'interpret_result': 1, 'run_mcl_clustering': 12}
 
 
@@ -121,10 +124,12 @@ def _run_then_join(original):
     return run
 
 
-def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics=False):
+def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics=False, dense=False):
     """H: the imported reference module (HapHiC_cluster).  Returns {name: original} so the caller can undo.  allelic=True (together with
     ingest): remove_allelic_HiC_links :474-692 is re-bound too (ALLELIC_SEAMS); `python -m haphic_amd cluster` asks for it on one-rank jobs.
-    statistics=True (together with ingest): output_statistics :2279-2478 likewise (STATISTICS_SEAMS)."""
+    statistics=True (together with ingest): output_statistics :2279-2478 likewise (STATISTICS_SEAMS).  dense=True: the four seams of DENSE_ARG
+    take their dense_matrix=True calls (--dense_matrix) themselves instead of handing them back to the reference's numpy code, and
+    dict_to_matrix leaves the clustering matrix of a frozen table in HBM for them."""
     from . import _lib
     _lib.load()                          # fail loudly here if the HIP library is missing
     saved = {}
@@ -147,7 +152,8 @@ def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics
         saved[name] = getattr(H, name, None)
         if name in CONTAINER_SEAMS or name in _NEEDS_ORIGINAL or name in ALLELIC_SEAMS or name in STATISTICS_SEAMS:
             fn = _with_original(fn, saved[name])
-        setattr(H, name, _dense_dispatch(fn, saved[name], DENSE_ARG[name]) if name in DENSE_ARG else fn)
+        setattr(H, name, _dense_dispatch(fn, saved[name], DENSE_ARG[name]) if name in DENSE_ARG and not dense else fn)
+    cluster.DENSE_SEAM_BOUND = bool(dense)
     if ingest and getattr(H, 'run', None) is not None:
         saved['run'] = H.run
         H.run = _run_then_join(H.run)    # main() :2967 and HapHiC_pipeline.py:358 resolve `run` through the module, like every seam
@@ -212,6 +218,7 @@ def patch_sort(S, engine=None):
 
 
 def unpatch_reference(H, saved):
+    cluster.DENSE_SEAM_BOUND = False
     for name, fn in saved.items():
         if fn is None and hasattr(H, name):
             delattr(H, name)

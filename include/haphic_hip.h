@@ -223,6 +223,43 @@ int hhx_row_products(const hhx_csr *a, const hhx_csr *b, int64_t *products_host)
 int hhx_expand_links(const hhx_csr *links, int32_t r0, int32_t r1, int fx_shift, double inflation, double pruning,
                      hhx_csr **out, int64_t *n_products, int64_t *nnz_expanded);
 
+/* ---------------------------------------------------------------- --dense_matrix (:2723): the reference's numpy mode of mcl()
+ * hhx_dmat: an n x n float32 matrix M in HBM, the column-stochastic operand of the dense recurrence (hhx_dense above is something else:
+ * rows of M^2 of the SPARSE sweep).  Stored as T = M^T row-major in an ld x ld block (ld = n rounded up to 128) whose entries outside
+ * n x n are always zero (csrc/hhx_densemcl.hip); every array that crosses this interface is M as the reference has it.  Products are
+ * float32 in, float32 accumulate, one accumulator per element with k ascending (v_mfma_f32_32x32x2_f32: an fmaf chain, the same bits on
+ * every launch); sums of a column are float32 in one fixed order.  Memory comes from the pool: mcl() with expansion 2 holds the input,
+ * the matrix and its product (one block more from expansion 3 on); a block that does not fit is an error that names its size. */
+typedef struct hhx_dmat hhx_dmat;
+/* m: n x n float32, row-major, M itself (numpy: the C-contiguous array `matrix`) */
+int hhx_dmat_from_host(int32_t n, const float *m, hhx_dmat **out);
+/* t: CSR(T) == the reference's CSC(M), as dict_to_matrix :362-368 leaves it on the device; `.toarray()` without the host */
+int hhx_dmat_from_csr(const hhx_csr *t, hhx_dmat **out);
+int hhx_dmat_to_host(const hhx_dmat *m, float *out);                    /* out: n x n float32, row-major, M */
+/* the non-zero entries as CSR(T), columns ascending: hhx_interpret (:2065-2095, the dense branch :2080 picks the same entries) and
+ * to_scipy_csc serve the result unchanged */
+int hhx_dmat_to_csr(const hhx_dmat *m, hhx_csr **out);
+int hhx_dmat_copy(const hhx_dmat *m, hhx_dmat **out);                   /* matrix.copy() :2003 :2057 */
+int hhx_dmat_shape(const hhx_dmat *m, int32_t *n, int64_t *ld, int64_t *bytes);     /* any of the three may be NULL */
+int hhx_dmat_free(hhx_dmat *m);
+/* out = a @ b (numpy matmul of the two M; on the stored transposes T_b * T_a): the bare product of matrix_power :2035 :2149 */
+int hhx_dmat_gemm(const hhx_dmat *a, const hhx_dmat *b, hhx_dmat **out);
+/* normalize(matrix, norm='l1', axis=0) :2144 in place: every column divided by its float32 sum of absolute values; a zero column stays */
+int hhx_dmat_normalize_l1(hhx_dmat *m);
+/* prune(matrix, pruning, dense_matrix=True) :1999-2014: entries < pruning zeroed, the FIRST maximum of every column of the un-pruned
+ * matrix (argmax(axis=0) :2012) put back whatever its value, columns L1-normalised */
+int hhx_dmat_prune(const hhx_dmat *m, double pruning, hhx_dmat **out);
+/* numpy.linalg.matrix_power(matrix, expansion) :2035 :2149 in numpy's association order: 1 the matrix, 2 M@M, 3 (M@M)@M, from 4 on the
+ * binary decomposition (z = z@z per bit, result = result@z for the set bits, lowest first) */
+int hhx_dmat_power(const hhx_dmat *m, int expansion, hhx_dmat **out);
+/* mcl(matrix, expansion, inflation, iters, pruning, dense_matrix=True) :2026-2062 on the pre-expanded matrix of :2144-2149: per round
+ * matrix_power (not in round 0), power + normalize :2040, prune :2042, and from the third round on allclose(matrix, last_matrix) :2051
+ * (|a - b| <= 1e-8 + 1e-5 |b| on every entry, float32).  *n_iter: rounds done when it stopped (n + 1 of :2052, max_iter when it did not
+ * converge).  done = the rounds already applied to the input (0: a fresh pre-expanded matrix); done = k with max_iter = k + 1 applies
+ * exactly round k (cf. hhx_mcl_resume).  A resumed call has no last_matrix: it never reports convergence in its first round. */
+int hhx_dmat_mcl(const hhx_dmat *pre_expanded, int done, int expansion, double inflation, int max_iter, double pruning, hhx_dmat **result,
+                 int *n_iter, int *converged);
+
 /* ---------------------------------------------------------------- a12: interpret_result :2065-2095
  * Array half: attractors (ascending) = rows with a non-zero diagonal; members of attractor a =
  * rows of CSR(T) holding column a (ascending).  att[n], att_ptr[n+1], members[nnz] are host
