@@ -8,8 +8,9 @@ Argument parsing, logging, file formats and every stage outside the hot path are
 binning into the scaffold-bin contact matrix) and normalize_matrix (the Knight-Ruiz balancing of `--normalization KR`, the scaled
 matrix and the median behind vmax; `log10` / `none`: the median alone) run on the device (haphic_amd.plot.patch_plot), main() is the reference's.
 `python -m haphic_amd reassign <arguments of "haphic reassign">` wraps HapHiC_reassign.py: parse_link_dict (the per-group link sums) and
-split_clm_file (paired_links.clm split into split_clms/<group>.clm, haphic_amd/reassign.py) run on the device (haphic_amd.patch.patch_reassign);
-the rescue rounds and run() :752-916 are the reference's, called as its main() :919-924 calls them.
+split_clm_file (paired_links.clm split into split_clms/<group>.clm, haphic_amd/reassign.py) run on the device (haphic_amd.patch.patch_reassign),
+and so do the rescue and reassignment rounds (run_reassignment :266-427) and the group-pair sums of the agglomerative step (:489-560) between them
+(patch_reassign(R, rounds=True)); run() :752-916 is the reference's, called as its main() :919-924 calls it.
 `python -m haphic_amd sort <arguments of "haphic sort">` wraps HapHiC_sort.py: the dense work of fast sorting (link matrix, density graph, confidence
 graph and the link re-aggregation of every round, haphic_amd/sort.py) runs on the device (haphic_amd.patch.patch_sort); fast_sort's loop, the spanning
 forest, the ALLHiC child per group and run() :847-959 are the reference's, its process pool replaced by threads; called as its main() :962-967 does.  `sort` with nothing after it has nothing to hand on and exits with a usage message.
@@ -25,6 +26,13 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              also hands a call back to the reference's function when the containers were already thawed, flank_link_dict is
                              empty, --remove_concentrated_links or ultra-long reads (--ul) are on, the log level is DEBUG (the per-key debug
                              lines), a contig is shorter than --nwindows bp, or --max_read_pairs exceeds 4096
+  --keep-reference-rounds    reassign only: leave run_reassignment :266-427 and agglomerative_hierarchical_clustering :489-560 to the reference's loops
+                             over Python dicts, which parse_link_dict then builds as before.  Without the flag parse_link_dict leaves the
+                             per-(contig, group) cells in device memory, every round is a chain of kernel launches on them and only the changed
+                             values are written back into ctg_group_dict and group_RE_dict.  A call still goes to the reference's function when
+                             the link counts are floats or --normalize_by_nlinks is on, a whitelist is given, --min_links is below 1, the log
+                             level is DEBUG (the per-contig lines), a link or RE total reaches 2^53, or the cells of contigs x groups do not
+                             fit in half of the device's memory
   --keep-reference-statistics  cluster only: leave output_statistics :2279-2478 (the *_statistics.txt files and statistics.pdf of every inflation) to the
                              reference's per-contig loop over ctg_group_link_dict, which is rebuilt as Python dicts once per inflation.  Without the
                              flag a one-rank job takes the per-contig numbers of all inflations from one device call on the frozen full_link_dict
@@ -95,6 +103,7 @@ def main(argv=None):
     keep_allelic = bool(_take(argv, '--keep-reference-allelic', False))
     keep_statistics = bool(_take(argv, '--keep-reference-statistics', False))
     keep_dense = bool(_take(argv, '--keep-reference-dense', False))
+    keep_rounds = bool(_take(argv, '--keep-reference-rounds', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
     scripts = _reference_scripts(ref)
     if stub:
@@ -120,7 +129,7 @@ def main(argv=None):
         return 0
     if command == 'reassign':
         import HapHiC_reassign as R                                 # needs pysam / sklearn, as the reference does
-        patch.patch_reassign(R)
+        patch.patch_reassign(R, rounds=not keep_rounds)
         sys.argv = ['haphic reassign'] + argv
         R.run(R.parse_arguments(), 'HapHiC_reassign.log')           # == HapHiC_reassign.main() :919-924
         return 0

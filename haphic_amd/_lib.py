@@ -150,6 +150,12 @@ SIGNATURES = {
     'hhx_lsap_small': (C.c_int, [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     'hhx_ingest_group_stats': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    'hhx_reassign_create': (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_vpp]),
+    'hhx_reassign_cells': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_reassign_round': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                     C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]),
+    'hhx_reassign_pair_sums': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'hhx_reassign_destroy': (C.c_int, [C.c_void_p]),
     'hhx_group_stats': (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_ingest_link_matrix': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, c_i32p, c_vpp]),
@@ -982,6 +988,78 @@ def group_stats(frag_i, frag_j, links, group, n_groups, group_re, ctg_re, sum_mo
         return None
     check(rc)
     return out
+
+
+class Reassign:
+    """hhx_reassign: the cells, the adjacency and the keys of one full_link_dict in HBM for the rounds of `haphic reassign` (run_reassignment
+    :266-427) and the group-pair sums of its agglomerative step (include/haphic_hip.h).  tests/reassign_cases.py holds a numpy engine with the
+    same interface.  Raises Unsupported where the library answers HHX_UNSUPPORTED."""
+
+    class Unsupported(RuntimeError):
+        pass
+
+    def __init__(self, frag_i, frag_j, links, n_ctg, group, n_groups):
+        fi, fj = np.ascontiguousarray(frag_i, np.int32), np.ascontiguousarray(frag_j, np.int32)
+        lk, grp = np.ascontiguousarray(links, np.int64), np.ascontiguousarray(group, np.int32)
+        if not (fi.size == fj.size == lk.size) or grp.size != int(n_ctg):
+            raise ValueError('Reassign: {} / {} / {} key arrays, {} groups for {} contigs'.format(fi.size, fj.size, lk.size, grp.size, n_ctg))
+        self.n_ctg, self.n_groups = int(n_ctg), int(n_groups)
+        self.rounds = 0                 # device rounds so far: the tables are the reference's dicts only while it is 0
+        self.launches = 0               # launch pairs of the last round
+        self.h = C.c_void_p()
+        self._check(load().hhx_reassign_create(fi.size, ptr(fi), ptr(fj), ptr(lk), self.n_ctg, ptr(grp), self.n_groups, C.byref(self.h)))
+
+    def _check(self, rc):
+        if rc == GROUP_STATS_UNSUPPORTED:
+            raise Reassign.Unsupported(load().hhx_last_error().decode('utf-8', 'replace'))
+        check(rc)
+
+    def cells(self):
+        """(sums, first) int64 [n_ctg, n_groups] as group_link_sums returns them"""
+        sums, first = np.zeros((self.n_ctg, self.n_groups), np.int64), np.full((self.n_ctg, self.n_groups), -1, np.int64)
+        check(load().hhx_reassign_cells(self.h, ptr(sums), ptr(first)))
+        return sums, first
+
+    def round(self, group, group_re, ctg_re, order, flags, dismissed, min_links, min_link_density, min_density_ratio, ambiguous_cutoff,
+              is_rescue_round, gfa, sum_mode):
+        """one call of run_reassignment: group (int32 [n_ctg], -1 = 'ungrouped') and group_re (int64 [n_groups]) are changed in place;
+        -> counts int64 [4] (consistent, rescued, reassigned, not rescued)"""
+        for a, dt, n in ((group, np.int32, self.n_ctg), (group_re, np.int64, self.n_groups)):
+            if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.shape == (n,)):
+                raise ValueError('Reassign.round: group is a contiguous int32 [n_ctg] array, group_re an int64 [n_groups] one (changed in place)')
+        cre, od = np.ascontiguousarray(ctg_re, np.int64), np.ascontiguousarray(order, np.int32)
+        fl = np.ascontiguousarray(flags, np.uint8)
+        dm = None if dismissed is None else np.ascontiguousarray(dismissed, np.uint8)
+        if cre.shape != (self.n_ctg,) or fl.shape != (self.n_ctg,) or (dm is not None and dm.shape != (self.n_groups,)):
+            raise ValueError('Reassign.round: ctg_re and flags per contig, dismissed per group')
+        counts, launches = np.zeros(4, np.int64), C.c_int64(0)
+        self._check(load().hhx_reassign_round(self.h, ptr(group), ptr(group_re), ptr(cre), od.size, ptr(od), ptr(fl), ptr(dm), float(min_links),
+                                              float(min_link_density), float(min_density_ratio), float(ambiguous_cutoff), int(bool(is_rescue_round)),
+                                              int(bool(gfa)), int(sum_mode), ptr(counts), C.byref(launches)))
+        self.rounds += 1
+        self.launches = launches.value
+        return counts
+
+    def pair_sums(self, member, group_of_ctg, n_groups):
+        """(sums, first) int64 [n_groups, n_groups]: the links between the member contigs of two different groups at cell (smaller id, larger id)
+        and the dict position of the first such key (-1 = none)"""
+        mb, grp = np.ascontiguousarray(member, np.uint8), np.ascontiguousarray(group_of_ctg, np.int32)
+        if mb.shape != (self.n_ctg,) or grp.shape != (self.n_ctg,):
+            raise ValueError('Reassign.pair_sums: member and group_of_ctg per contig')
+        sums, first = np.zeros((int(n_groups), int(n_groups)), np.int64), np.full((int(n_groups), int(n_groups)), -1, np.int64)
+        check(load().hhx_reassign_pair_sums(self.h, ptr(mb), ptr(grp), int(n_groups), ptr(sums), ptr(first)))
+        return sums, first
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            load().hhx_reassign_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def allelic_nonmax(ki, kj, kcnt, n_ctg, gptr, gmem):

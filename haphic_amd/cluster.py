@@ -457,11 +457,15 @@ def parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks=False, _origi
     if _original is not None and (not group_names or len(id_names) * len(group_names) > 50_000_000):
         return _original(link_dict, ctg_group_dict, normalize_by_nlinks)
     sums, first = _lib.group_link_sums(fi, fj, val.astype(np.int64), grp, len(group_names))
+    return nested_group_links(sums, first, id_names, group_names), linked_contigs(fi, fj, id_names)
+
+
+def nested_group_links(sums, first, id_names, group_names):
+    """ctg_group_link_dict of parse_link_dict :217-263 from the dense (sums, first) tables of hhx_group_link_sums: the outer dict in the order
+    contigs were first touched by add_ctg_group (smallest `first` of the row), every inner dict in the order of its cells' `first`"""
     ctg_group_link_dict = defaultdict(dict)
-    linked_ctg_dict = defaultdict(set)
     rows, cols = np.nonzero(first >= 0)
     order = np.lexsort((first[rows, cols], rows))
-    # outer dict order = order in which contigs were first touched by add_ctg_group (smallest `first` of the row)
     row_first = np.full(len(id_names), np.iinfo(np.int64).max, np.int64)
     np.minimum.at(row_first, rows, first[rows, cols])
     for r in np.argsort(row_first, kind='stable').tolist():
@@ -470,10 +474,16 @@ def parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks=False, _origi
         ctg_group_link_dict[id_names[r]] = {}
     for r, c in zip(rows[order].tolist(), cols[order].tolist()):
         ctg_group_link_dict[id_names[r]][group_names[c]] = int(sums[r, c])
+    return ctg_group_link_dict
+
+
+def linked_contigs(fi, fj, id_names):
+    """linked_ctg_dict of parse_link_dict :248-249"""
+    linked_ctg_dict = defaultdict(set)
     for a, b in zip(fi.tolist(), fj.tolist()):
         linked_ctg_dict[id_names[a]].add(id_names[b])
         linked_ctg_dict[id_names[b]].add(id_names[a])
-    return ctg_group_link_dict, linked_ctg_dict
+    return linked_ctg_dict
 
 
 def group_link_dict(link_dict, ctg_group_dict, _original=None):

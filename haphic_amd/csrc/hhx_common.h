@@ -115,6 +115,11 @@ i64 tune_get(const char *name, i64 dflt);
 int exclusive_scan_i32(const i32 *in, i32 *out, i64 n, i64 *total_host);
 int exclusive_scan_i64(const i64 *in, i64 *out, i64 n, i64 *total_host);
 
+// ------------------------------------------------------------------ per-(contig, group) link sums (hhx_weights.hip)
+// k_group_link_sums on device arrays: sums += links, first = min(2 * key + side) per cell of the dense [n_ctg x n_groups] tables
+int launch_group_link_sums(i64 n_keys, const i32 *fi, const i32 *fj, const i64 *links, const i32 *group, i32 n_groups, unsigned long long *sums,
+                           unsigned long long *first);
+
 // ------------------------------------------------------------------ the file-writer thread (hhx_jobs.hip)
 // run() writes HT_links.pkl, paired_links.clm and full_links.pkl between the seams (:2879 :2888 :2929) and reads none of them: the *_async entry
 // points queue the file on a library-owned host thread (two lanes, each with its own non-blocking stream and pool arena; the jobs of a lane run in

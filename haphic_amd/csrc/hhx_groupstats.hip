@@ -15,84 +15,13 @@
 // second kernel on a per-workgroup table in HBM, indexed by group id.  All sets of a call share the adjacency; the workgroups of one contig are
 // neighbours in the grid, so its row is read from HBM once.  Integer sums are exact; the quotients are IEEE divisions of the sums converted to
 // float64, which equals Python's int / int below 2^53.  No fused multiply-add, no reassociation (the library is built with -ffp-contract=off).
-#include <algorithm>
-
-#include "hhx_ingest.h"
-
-using namespace hhx;
+#include "hhx_groupstats.h"
 
 namespace {
 
-constexpr int GS_THREADS = 256;
 constexpr i64 GS_SLOTS_DEFAULT = 2048, GS_SLOTS_MIN = 16, GS_SLOTS_MAX = 2048;     // 40 bytes of LDS per slot: 80 KB by default, two workgroups per CU (1024 slots measured slower at C3: DESIGN.md)
 constexpr int GS_SPILL_GRID = 1024;                                                // workgroups of the spill kernel at most
 constexpr size_t GS_SPILL_BYTES = (size_t)2 << 30;                                 // ... and HBM for their tables at most
-constexpr u64 GS_NONE = ~0ull;
-constexpr i64 GS_PAD = INT64_MIN;                                                  // sum of a padding cell: sorts behind every real one
-
-inline unsigned gs_grid(u64 n) {
-    u64 b = (n + GS_THREADS - 1) / GS_THREADS;
-    return (unsigned)std::max<u64>(1, std::min<u64>(b, 256 * 16));
-}
-inline i64 pow2_ceil(i64 v) {
-    i64 p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-// where the keys come from: the aggregated contig-pair table of an ingest handle (key != nullptr), or arrays in dict order
-struct GsSource {
-    i64 n;
-    const u64 *key, *ord;
-    const u32 *ht;
-    const i32 *fi, *fj;
-    const i64 *links;
-};
-
-__device__ __forceinline__ bool gs_entry(const GsSource &s, i64 e, i32 &a, i32 &b, i64 &links, u64 &pos) {
-    if (s.key) {
-        const u64 ord = s.ord[e];
-        if (ord == NO_ORD) return false;                                           // not a key of full_link_dict (never was, or dropped)
-        const u64 key = s.key[e] & KEY_MASK;
-        a = (i32)(key >> ID_BITS);
-        b = (i32)(key & ID_MASK);
-        links = (i64)s.ht[4 * e] + (i64)s.ht[4 * e + 1] + (i64)s.ht[4 * e + 2] + (i64)s.ht[4 * e + 3];
-        pos = 2 * ord;                                                             // only the relative order of the positions matters
-        return true;
-    }
-    a = s.fi[e];
-    b = s.fj[e];
-    links = s.links[e];
-    pos = 2 * (u64)e;
-    return true;
-}
-
-__global__ __launch_bounds__(GS_THREADS) void k_gs_count(GsSource s, i32 n_ctg, unsigned long long *__restrict__ deg, int *__restrict__ bad) {
-    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < s.n; e += (i64)gridDim.x * blockDim.x) {
-        i32 a, b;
-        i64 links;
-        u64 pos;
-        if (!gs_entry(s, e, a, b, links, pos)) continue;
-        if ((u32)a >= (u32)n_ctg || (u32)b >= (u32)n_ctg) { atomicExch(bad, 1); continue; }
-        atomicAdd(&deg[a], 1ull);
-        atomicAdd(&deg[b], 1ull);
-    }
-}
-
-__global__ __launch_bounds__(GS_THREADS) void k_gs_scatter(GsSource s, i32 n_ctg, unsigned long long *__restrict__ cursor, i32 *__restrict__ partner,
-                                                           i64 *__restrict__ lk, u64 *__restrict__ ps) {
-    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < s.n; e += (i64)gridDim.x * blockDim.x) {
-        i32 a, b;
-        i64 links;
-        u64 pos;
-        if (!gs_entry(s, e, a, b, links, pos)) continue;
-        if ((u32)a >= (u32)n_ctg || (u32)b >= (u32)n_ctg) continue;
-        const u64 x = atomicAdd(&cursor[a], 1ull);                                 // add_ctg_group(ctg_i, group_j) :2265
-        partner[x] = b; lk[x] = links; ps[x] = pos;
-        const u64 y = atomicAdd(&cursor[b], 1ull);                                 // add_ctg_group(ctg_j, group_i) :2266
-        partner[y] = a; lk[y] = links; ps[y] = pos + 1;
-    }
-}
 
 struct GsSets {
     const i32 *group;        // [n_sets][n_ctg], -1 = ungrouped
@@ -109,28 +38,10 @@ struct GsOut {
     double *other_sum;
 };
 
-__device__ __forceinline__ bool gs_before(i64 sa, u64 fa, i64 sb, u64 fb) { return sa > sb || (sa == sb && fa < fb); }
-
-// The n cells (cg, cs, cf) of one contig, padded to n2 = 2^k slots, in any order -> the outputs of (row, set).  The positions are distinct, so
-// (sum descending, first ascending) is a total order and the network needs no stability.  cf is reused for the quotients.
+// The n cells (cg, cs, cf) of one contig, padded to n2 = 2^k slots, in any order -> the outputs of (row, set).  cf is reused for the quotients.
 __device__ __forceinline__ void gs_finish(i32 *cg, i64 *cs, u64 *cf, i32 n, i32 n2, i32 row, i32 set, const GsSets &S, const GsOut &O) {
     const int tid = threadIdx.x;
-    for (i32 k = 2; k <= n2; k <<= 1)
-        for (i32 j = k >> 1; j > 0; j >>= 1) {
-            for (i32 t = tid; t < n2; t += GS_THREADS) {
-                const i32 p = t ^ j;
-                if (p > t) {
-                    const i64 sa = cs[t], sb = cs[p];
-                    const u64 fa = cf[t], fb = cf[p];
-                    const bool swap = (t & k) == 0 ? gs_before(sb, fb, sa, fa) : gs_before(sa, fa, sb, fb);
-                    if (swap) {
-                        const i32 ga = cg[t], gb = cg[p];
-                        cs[t] = sb; cs[p] = sa; cf[t] = fb; cf[p] = fa; cg[t] = gb; cg[p] = ga;
-                    }
-                }
-            }
-            __syncthreads();
-        }
+    gs_sort_cells(cg, cs, cf, n2);
     const i32 own = S.group[(size_t)set * S.n_ctg + row];
     const i64 *gre = S.group_re + S.re_off[set];
     const i64 cre = S.ctg_re[row];
@@ -142,19 +53,7 @@ __device__ __forceinline__ void gs_finish(i32 *cg, i64 *cs, u64 *cf, i32 n, i32 
     }
     __syncthreads();
     if (tid == 0) {
-        double total = 0.0;
-        if (S.sum_mode == 0) {
-            for (i32 r = 1; r < n; ++r) total += q[r];
-        } else {                                                                   // Neumaier's sum as CPython 3.12's sum() writes it
-            double c = 0.0;
-            for (i32 r = 1; r < n; ++r) {
-                const double x = q[r], t = total + x;
-                if (fabs(total) >= fabs(x)) c += (total - t) + x;
-                else c += (x - t) + total;
-                total = t;
-            }
-            if (c != 0.0 && isfinite(c)) total += c;
-        }
+        const double total = gs_ordered_sum(q, 1, n, S.sum_mode);
         const size_t o = (size_t)set * S.n_ctg + row;
         O.n_cells[o] = n;
         O.max_links[o] = cs[0];
@@ -319,44 +218,26 @@ int gs_run(const char *who, GsSource src, i32 n_ctg, i32 n_sets, const i32 *grou
             if (g[c] < -1 || g[c] >= n_groups[s]) return fail("%s: group id %d of contig %d in set %d (n_groups %d)", who, g[c], c, s, n_groups[s]);
     }
     if (n_re && !group_re_host) return fail("%s: null pointer", who);
-    DevBuf<i32> d_group, d_ng, d_ncells, d_maxg, d_items, d_partner;
-    DevBuf<i64> d_reoff, d_gre, d_cre, d_maxl, d_rowptr, d_lk;
-    DevBuf<u64> d_ps;
+    DevBuf<i32> d_group, d_ng, d_ncells, d_maxg, d_items;
+    DevBuf<i64> d_reoff, d_gre, d_cre, d_maxl;
     DevBuf<double> d_other;
-    DevBuf<unsigned long long> d_deg, d_cursor, d_nspill;
-    DevBuf<int> d_bad;
+    DevBuf<unsigned long long> d_nspill;
     if (d_group.alloc(cells) || d_ng.alloc((size_t)n_sets) || d_reoff.alloc((size_t)n_sets) || d_gre.alloc((size_t)n_re + 1) || d_cre.alloc((size_t)n_ctg) ||
         d_ncells.alloc(cells) || d_maxg.alloc(cells) || d_maxl.alloc(cells) || d_other.alloc(cells) || d_items.alloc(cells) ||
-        d_deg.alloc((size_t)n_ctg + 2) || d_rowptr.alloc((size_t)n_ctg + 2) || d_cursor.alloc((size_t)n_ctg + 2) || d_nspill.alloc(1) || d_bad.alloc(1))
+        d_nspill.alloc(1))
         return 1;
     HHX_HIP(hipMemcpyAsync(d_group.p, group_host, sizeof(i32) * cells, hipMemcpyHostToDevice, g_stream));
     HHX_HIP(hipMemcpyAsync(d_ng.p, n_groups, sizeof(i32) * (size_t)n_sets, hipMemcpyHostToDevice, g_stream));
     HHX_HIP(hipMemcpyAsync(d_reoff.p, re_off.data(), sizeof(i64) * (size_t)n_sets, hipMemcpyHostToDevice, g_stream));
     if (n_re) HHX_HIP(hipMemcpyAsync(d_gre.p, group_re_host, sizeof(i64) * (size_t)n_re, hipMemcpyHostToDevice, g_stream));
     HHX_HIP(hipMemcpyAsync(d_cre.p, ctg_re_host, sizeof(i64) * (size_t)n_ctg, hipMemcpyHostToDevice, g_stream));
-    HHX_HIP(hipMemsetAsync(d_deg.p, 0, sizeof(unsigned long long) * ((size_t)n_ctg + 2), g_stream));
     HHX_HIP(hipMemsetAsync(d_nspill.p, 0, sizeof(unsigned long long), g_stream));
-    HHX_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), g_stream));
     // ---- (a) the symmetric adjacency by contig: count, scan, scatter
-    i64 n_adj = 0;
-    {
-        KTimer kt("groupstats_adjacency", 2);
-        if (src.n) {
-            k_gs_count<<<gs_grid((u64)src.n), GS_THREADS, 0, g_stream>>>(src, n_ctg, d_deg.p, d_bad.p);
-            HHX_LAUNCH_CHECK();
-        }
-        HHX_TRY(exclusive_scan_i64(reinterpret_cast<const i64 *>(d_deg.p), d_rowptr.p, n_ctg, &n_adj));
-        int bad = 0;
-        HHX_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, g_stream));
-        HHX_HIP(hipStreamSynchronize(g_stream));
-        if (bad) return fail("%s: a contig id outside [0, %d)", who, n_ctg);
-        if (d_partner.alloc((size_t)n_adj + 1) || d_lk.alloc((size_t)n_adj + 1) || d_ps.alloc((size_t)n_adj + 1)) return 1;
-        HHX_HIP(hipMemcpyAsync(d_cursor.p, d_rowptr.p, sizeof(i64) * ((size_t)n_ctg + 1), hipMemcpyDeviceToDevice, g_stream));
-        if (src.n) {
-            k_gs_scatter<<<gs_grid((u64)src.n), GS_THREADS, 0, g_stream>>>(src, n_ctg, d_cursor.p, d_partner.p, d_lk.p, d_ps.p);
-            HHX_LAUNCH_CHECK();
-        }
-    }
+    GsAdjacency A;
+    HHX_TRY(gs_build_adjacency(who, src, n_ctg, A));
+    const i64 *rowptr = A.rowptr.p, *lk = A.lk.p;
+    const i32 *partner = A.partner.p;
+    const u64 *ps = A.ps.p;
     // ---- (b) one workgroup per (contig, set)
     i64 slots = std::max<i64>(GS_SLOTS_MIN, std::min<i64>(GS_SLOTS_MAX, tune_get("groupstats_lds_slots", GS_SLOTS_DEFAULT)));
     while (slots & (slots - 1)) slots &= slots - 1;                                 // a power of two, rounded down
@@ -365,7 +246,7 @@ int gs_run(const char *who, GsSource src, i32 n_ctg, i32 n_sets, const i32 *grou
     HHX_TRY((raise_dynamic_lds<k_gs_rows>((int)GS_SLOTS_MAX * 40)));                  // beside the kernel's two static words
     {
         KTimer kt("groupstats_rows");
-        k_gs_rows<<<(unsigned)cells, GS_THREADS, (size_t)slots * 40, g_stream>>>(d_rowptr.p, d_partner.p, d_lk.p, d_ps.p, S, O, (i32)slots, d_nspill.p,
+        k_gs_rows<<<(unsigned)cells, GS_THREADS, (size_t)slots * 40, g_stream>>>(rowptr, partner, lk, ps, S, O, (i32)slots, d_nspill.p,
                                                                                  d_items.p);
         HHX_LAUNCH_CHECK();
     }
@@ -388,7 +269,7 @@ int gs_run(const char *who, GsSource src, i32 n_ctg, i32 n_sets, const i32 *grou
         HHX_HIP(hipMemsetAsync(tfirst.p, 0xff, sizeof(unsigned long long) * (size_t)wgs * g_cap, g_stream));
         {
             KTimer kt("groupstats_spill");
-            k_gs_spill<<<(unsigned)wgs, GS_THREADS, 0, g_stream>>>(d_rowptr.p, d_partner.p, d_lk.p, d_ps.p, S, O, (i64)n_spill, d_items.p, g_cap, p_cap, tsum.p,
+            k_gs_spill<<<(unsigned)wgs, GS_THREADS, 0, g_stream>>>(rowptr, partner, lk, ps, S, O, (i64)n_spill, d_items.p, g_cap, p_cap, tsum.p,
                                                                    tfirst.p, cg.p, cs.p, cf.p);
             HHX_LAUNCH_CHECK();
         }

@@ -123,6 +123,17 @@ __global__ __launch_bounds__(256) void k_group_link_sums(i64 n, const i32 *__res
 }
 }  // namespace
 
+// the launch alone, on device arrays (hhx_groupstats.h: hhx_reassign_create keeps the two tables in HBM)
+int hhx::launch_group_link_sums(i64 n_keys, const i32 *fi, const i32 *fj, const i64 *links, const i32 *group, i32 n_groups, unsigned long long *sums,
+                                unsigned long long *first) {
+    if (n_keys <= 0) return 0;
+    KTimer kt("group_link_sums");
+    k_group_link_sums<<<(unsigned)std::max<i64>(1, std::min<i64>((n_keys + 255) / 256, 256 * 16)), 256, 0, g_stream>>>(n_keys, fi, fj, links, group, n_groups,
+                                                                                                                     sums, first);
+    HHX_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int hhx_group_link_sums(i64 n_keys, const i32 *frag_i, const i32 *frag_j, const i64 *links, i32 n_ctg, const i32 *group_host,
                                    i32 n_groups, i64 *sums_host, i64 *first_host) {
     if (n_keys < 0 || n_ctg < 0 || n_groups < 0) return fail("hhx_group_link_sums: bad arguments");
@@ -142,12 +153,7 @@ extern "C" int hhx_group_link_sums(i64 n_keys, const i32 *frag_i, const i32 *fra
     HHX_HIP(hipMemcpyAsync(dg.p, group_host, sizeof(i32) * (size_t)n_ctg, hipMemcpyHostToDevice, g_stream));
     HHX_HIP(hipMemsetAsync(ds.p, 0, sizeof(unsigned long long) * cells, g_stream));
     HHX_HIP(hipMemsetAsync(df.p, 0xff, sizeof(unsigned long long) * cells, g_stream));
-    if (n_keys) {
-        KTimer kt("group_link_sums");
-        k_group_link_sums<<<(unsigned)std::max<i64>(1, std::min<i64>((n_keys + 255) / 256, 256 * 16)), 256, 0, g_stream>>>(
-            n_keys, di.p, dj.p, dl.p, dg.p, n_groups, ds.p, df.p);
-        HHX_LAUNCH_CHECK();
-    }
+    HHX_TRY(launch_group_link_sums(n_keys, di.p, dj.p, dl.p, dg.p, n_groups, ds.p, df.p));
     HHX_HIP(hipMemcpyAsync(sums_host, ds.p, sizeof(i64) * cells, hipMemcpyDeviceToHost, g_stream));
     HHX_HIP(hipMemcpyAsync(first_host, df.p, sizeof(i64) * cells, hipMemcpyDeviceToHost, g_stream));
     HHX_HIP(hipStreamSynchronize(g_stream));

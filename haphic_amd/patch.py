@@ -162,15 +162,23 @@ def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics
     return saved
 
 
-def patch_reassign(R):
+def patch_reassign(R, rounds=False, engine=None):
     """R: the imported HapHiC_reassign module.  f3: parse_link_dict :217-263 (the per-group link sums behind reassign's
     link densities) on the device for integer link counts; float / normalised links go to the original function.
     split_clm_file :581-622 (paired_links.clm routed line by line to split_clms/<group>.clm) goes through the device too
-    (haphic_amd/reassign.py); the cases the reference answers with an exception of its own go to the original function."""
-    from . import _lib, reassign
-    _lib.load()
+    (haphic_amd/reassign.py); the cases the reference answers with an exception of its own go to the original function.
+    rounds=True: run_reassignment :266-427 and agglomerative_hierarchical_clustering :489-560 are re-bound too and parse_link_dict leaves its
+    result in HBM for them (reassign.bind_rounds: what is handed back to the original functions is listed there); engine: a stand-in for
+    _lib.Reassign (the tests' numpy engine), with which the three mirrors run without a GPU.  Returns {name: original}."""
+    from . import reassign
+    if not rounds:
+        engine = None
+    if engine is None:
+        from . import _lib
+        _lib.load()
     original = R.parse_link_dict
     original_split = R.split_clm_file
+    mirrors = reassign.bind_rounds(R, engine) if rounds else {}                   # around the reference's own functions, as R holds them now
 
     def parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks=False):
         return cluster.parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks, _original=original)
@@ -181,7 +189,11 @@ def patch_reassign(R):
         return reassign.split_clm_file(clm_file, group_ctg_dict, ctg_group_dict, subdir, _original=original_split)
     split_clm_file.__wrapped__ = reassign.split_clm_file
     R.split_clm_file = split_clm_file
-    return {'parse_link_dict': original, 'split_clm_file': original_split}
+    saved = {'parse_link_dict': original, 'split_clm_file': original_split}
+    for name, fn in mirrors.items():
+        saved.setdefault(name, getattr(R, name))
+        setattr(R, name, fn)
+    return saved
 
 
 # `haphic sort`: the module globals fast_sort :470-615 resolves at call time (haphic_amd/sort.py)

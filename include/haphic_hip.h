@@ -72,7 +72,9 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * same bits); "sort_lds_shape" = the largest new shape whose re-aggregation of hhx_sort_graph_aggregate accumulates in LDS, clamped to [0, 192]
  * (default 192; 0: always global atomics; same bits); "groupstats_lds_slots" = slots of the per-workgroup LDS table of hhx_group_stats /
  * hhx_ingest_group_stats (40 bytes each), rounded down to a power of two in [16, 2048] (default 2048; a contig with more distinct groups than slots takes
- * the table in HBM; same bits).  value INT64_MIN: back to the default.  Unset knobs fall back to the
+ * the table in HBM; same bits; hhx_reassign_round orders a row of that many groups in LDS (20 bytes each) and a wider one in HBM);
+ * "reassign_window" = the most contigs of the visiting order one evaluation of hhx_reassign_round judges, clamped to [1, 4096] (default 512; same
+ * results, other launch counts).  value INT64_MIN: back to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
 int hhx_profile_enable(int on);
@@ -613,6 +615,41 @@ int hhx_group_stats(int64_t n_keys, const int32_t *frag_i, const int32_t *frag_j
                     int32_t n_sets, const int32_t *group_host, const int32_t *n_groups, const int64_t *group_re_host,
                     const int64_t *ctg_re_host, int sum_mode, int32_t *n_cells, int64_t *max_links, int32_t *max_group, double *other_sum);
 int hhx_ingest_destroy(hhx_ingest *h);
+
+/* The rescue and reassignment rounds of `haphic reassign` and the group-pair sums of its agglomerative step (HapHiC_reassign.py run_reassignment
+ * :266-427, agglomerative_hierarchical_clustering :494-508; haphic_amd/csrc/hhx_reassign.hip).  The handle keeps in HBM: the keys of
+ * full_link_dict in dict order, their symmetric adjacency by contig, and per (contig, group) cell `sum` (int64) and `stamp` (the cell's position in
+ * the reference's inner dict: 2 * key + side of its first contribution as hhx_group_link_sums defines it, or 2 * n_keys + the number of the move
+ * that created it; UINT64_MAX = no cell).  hhx_reassign_create builds them from the keys and the group of every contig (-1 = 'ungrouped');
+ * hhx_reassign_cells copies the two tables out as hhx_group_link_sums returns them (first == -1: no cell).
+ * hhx_reassign_round is one call of run_reassignment.  group [n_ctg] and group_re [n_groups] (group_RE_dict's values) are uploaded from the
+ * caller's arrays at the start of every call and returned at the end; the cells live across calls.  ctg_re [n_ctg] = RE_site_dict, order [n_order]
+ * = the contigs of sorted_ctg_list, flags [n_ctg]: bit 0 = the RE filter :335 is passed, bit 1 = short enough to be reassigned :415; dismissed
+ * [n_groups] (or NULL) = the groups :304-324 dismisses: their contigs become -1, every contig's links to them 0.  Each contig is judged against the
+ * state all earlier contigs of the call left: the non-zero cells ordered by (sum descending, stamp ascending), the filters :335-368 in their order
+ * (the ambiguity filter only when is_rescue_round is 0), the densities of all cells after the first added one by one in that order (sum_mode as
+ * for hhx_group_stats), divided by n_groups - 1 or, with gfa, by their count; 1000000000 when the sum is 0; the verdicts :392-424.  A move changes
+ * group, group_re of the former and the new group, and the two cells of every neighbour.  counts[4] = consistent, rescued, reassigned, not
+ * rescued; *launches (may be NULL) = the launch pairs the round took.  A round is a chain of (evaluate a window of the order, commit its first
+ * mover) launch pairs in stream order: about n_order / window + movers of them; hhx_tune "reassign_window" bounds the window.  Cells of value 0
+ * are not told apart from absent ones, which is the reference's result while min_links >= 1 (anything below is refused).  Sums and RE totals are
+ * taken to stay below 2^53.
+ * hhx_reassign_pair_sums: for every key in dict order whose two contigs are both in member [n_ctg], both have a group in group_of_ctg (-1 = none)
+ * and the groups differ, the links are added to cell (smaller id, larger id) of sums [n_groups][n_groups], and first holds the dict position of
+ * the first such key (-1 = none).
+ * HHX_UNSUPPORTED (hhx_last_error() says why): n_ctg * n_groups * 16 bytes (the two tables) beyond half of the device's memory; a sum_mode other
+ * than 0 / 1. */
+typedef struct hhx_reassign hhx_reassign;
+int hhx_reassign_create(int64_t n_keys, const int32_t *frag_i, const int32_t *frag_j, const int64_t *links, int32_t n_ctg,
+                        const int32_t *group_host, int32_t n_groups, hhx_reassign **out);
+int hhx_reassign_cells(hhx_reassign *h, int64_t *sums_host, int64_t *first_host);
+int hhx_reassign_round(hhx_reassign *h, int32_t *group_host, int64_t *group_re_host, const int64_t *ctg_re_host, int32_t n_order,
+                       const int32_t *order_host, const uint8_t *flags_host, const uint8_t *dismissed_host, double min_links,
+                       double min_link_density, double min_density_ratio, double ambiguous_cutoff, int is_rescue_round, int gfa,
+                       int sum_mode, int64_t *counts, int64_t *launches);
+int hhx_reassign_pair_sums(hhx_reassign *h, const uint8_t *member_host, const int32_t *group_of_ctg_host, int32_t n_groups, int64_t *sums_host,
+                           int64_t *first_host);
+int hhx_reassign_destroy(hhx_reassign *h);
 
 /* Multi-GPU exchange step (ingest).  The aggregated table of a finalized handle, device
  * SoA in no particular order: key = (i << 29) | j, first-seen global ordinals of the key in
