@@ -14,6 +14,10 @@ and so do the rescue and reassignment rounds (run_reassignment :266-427) and the
 `python -m haphic_amd sort <arguments of "haphic sort">` wraps HapHiC_sort.py: the dense work of fast sorting (link matrix, density graph, confidence
 graph and the link re-aggregation of every round, haphic_amd/sort.py) runs on the device (haphic_amd.patch.patch_sort); fast_sort's loop, the spanning
 forest, the ALLHiC child per group and run() :847-959 are the reference's, its process pool replaced by threads; called as its main() :962-967 does.  `sort` with nothing after it has nothing to hand on and exits with a usage message.
+`python -m haphic_amd build <arguments of "haphic build">` wraps HapHiC_build.py: parse_fasta (HapHiC_cluster.py:87-113: the FASTA text goes to HBM in one piece
+and is compacted there into the contigs' sequences, haphic_amd/scaffolds.py) and build_final_scaffolds :74-179 (scaffolds.fa gathered, reverse-complemented and
+wrapped on the device, written slab by slab; both AGP files from the host arrays) run on the device (haphic_amd.patch.patch_build); parse_tours, the juicebox
+script and run() :244-283 are the reference's, called as its main() :286-291 calls it.
 
 The reference checkout is found through --reference DIR or $HAPHIC_REFERENCE (the repository root or its scripts/
 directory).  Extra flags of the wrapper (removed before the reference parses the command line):
@@ -44,6 +48,9 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              --dense_matrix runs that recurrence on the device (float32 MFMA products, csrc/hhx_densemcl.hip): same round counts and
                              clusters, the n x n matrix never leaves HBM; under --gpus N > 1 or torchrun the numpy code runs whatever the flag says.
                              Without --dense_matrix the flag changes nothing
+  --keep-reference-build     build only: leave parse_fasta and build_final_scaffolds to the reference's per-line and per-60-bases Python loops.  Without the
+                             flag a call still goes to the reference's function for a FASTA file with a byte >= 0x80, with a sequence line in front of
+                             the first header, with a contig name that repeats, or beyond half of the device's memory, and for --max_width < 1 or --Ns < 0
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
@@ -84,15 +91,15 @@ def main(argv=None):
         print(__doc__)
         return 0
     command = argv.pop(0)
-    if command not in ('cluster', 'plot', 'reassign', 'sort'):
-        raise SystemExit('haphic_amd wraps the "cluster", "plot", "reassign" and "sort" steps only (got {!r}); run the other steps with the reference'.format(command))
+    if command not in ('cluster', 'plot', 'reassign', 'sort', 'build'):
+        raise SystemExit('haphic_amd wraps the "cluster", "plot", "reassign", "sort" and "build" steps only (got {!r}); run the other steps with the reference'.format(command))
     if command == 'sort' and not argv:
         # nothing to hand to the reference: say what the wrapper is, as for a step it does not wrap, rather than go looking for the checkout
-        raise SystemExit('haphic_amd wraps the "cluster", "plot", "reassign" and "sort" steps only and hands them the arguments of the reference\'s '
+        raise SystemExit('haphic_amd wraps the "cluster", "plot", "reassign", "sort" and "build" steps only and hands them the arguments of the reference\'s '
                          'command; {!r} came without any (haphic sort: fasta HT_links clm_dir groups ...)'.format(command))
     from . import ranks
     gpus, host_transport = ranks.take_args(argv)
-    if command in ('plot', 'reassign', 'sort') and (gpus or 1) > 1:
+    if command in ('plot', 'reassign', 'sort', 'build') and (gpus or 1) > 1:
         raise SystemExit('--gpus is a flag of the "cluster" step only')
     if (gpus or 1) > 1 and not ranks.in_torchrun():
         # one fresh child process per rank (never exec: this process may not replace itself), each with RANK / WORLD_SIZE / LOCAL_RANK
@@ -104,6 +111,7 @@ def main(argv=None):
     keep_statistics = bool(_take(argv, '--keep-reference-statistics', False))
     keep_dense = bool(_take(argv, '--keep-reference-dense', False))
     keep_rounds = bool(_take(argv, '--keep-reference-rounds', False))
+    keep_build = bool(_take(argv, '--keep-reference-build', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
     scripts = _reference_scripts(ref)
     if stub:
@@ -140,6 +148,13 @@ def main(argv=None):
         patch.patch_sort(S)
         sys.argv = ['haphic sort'] + argv
         S.run(S.parse_arguments(), 'HapHiC_sort.log')               # == HapHiC_sort.main() :962-967
+        return 0
+    if command == 'build':
+        import HapHiC_build as B                                    # imports HapHiC_cluster for parse_fasta :17, with all it needs
+        if not keep_build:
+            patch.patch_build(B)
+        sys.argv = ['haphic build'] + argv
+        B.run(B.parse_arguments(), 'HapHiC_build.log')              # == HapHiC_build.main() :286-291
         return 0
     import HapHiC_cluster as H                                      # the unmodified reference module
     patch.patch_reference(H, ingest=not keep_ingest, allelic=not keep_allelic and ctx is None,      # the allelic, statistics and dense seams: one-rank jobs only

@@ -219,6 +219,14 @@ SIGNATURES = {
     'hhx_sort_graph_fetch_dense': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     'hhx_sort_graph_stats': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_sort_graph_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_fasta_open': (C.c_int, [C.c_char_p, C.c_int, c_vpp]),
+    'hhx_fasta_open_bytes': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, c_vpp]),
+    'hhx_fasta_counts': (C.c_int, [C.c_void_p, c_i64p, c_i64p, c_i64p]),
+    'hhx_fasta_table': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_fasta_sequences': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_fasta_emit': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                 c_i64p]),
+    'hhx_fasta_close': (C.c_int, [C.c_void_p]),
     'hhx_dmat_from_host': (C.c_int, [C.c_int32, C.c_void_p, c_vpp]),
     'hhx_dmat_from_csr': (C.c_int, [C.c_void_p, c_vpp]),
     'hhx_dmat_to_host': (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1053,6 +1061,76 @@ class Reassign:
     def close(self):
         if self.h is not None and self.h.value:
             load().hhx_reassign_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Fasta:
+    """hhx_fasta: one FASTA file parsed on the device (parse_fasta, HapHiC_cluster.py:87-113) — the sequences back to back in HBM, the table on the
+    host — and the writer of scaffolds.fa over it (build_final_scaffolds, HapHiC_build.py:153-168).  source: a path (str / os.PathLike) or the bytes
+    of the file.  tests/build_cases.py holds a numpy engine with the same interface.  Raises Unsupported where the library answers HHX_UNSUPPORTED."""
+
+    class Unsupported(RuntimeError):
+        pass
+
+    def __init__(self, source, keep_letter_case=False):
+        self.h = C.c_void_p()
+        if isinstance(source, (str, os.PathLike)):
+            rc = load().hhx_fasta_open(os.fsencode(source), int(bool(keep_letter_case)), C.byref(self.h))
+        else:
+            buf = np.frombuffer(source, np.uint8)
+            rc = load().hhx_fasta_open_bytes(ptr(buf) if buf.size else None, buf.size, int(bool(keep_letter_case)), C.byref(self.h))
+        self._check(rc)
+        n, ns, nn = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(load().hhx_fasta_counts(self.h, C.byref(n), C.byref(ns), C.byref(nn)))
+        self.n_ctg, self.n_seq_bytes = n.value, ns.value
+        self.seq_off, self.seq_len = np.zeros(self.n_ctg, np.int64), np.zeros(self.n_ctg, np.int64)
+        self.name_off, self.name_bytes = np.zeros(self.n_ctg + 1, np.int64), np.zeros(max(nn.value, 1), np.uint8)
+        check(load().hhx_fasta_table(self.h, ptr(self.seq_off), ptr(self.seq_len), ptr(self.name_off), ptr(self.name_bytes)))
+        self.name_bytes = self.name_bytes[:nn.value]
+
+    @staticmethod
+    def _check(rc):
+        if rc == GROUP_STATS_UNSUPPORTED:
+            raise Fasta.Unsupported(load().hhx_last_error().decode('utf-8', 'replace'))
+        check(rc)
+
+    def names(self):
+        """the contig names in file order (the text is ASCII: a byte >= 0x80 is refused)"""
+        blob, off = self.name_bytes.tobytes().decode('ascii'), self.name_off.tolist()
+        return [blob[off[k]:off[k + 1]] for k in range(self.n_ctg)]
+
+    def sequences(self):
+        """the sequences of all contigs, one after the other (uint8; contig k: [seq_off[k], seq_off[k] + seq_len[k]))"""
+        out = np.zeros(max(self.n_seq_bytes, 1), np.uint8)
+        check(load().hhx_fasta_sequences(self.h, ptr(out)))
+        return out[:self.n_seq_bytes]
+
+    def re_counts(self, sites):
+        """occurrences of the (N-expanded, bytes) sites per contig, int64 (count_RE_sites :75-84)"""
+        return count_re_sites(self.sequences(), self.seq_off, self.seq_len, sites)
+
+    def emit(self, path, rec_names, piece_off, piece_ctg, piece_rev, Ns, max_width):
+        """writes the records (rec_names: list of str; record r: pieces [piece_off[r], piece_off[r + 1]) = (contig id, reversed?)) as a FASTA file
+        of max_width columns, pieces joined by Ns 'N'.  -> bytes written"""
+        blob, off = names_blob(rec_names)
+        po, pc = np.ascontiguousarray(piece_off, np.int64), np.ascontiguousarray(piece_ctg, np.int32)
+        pr = np.ascontiguousarray(piece_rev, np.uint8)
+        if po.size != len(rec_names) + 1 or pc.size != pr.size or (po.size and pc.size != po[-1]):
+            raise ValueError('Fasta.emit: {} records, {} piece offsets, {} / {} pieces'.format(len(rec_names), po.size, pc.size, pr.size))
+        n = C.c_int64(0)
+        self._check(load().hhx_fasta_emit(self.h, os.fsencode(path), len(rec_names), ptr(blob), ptr(off), ptr(po), ptr(pc) if pc.size else None,
+                                          ptr(pr) if pr.size else None, int(Ns), int(max_width), C.byref(n)))
+        return n.value
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            load().hhx_fasta_close(self.h)
             self.h = None
 
     def __del__(self):

@@ -153,3 +153,84 @@ def slices_as_arrays(code, flat, ptr, width):
     step = width * flat.dtype.itemsize
     bounds = (np.asarray(ptr, np.int64) * step).tolist()
     return map(array, repeat(code), map(bytes, map(view.__getitem__, map(slice, bounds[:-1], bounds[1:]))))
+
+
+# ------------------------------------------------------------------ fa_dict of `haphic build` (haphic_amd/scaffolds.py)
+class ThawedFasta(dict):
+    """A FastaTable after its entries became real dict entries: the reference's fa_dict in all but the class name."""
+
+    @property
+    def frozen(self):
+        return False
+
+
+class FastaTable(dict):
+    """fa_dict (parse_fasta, HapHiC_cluster.py:87-113): {ctg: [seq, len, RE sites + 1]} whose sequences exist only in the memory of the device
+    (engine: _lib.Fasta or a stand-in with its interface).  len(), `in` and iteration over the names in file order are answered from the arrays —
+    what parse_tours :29-57 needs — and the build_final_scaffolds mirror works on `engine`, `names`, `lengths` and index_of().  ANY other access
+    ([], .items(), .values(), assignment, deletion, ...) thaws it first: the sequences come to the host (engine.sequences()), the RE sites are
+    counted (engine.re_counts(sites)), the object turns into a plain dict subclass and `frozen` is False for good."""
+
+    frozen = True
+
+    def __init__(self, engine, sites):
+        dict.__init__(self)
+        self.engine = engine
+        self.sites = list(sites)
+        self.names = engine.names()
+        self.lengths = np.asarray(engine.seq_len, np.int64)
+        self._index = None
+
+    def index_of(self, name):
+        """position of the contig in the file, -1 when it has none"""
+        if self._index is None:
+            self._index = dict(zip(self.names, range(len(self.names))))
+        return self._index.get(name, -1)
+
+    def _thaw(self):
+        if type(self) is ThawedFasta:
+            return
+        import time
+        t0 = time.perf_counter()
+        engine, names = self.engine, self.names
+        blob = engine.sequences().tobytes().decode('ascii')
+        counts = engine.re_counts(self.sites) if names else []
+        off, ln = np.asarray(engine.seq_off, np.int64).tolist(), self.lengths.tolist()
+        try:
+            dict.update(self, ((names[k], [blob[off[k]:off[k] + ln[k]], ln[k], int(counts[k]) + 1]) for k in range(len(names))))    # pseudo-count of 1 (:110)
+        except BaseException:
+            dict.clear(self)
+            raise
+        self.__dict__.clear()
+        self.__class__ = ThawedFasta
+        THAW_LOG.append(('fasta', dict.__len__(self), time.perf_counter() - t0))
+
+    # answered from the arrays
+    def __len__(self):
+        return len(self.names)
+
+    def __bool__(self):
+        return len(self.names) > 0
+
+    def __contains__(self, name):
+        return self.index_of(name) >= 0
+
+    def __iter__(self):
+        return iter(self.names)
+
+    def __copy__(self):
+        self._thaw()
+        return dict(self)
+
+    copy = __copy__
+
+    def __reduce_ex__(self, protocol):
+        self._thaw()
+        return dict, (), None, None, iter(dict.items(self))
+
+    __reduce__ = lambda self: self.__reduce_ex__(2)             # noqa: E731
+
+
+for _name in ('__getitem__', '__setitem__', '__delitem__', '__reversed__', 'keys', 'values', 'items', 'get', 'pop', 'popitem', 'setdefault', 'update',
+              'clear', '__eq__', '__ne__', '__repr__', '__or__', '__ror__', '__ior__'):
+    setattr(FastaTable, _name, _thawing(_name))

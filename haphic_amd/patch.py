@@ -229,6 +229,37 @@ def patch_sort(S, engine=None):
     return saved
 
 
+# `haphic build`: the two module globals run() :244-283 resolves at call time (haphic_amd/scaffolds.py)
+BUILD_SEAMS = {
+    'parse_fasta': 'HapHiC_cluster.py:87-113',           # bound into HapHiC_build by `from HapHiC_cluster import parse_fasta` :17
+    'build_final_scaffolds': 'HapHiC_build.py:74-179',
+}
+
+
+def patch_build(B, engine=None):
+    """B: the imported HapHiC_build module.  parse_fasta reads the FASTA file on the device and returns a containers.FastaTable, whose sequences
+    stay in HBM; build_final_scaffolds writes scaffolds.fa from them with one library call and both AGP files from the host arrays
+    (haphic_amd/scaffolds.py, which lists what is handed back to the reference's own functions).  parse_tours, parse_corrected_ctgs,
+    generate_juicebox_script and run() stay the reference's.  engine: a stand-in for _lib.Fasta (the tests' numpy engine).  Returns {name: original}."""
+    from . import scaffolds
+    if engine is None:
+        from . import _lib
+        _lib.load()
+    saved = {name: getattr(B, name) for name in BUILD_SEAMS}
+    original_fasta, original_build = saved['parse_fasta'], saved['build_final_scaffolds']
+
+    def parse_fasta(fasta, RE='GATC', keep_letter_case=False, logger=B.logger):
+        return scaffolds.parse_fasta(fasta, RE, keep_letter_case, logger, _original=original_fasta, _engine=engine)
+    parse_fasta.__wrapped__ = scaffolds.parse_fasta
+    B.parse_fasta = parse_fasta
+
+    def build_final_scaffolds(tour_dict, fa_dict, output_ctgs, corrected_ctg_set, args):
+        return scaffolds.build_final_scaffolds(tour_dict, fa_dict, output_ctgs, corrected_ctg_set, args, _original=original_build, _logger=B.logger)
+    build_final_scaffolds.__wrapped__ = scaffolds.build_final_scaffolds
+    B.build_final_scaffolds = build_final_scaffolds
+    return saved
+
+
 def unpatch_reference(H, saved):
     cluster.DENSE_SEAM_BOUND = False
     for name, fn in saved.items():

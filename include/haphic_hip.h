@@ -74,7 +74,8 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * hhx_ingest_group_stats (40 bytes each), rounded down to a power of two in [16, 2048] (default 2048; a contig with more distinct groups than slots takes
  * the table in HBM; same bits; hhx_reassign_round orders a row of that many groups in LDS (20 bytes each) and a wider one in HBM);
  * "reassign_window" = the most contigs of the visiting order one evaluation of hhx_reassign_round judges, clamped to [1, 4096] (default 512; same
- * results, other launch counts).  value INT64_MIN: back to the default.  Unset knobs fall back to the
+ * results, other launch counts); "fasta_slab" = bytes of scaffolds.fa that hhx_fasta_emit produces per kernel launch and hands to the file writer
+ * in one piece, rounded down to a multiple of 16 in [256, 2^26] (default 2^26; the same file, other seams).  value INT64_MIN: back to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
 int hhx_profile_enable(int on);
@@ -856,6 +857,35 @@ int hhx_sort_graph_patch_cells(hhx_sort_graph *g, int64_t n, const int64_t *cell
 int hhx_sort_graph_fetch_dense(hhx_sort_graph *g, int which, float *out);
 int hhx_sort_graph_stats(const hhx_sort_graph *g, int64_t *values);
 int hhx_sort_graph_destroy(hhx_sort_graph *g);
+
+/* ---------------------------------------------------------------- `haphic build`: FASTA reader and scaffold writer, haphic_amd/csrc/hhx_fasta.hip
+ * hhx_fasta_open / hhx_fasta_open_bytes — parse_fasta, scripts/HapHiC_cluster.py:87-113, on a file or on bytes in host memory; the whole text goes
+ *   to HBM in one piece.  Lines are Python's text-mode lines ('\n', "\r\n" and a lone '\r' end a line); a line that is empty after str.strip() is
+ *   skipped :95; a line whose FIRST RAW byte is '>' is a header :97 and names the contig line.split()[0][1:] :98 ('>' alone and "> x" name ''); every
+ *   other line is a sequence line: its bytes from the first to the last one that is no whitespace are kept, inner whitespace included, a-z folded to
+ *   A-Z unless keep_letter_case :101-104.  Contigs stand in file order; a header without sequence lines is a contig of length 0.  The handle holds the
+ *   sequences back to back in HBM, seq_off / seq_len per contig, and the names on the host.  Whitespace is the ASCII part of str.strip()'s.
+ *   HHX_UNSUPPORTED (hhx_last_error() says why, no handle is made): a byte >= 0x80 (the reference decodes by the locale); a sequence line in front of
+ *   the first header (the reference raises UnboundLocalError :102); text, sequences and one output slab beyond half of the device's memory; a path
+ *   that is no regular file.  Contigs of one name are NOT detected here (fa_dict[ctg] = list() :99 overwrites): the caller compares the names.
+ * hhx_fasta_counts: contigs, sequence bytes, name bytes (any pointer may be null).  hhx_fasta_table: seq_off [n_ctg], seq_len [n_ctg],
+ *   name_off [n_ctg + 1] and the names one after the other (any pointer may be null).  hhx_fasta_sequences: the sequence bytes, copied to the host.
+ * hhx_fasta_emit — the FASTA half of build_final_scaffolds, scripts/HapHiC_build.py:153-168: n_rec records in the order given; record r is
+ *   ">name\n" (rec_names / rec_name_off [n_rec + 1]), then its sequence in lines of max_width bytes, each followed by '\n', the last one possibly
+ *   shorter, none when the sequence is empty :159-160.  The sequence is the pieces [piece_off[r], piece_off[r + 1]) joined by Ns bytes of 'N' :84: piece k is
+ *   contig piece_ctg[k], as it is or (piece_rev[k] != 0) reversed and mapped through ATCGNatcgn -> TAGCNtagcn :83, :127-129, every other byte
+ *   unchanged; an unanchored contig :164-168 is a record of one forward piece.  All offsets are int64.  The file is produced in slabs of hhx_tune
+ *   "fasta_slab" bytes on the device and written while the next slab is produced; *n_bytes (may be null) = its size.  It is complete and closed on return;
+ *   after a failure it is removed.  HHX_UNSUPPORTED before the file is touched: max_width < 1, Ns < 0 or beyond 2^40, a record beyond 2^60 bytes. */
+typedef struct hhx_fasta hhx_fasta;
+int hhx_fasta_open(const char *path, int keep_letter_case, hhx_fasta **out);
+int hhx_fasta_open_bytes(const uint8_t *text, int64_t n_bytes, int keep_letter_case, hhx_fasta **out);
+int hhx_fasta_counts(const hhx_fasta *f, int64_t *n_ctg, int64_t *n_seq_bytes, int64_t *n_name_bytes);
+int hhx_fasta_table(const hhx_fasta *f, int64_t *seq_off, int64_t *seq_len, int64_t *name_off, uint8_t *names);
+int hhx_fasta_sequences(hhx_fasta *f, uint8_t *seq_host);
+int hhx_fasta_emit(hhx_fasta *f, const char *path, int64_t n_rec, const uint8_t *rec_names, const int64_t *rec_name_off, const int64_t *piece_off,
+                   const int32_t *piece_ctg, const uint8_t *piece_rev, int64_t Ns, int64_t max_width, int64_t *n_bytes);
+int hhx_fasta_close(hhx_fasta *f);
 
 #ifdef __cplusplus
 }
