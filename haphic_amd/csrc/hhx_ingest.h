@@ -194,8 +194,8 @@ struct PairGroups {
 int group_pairs(hhx_ingest *h, PairGroups &G, const char *who);
 }
 
-// hhx_matrix.hip: dict_to_matrix on a run (flank rows, first-seen order taken from ord_flank)
-int hhx_link_matrix_from_run(const hhx::LinkRun *run, i32 n_frag, u64 ord_limit, const uint8_t *in_set_host, i32 n_rest, int add_self_loops,
+// hhx_matrix.hip: dict_to_matrix on a run (flank rows, first-seen order taken from ord_flank; ordinals in [ord_base, ord_limit))
+int hhx_link_matrix_from_run(const hhx::LinkRun *run, i32 n_frag, u64 ord_base, u64 ord_limit, const uint8_t *in_set_host, i32 n_rest, int add_self_loops,
                              i32 *frag_index_host, i32 *n_linked_out, hhx_csr **out);
 
 // hhx_pairs.hip: paired_links.clm into an open file descriptor (closed there)

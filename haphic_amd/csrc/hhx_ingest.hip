@@ -931,7 +931,7 @@ extern "C" int hhx_ingest_link_matrix(hhx_ingest *h, const uint8_t *in_set_host,
                                       int32_t *frag_index_host, int32_t *n_linked, hhx_csr **out) {
     if (!h || !h->finalized) return fail("ingest handle not finalized");
     KTimer kt("link_matrix");
-    return hhx_link_matrix_from_run(h->table(1), h->t.n_frag, h->ord_limit, in_set_host, n_rest, add_self_loops, frag_index_host, n_linked, out);
+    return hhx_link_matrix_from_run(h->table(1), h->t.n_frag, h->ord_base, h->ord_limit, in_set_host, n_rest, add_self_loops, frag_index_host, n_linked, out);
 }
 
 extern "C" int hhx_ingest_destroy(hhx_ingest *h) {

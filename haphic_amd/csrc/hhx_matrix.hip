@@ -333,6 +333,12 @@ struct SrcDirectedPacked {
     unsigned long long *first_pos;          // [N_XCC][n_frag]; set in the object the level-1 count pass reads through, null otherwise
     unsigned int *too_big;
     i32 n_frag;
+    // the first-position cut (see mark_load): positions at or past cut_pos take no table read; park_mask + 1 is the largest power
+    // of two <= n_frag; n_reads counts the entries below the cut (device word, profile counter d2m_first_reads; a thread's share
+    // of it is a local of the kernel, handed to mark_apply and mark_flush: the source itself holds no state of a thread)
+    u64 cut_pos = ~0ull;
+    u32 park_mask = 0;
+    unsigned long long *n_reads = nullptr;
     // the loads of a record without a branch between them (hhx_partition.h: BATCHED): the three words of the table row, then
     // (!IN_LDS) the two membership words its key points at — every load of a chunk of records is in flight before the first is consumed
     typedef typename std::conditional<IN_LDS, PackedRawBase, PackedRawWords>::type Raw;
@@ -394,14 +400,40 @@ struct SrcDirectedPacked {
     __device__ __forceinline__ unsigned long long *my_table() const {
         return first_pos + (size_t)xcc_id() * (size_t)n_frag;
     }
+    // THE CUT.  The 100k minima settle in the first fraction of the stream; after that every one of these reads (a divergent
+    // 8-byte gather served by L2, 330 M a step at C3) returns a value its entry cannot beat.  An entry at or past cut_pos is
+    // therefore not compared at all: a fragment that has an entry below the cut has its minimum there, and a fragment all of
+    // whose entries lie past it keeps ~0 in the table and is found and repaired afterwards (k_first_unsettled, k_first_repair).
+    // Whether an entry is below the cut is known from the ord word load1 brought — nothing new to wait for.  The read of a skipped
+    // lane is not branched around (a branch per record puts every load of the chunk into a block of its own, each behind a
+    // vmcnt(0): hhx_partition.h, BATCHED) but PARKED: it goes to element idx & park_mask of the same table, consecutive lanes on
+    // consecutive words, so the skipped lanes of a wave share four 128-byte lines — which lines moves with the tile, over the
+    // whole table, so no L2 channel is singled out — and its value is never looked at (mark_apply tests the cut first).
     __device__ __forceinline__ u64 mark_load(i64 idx, const Raw &r) const {
         if (!first_pos) return 0;
-        return __hip_atomic_load(&my_table()[(idx & 1) ? frag_j(r) : frag_i(r)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const u32 side = (u32)(idx & 1);
+        const u32 f = side ? frag_j(r) : frag_i(r);
+        // (2 * r.ord + side is the pos decode_marked hands to mark_apply: this test and mark_apply's `pos < cut_pos` must stay the
+        //  same expression — were they to part, mark_apply would compare an entry with the word its read was parked on)
+        const u32 at = 2 * r.ord + side < cut_pos ? f : ((u32)idx & park_mask);
+        return __hip_atomic_load(&my_table()[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    __device__ __forceinline__ void mark_apply(u64 w0, u64 pos, u64 seen) const {
+    // reads: the calling thread's count of entries below the cut (mark_flush adds it up)
+    __device__ __forceinline__ void mark_apply(u64 w0, u64 pos, u64 seen, u32 &reads) const {
         if (!first_pos) return;
         if (pos == ~0ull) *too_big = 1u;                                            // 16-byte entries then (the caller starts over)
-        else if (pos < seen) atomicMin(&my_table()[(u32)(w0 >> (PK_ID_BITS + PK_CNT_BITS)) & PK_ID_MASK], (unsigned long long)pos);
+        else if (pos < cut_pos) {
+            ++reads;
+            if (pos < seen) atomicMin(&my_table()[(u32)(w0 >> (PK_ID_BITS + PK_CNT_BITS)) & PK_ID_MASK], (unsigned long long)pos);
+        }
+    }
+    // behind the last tile of the workgroup: one atomic a wave
+    __device__ __forceinline__ void mark_flush(u32 reads) const {
+        if (!first_pos) return;
+        u32 s = reads;
+#pragma unroll
+        for (int o = HHX_WAVE / 2; o > 0; o >>= 1) s += __shfl_down(s, o, HHX_WAVE);
+        if (lane_id() == 0 && s) atomicAdd(n_reads, (unsigned long long)s);
     }
 };
 constexpr int N_XCC = 8;
@@ -416,6 +448,37 @@ __global__ __launch_bounds__(256) void k_min_over_xcc(i32 n_frag, const unsigned
 struct DigRowPacked {
     __device__ __forceinline__ u32 operator()(u64 w0) const { return (u32)(w0 >> (PK_ID_BITS + PK_CNT_BITS)) & PK_ID_MASK; }
 };
+// What the cut got wrong.  UNSETTLED: a fragment that has entries (base[f + 1] > base[f]: the row partition counted them) and no
+// first position — every entry of it lies at or past the cut.  One bit per such fragment (bits zeroed by the caller) and their number.
+__global__ __launch_bounds__(256) void k_first_unsettled(i32 n_frag, const unsigned long long *__restrict__ first_pos, const i64 *__restrict__ base,
+                                                         u32 *__restrict__ bits, unsigned int *__restrict__ n_unsettled) {
+    // (the grid covers whole waves: every lane takes part in the ballot)
+    for (i32 f0 = blockIdx.x * blockDim.x; f0 < n_frag; f0 += gridDim.x * blockDim.x) {
+        const i32 f = f0 + threadIdx.x;
+        const bool un = f < n_frag && first_pos[f] == ~0ull && base[f + 1] > base[f];
+        if (un) atomicOr(&bits[f >> 5], 1u << (f & 31));
+        const unsigned long long m = __ballot(un);
+        if (lane_id() == 0 && m) atomicAdd(n_unsettled, (unsigned int)__popcll(m));
+    }
+}
+// ... and the repair: launched always, over at once when nothing is unsettled (the count is not read back in between).  Otherwise
+// the table is streamed once more — the source is the !IN_LDS one, its membership words gathered from global memory, entries decoded
+// exactly as the partition decodes them — and an entry whose row fragment is unsettled takes the parent's read (here of the merged
+// table: a stale value is only ever too large, and costs an atomic that changes nothing) and the atomic min.  Exact, not fast.
+__global__ __launch_bounds__(256) void k_first_repair(SrcDirectedPacked<false> src, i64 n, const u32 *__restrict__ bits,
+                                                      const unsigned int *__restrict__ n_unsettled, unsigned long long *first_pos) {
+    if (*n_unsettled == 0) return;
+    for (i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (i64)gridDim.x * blockDim.x) {
+        SrcDirectedPacked<false>::Raw r;
+        src.load1(idx, r);
+        src.load2(r);
+        u64 w0, pos;
+        if (!src.decode_marked(idx, r, w0, pos) || pos == ~0ull) continue;          // (a count too big: the count pass has said so)
+        const u32 row = DigRowPacked()(w0);
+        if (!((bits[row >> 5] >> (row & 31u)) & 1u)) continue;
+        if (pos < __hip_atomic_load(&first_pos[row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&first_pos[row], (unsigned long long)pos);
+    }
+}
 __global__ __launch_bounds__(256) void k_len_from_base(i32 n_frag, const i64 *__restrict__ base, const i32 *__restrict__ frag_index, i32 *__restrict__ cnt) {
     for (i32 f = blockIdx.x * blockDim.x + threadIdx.x; f < n_frag; f += gridDim.x * blockDim.x)
         if (frag_index[f] >= 0) cnt[frag_index[f]] += (i32)(base[f + 1] - base[f]);          // one writer per index
@@ -434,7 +497,10 @@ __global__ __launch_bounds__(256) void k_index_from_sorted(i64 n, const u64 *__r
         if (linked && (k + 1 == n || pos_sorted[k + 1] == ~0ull)) *n_linked = (unsigned int)(k + 1);
     }
 }
-int rank_first_positions(i32 n_frag, const unsigned long long *first_pos, u64 pos_limit, i32 *frag_index, unsigned int *n_linked_dev) {
+// the sort buffers belong to the caller, who keeps them until it next synchronises the stream (k_index_from_sorted reads them):
+// nothing here waits for the device on their account
+struct RankBufs { DevBuf<u64> iota, ks, vs; };
+int rank_first_positions(i32 n_frag, const unsigned long long *first_pos, u64 pos_limit, i32 *frag_index, unsigned int *n_linked_dev, RankBufs &bufs) {
     if (n_frag <= 4096) {
         k_rank_first<<<(unsigned)((n_frag + 255) / 256), 256, 0, g_stream>>>(n_frag, first_pos, frag_index, n_linked_dev);
         HHX_LAUNCH_CHECK();
@@ -442,14 +508,12 @@ int rank_first_positions(i32 n_frag, const unsigned long long *first_pos, u64 po
     }
     int bits = 1;
     while (bits < 64 && (pos_limit + 1) >> bits) ++bits;              // every real position < 2^bits - 1: ~0 keeps the top slot
-    DevBuf<u64> iota, ks, vs;
-    if (iota.alloc((size_t)n_frag) || ks.alloc((size_t)n_frag) || vs.alloc((size_t)n_frag)) return 1;
-    k_iota_u64<<<(unsigned)((n_frag + 255) / 256), 256, 0, g_stream>>>(n_frag, iota.p);
+    if (bufs.iota.alloc((size_t)n_frag) || bufs.ks.alloc((size_t)n_frag) || bufs.vs.alloc((size_t)n_frag)) return 1;
+    k_iota_u64<<<(unsigned)((n_frag + 255) / 256), 256, 0, g_stream>>>(n_frag, bufs.iota.p);
     HHX_LAUNCH_CHECK();
-    HHX_TRY(stable_sort_pairs_u64((const u64 *)first_pos, ks.p, iota.p, vs.p, n_frag, bits));
-    k_index_from_sorted<<<(unsigned)((n_frag + 255) / 256), 256, 0, g_stream>>>(n_frag, ks.p, vs.p, frag_index, n_linked_dev);
+    HHX_TRY(stable_sort_pairs_u64((const u64 *)first_pos, bufs.ks.p, bufs.iota.p, bufs.vs.p, n_frag, bits));
+    k_index_from_sorted<<<(unsigned)((n_frag + 255) / 256), 256, 0, g_stream>>>(n_frag, bufs.ks.p, bufs.vs.p, frag_index, n_linked_dev);
     HHX_LAUNCH_CHECK();
-    HHX_HIP(hipStreamSynchronize(g_stream));                           // ks / vs die here
     return 0;
 }
 
@@ -656,6 +720,18 @@ i32 d2m_lds_frags() {
     return v <= 0 ? 0 : (i32)std::min<long long>(v, D2M_LDS_MAX_FRAGS);
 }
 
+// The first-position cut as a position 2 * ordinal (SrcDirectedPacked::mark_load): HHX_D2M_FIRST_CUT ordinals from the ingest's
+// ordinal base, read at every launch (0: every linked fragment goes through the repair kernel; a very large value: every entry
+// takes the table read, as before the cut existed); unset: a sixteenth of the ordinals seen.  ~0: no cut.
+constexpr u64 D2M_FIRST_CUT_DIV = 16;
+u64 d2m_first_cut_pos(u64 ord_base, u64 ord_limit) {
+    const char *e = getenv("HHX_D2M_FIRST_CUT");
+    const u64 span = ord_limit > ord_base ? ord_limit - ord_base : 0;
+    const u64 count = e && *e ? (u64)strtoull(e, nullptr, 10) : (span + D2M_FIRST_CUT_DIV - 1) / D2M_FIRST_CUT_DIV;
+    if (count >= ((u64)1 << 62) || ord_base >= ((u64)1 << 62)) return ~0ull;
+    return 2 * (ord_base + count);
+}
+
 // positions of a row that the emit kernel stages in LDS per pass at most (HHX_EMIT_STAGE, read at every launch: a test places the pass
 // seams with it; unset: what LDS allows, 0: every entry stored directly from its thread)
 size_t emit_stage_cap() {
@@ -671,7 +747,7 @@ constexpr int EMIT_ROUNDS = 3;
 
 // PACKED: 8-byte entries (see SrcDirectedPacked); returns -2 when a count does not fit 24 bits (the caller takes the 16-byte path)
 template <bool PACKED>
-int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const uint8_t *in_set_host, i32 n_rest, int add_self_loops,
+int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_base, u64 ord_limit, const uint8_t *in_set_host, i32 n_rest, int add_self_loops,
                             i32 *frag_index_host, i32 *n_linked_out, hhx_csr **out) {
     typedef typename std::conditional<PACKED, NoPayload, u64>::type W1;
     DevBuf<unsigned char> in_set;                                // the 16-byte path reads the caller's bytes,
@@ -691,26 +767,48 @@ int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const
     while (((i64)1 << row_bits) < n_frag) ++row_bits;
     DevBuf<unsigned long long> first_pos;
     DevBuf<i32> frag_index, row_len;
-    DevBuf<unsigned int> nl;
-    if (first_pos.alloc((size_t)n_frag) || frag_index.alloc((size_t)n_frag) || nl.alloc(2)) return 1;
-    HHX_HIP(hipMemsetAsync(nl.p, 0, 2 * sizeof(unsigned int), g_stream));
+    // device words read back together: n_linked, "a count does not fit the packed entry", the fragments the first-position cut left
+    // unsettled, (padding), and — 64 bits — the entries that took the table read
+    struct Words { unsigned int n_linked, too_big, unsettled, pad; unsigned long long reads; };
+    DevBuf<Words> nl_buf;
+    DevBuf<u32> unsettled_bits;
+    if (first_pos.alloc((size_t)n_frag) || frag_index.alloc((size_t)n_frag) || nl_buf.alloc(1)) return 1;
+    HHX_HIP(hipMemsetAsync(nl_buf.p, 0, sizeof(Words), g_stream));
+    unsigned int *const nl = &nl_buf.p->n_linked;
     Partitioned<W1> part;
     static const int level_bits = getenv("HHX_D2M_LBITS") ? atoi(getenv("HHX_D2M_LBITS")) : 9;
     if constexpr (PACKED) {
         DevBuf<unsigned long long> per_xcc;
         if (per_xcc.alloc((size_t)N_XCC * (size_t)n_frag)) return 1;
         HHX_HIP(hipMemsetAsync(per_xcc.p, 0xff, sizeof(unsigned long long) * (size_t)N_XCC * (size_t)n_frag, g_stream));
+        const u64 cut_pos = d2m_first_cut_pos(ord_base, ord_limit);
+        u32 park = 1;
+        while ((u64)park * 2 <= (u64)n_frag) park *= 2;
         if (n_frag <= d2m_lds_frags()) {
             const SrcDirectedPacked<true> src{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, nullptr, nullptr, n_frag};
-            const SrcDirectedPacked<true> marking{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, per_xcc.p, nl.p + 1, n_frag};
+            const SrcDirectedPacked<true> marking{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, per_xcc.p, &nl_buf.p->too_big, n_frag,
+                                                  cut_pos, park - 1, &nl_buf.p->reads};
             HHX_TRY(partition_records(src, DigRowPacked(), 2 * run->n, row_bits, level_bits, &part, "d2m", &marking));
         } else {
             const SrcDirectedPacked<false> src{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, nullptr, nullptr, n_frag};
-            const SrcDirectedPacked<false> marking{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, per_xcc.p, nl.p + 1, n_frag};
+            const SrcDirectedPacked<false> marking{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, per_xcc.p, &nl_buf.p->too_big, n_frag,
+                                                   cut_pos, park - 1, &nl_buf.p->reads};
             HHX_TRY(partition_records(src, DigRowPacked(), 2 * run->n, row_bits, level_bits, &part, "d2m", &marking));
         }
         k_min_over_xcc<<<grid_for((u64)n_frag), 256, 0, g_stream>>>(n_frag, per_xcc.p, first_pos.p);
         HHX_LAUNCH_CHECK();
+        // the fragments the cut got wrong (none without entries: base is per fragment only when the partition ran all its levels)
+        if (part.n_valid && cut_pos != ~0ull) {
+            KTimer kt("d2m_first_repair");
+            const size_t n_words = ((size_t)n_frag + 31) / 32;
+            if (unsettled_bits.alloc(n_words)) return 1;
+            HHX_HIP(hipMemsetAsync(unsettled_bits.p, 0, sizeof(u32) * n_words, g_stream));
+            k_first_unsettled<<<grid_for((u64)n_frag), 256, 0, g_stream>>>(n_frag, first_pos.p, part.base.p, unsettled_bits.p, &nl_buf.p->unsettled);
+            HHX_LAUNCH_CHECK();
+            const SrcDirectedPacked<false> again{run->key.p, run->ord_flank.p, run->fl.p, in_bits.p, nullptr, nullptr, n_frag};
+            k_first_repair<<<grid_for((u64)(2 * run->n)), 256, 0, g_stream>>>(again, 2 * run->n, unsettled_bits.p, &nl_buf.p->unsettled, first_pos.p);
+            HHX_LAUNCH_CHECK();
+        }
         // (whether a count was too big for the packed entry is read back together with n_linked, below)
     } else {
         const SrcDirected src{run->key.p, run->ord_flank.p, run->fl.p, in_set.p};
@@ -725,15 +823,21 @@ int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const
         }
         HHX_LAUNCH_CHECK();
     }
+    RankBufs rank_bufs;                                          // (live until the synchronisation below)
     { KTimer kt("d2m_rank");
-    HHX_TRY(rank_first_positions(n_frag, first_pos.p, 2 * ord_limit + 1, frag_index.p, nl.p)); }
-    unsigned int nl_host[2] = {0, 0};                             // n_linked, "a count does not fit the packed entry"
-    HHX_HIP(hipMemcpyAsync(nl_host, nl.p, sizeof nl_host, hipMemcpyDeviceToHost, g_stream));
+    HHX_TRY(rank_first_positions(n_frag, first_pos.p, 2 * ord_limit + 1, frag_index.p, nl, rank_bufs)); }
+    Words nl_host{};
+    HHX_HIP(hipMemcpyAsync(&nl_host, nl_buf.p, sizeof nl_host, hipMemcpyDeviceToHost, g_stream));
     if (!PACKED && n_rest < 0)                                   // counted while the device works (the packed path counted while it packed)
         for (i32 f = 0; f < n_frag; ++f) members += in_set_host[f] != 0;
     HHX_HIP(hipStreamSynchronize(g_stream));
-    if (PACKED && nl_host[1]) return -2;
-    const unsigned int n_linked = nl_host[0];
+    rank_bufs = RankBufs();
+    if (PACKED && nl_host.too_big) return -2;
+    if (PACKED) {
+        prof_count("d2m_first_unsettled", (i64)nl_host.unsettled);
+        prof_count("d2m_first_reads", (i64)nl_host.reads);
+    }
+    const unsigned int n_linked = nl_host.n_linked;
     if (n_rest < 0) n_rest = (i32)(members - (i64)n_linked);
     const i64 shape64 = (i64)n_linked + n_rest;
     if (shape64 > INT32_MAX) return fail("matrix order exceeds int32");
@@ -802,16 +906,16 @@ int link_matrix_partitioned(const LinkRun *run, i32 n_frag, u64 ord_limit, const
 
 }  // namespace
 
-int hhx_link_matrix_from_run(const LinkRun *run, i32 n_frag, u64 ord_limit, const uint8_t *in_set_host, i32 n_rest, int add_self_loops,
+int hhx_link_matrix_from_run(const LinkRun *run, i32 n_frag, u64 ord_base, u64 ord_limit, const uint8_t *in_set_host, i32 n_rest, int add_self_loops,
                              i32 *frag_index_host, i32 *n_linked_out, hhx_csr **out) {
     if (!out || !in_set_host || n_frag <= 0) return fail("hhx_ingest_link_matrix: bad argument");
     // packed entries hold 2*ordinal+side in 33 bits and the count in 31: true whenever < 2^31 pairs were seen
     if (run && run->n && n_frag <= (1 << 20) && ord_limit <= ((u64)1 << 31) && !getenv("HHX_D2M_GENERIC")) {
         if (!getenv("HHX_D2M_WIDE")) {                           // 8-byte entries unless a count needs more than 24 bits
-            const int rc = link_matrix_partitioned<true>(run, n_frag, ord_limit, in_set_host, n_rest, add_self_loops, frag_index_host, n_linked_out, out);
+            const int rc = link_matrix_partitioned<true>(run, n_frag, ord_base, ord_limit, in_set_host, n_rest, add_self_loops, frag_index_host, n_linked_out, out);
             if (rc != -2) return rc;
         }
-        return link_matrix_partitioned<false>(run, n_frag, ord_limit, in_set_host, n_rest, add_self_loops, frag_index_host, n_linked_out, out);
+        return link_matrix_partitioned<false>(run, n_frag, ord_base, ord_limit, in_set_host, n_rest, add_self_loops, frag_index_host, n_linked_out, out);
     }
     const RunView vw{run ? run->key.p : nullptr, run ? run->ord_flank.p : nullptr, run ? run->fl.p : nullptr};
     return build_matrix(vw, run ? run->n : 0, n_frag, in_set_host, n_rest, add_self_loops, frag_index_host, n_linked_out, out);

@@ -113,6 +113,7 @@ __global__ __launch_bounds__(PT) void k_part_count(Src src_arg, Dig dig, i64 n, 
         lds_barrier();
     }
     u32 cur = 0xffffffffu;
+    u32 marked = 0;                                              // (MARK) what the side effect counts for this thread: mark_apply, mark_flush
     const i64 n_tiles = (n + P_TILE - 1) / P_TILE;
     for (i64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const i64 base = tile * P_TILE;
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(PT) void k_part_count(Src src_arg, Dig dig, i64 n, 
         }
         if constexpr (Src::BATCHED) {
             // the loads of a chunk of records, then the gathers that depend on them — for a source with a side effect per record
-            // (MARK: mark_load / mark_apply) the load the side effect needs rides with those gathers — then the histogram and the
+            // (MARK: mark_load / mark_apply, mark_flush at the kernel's end) the load the side effect needs rides with those gathers — then the histogram and the
             // side effect's (rare) atomics: an atomic inside the load loop would pin the loads of the following records behind it
             constexpr int CH = Src::CHUNK < P_ITEMS ? Src::CHUNK : P_ITEMS;
 #pragma unroll
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(PT) void k_part_count(Src src_arg, Dig dig, i64 n, 
                         if constexpr (Src::MARK) ok = src.decode_marked(idx, raw[k], w0, extra);
                         else { typename Src::w1_t w1; ok = src.decode(idx, raw[k], w0, w1); }
                         if (idx < n && ok) {
-                            if constexpr (Src::MARK) src.mark_apply(w0, extra, seen[k]);
+                            if constexpr (Src::MARK) src.mark_apply(w0, extra, seen[k], marked);
                             const u32 d = dig(w0) >> L.shift;
                             if ((d >> L.lds_bits) == tg) atomicAdd(&hist[d & (u32)(nb - 1)], 1u);
                             else atomicAdd(&ghist[d], 1ull);
@@ -183,6 +184,7 @@ __global__ __launch_bounds__(PT) void k_part_count(Src src_arg, Dig dig, i64 n, 
     if (cur != 0xffffffffu)
         for (int t = tid; t < nb; t += PT)
             if (hist[t]) atomicAdd(&ghist[((u64)cur << L.lds_bits) | (u64)t], (unsigned long long)hist[t]);
+    if constexpr (Src::MARK) src.mark_flush(marked);             // one sum per wave (every thread is here)
 }
 
 template <class W1, int T>

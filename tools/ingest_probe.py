@@ -15,7 +15,7 @@ from haphic_amd import _lib, synth  # noqa: E402
 from haphic_amd.cluster import FragTable  # noqa: E402
 
 NAMES = ('ingest', 'map', 'part_count1', 'part_scatter1', 'part_count2', 'part_scatter2', 'part_count3', 'part_scatter3', 'aggregate',
-         'link_matrix', 'd2m_first', 'd2m_count1', 'd2m_scatter1', 'd2m_count2', 'd2m_scatter2', 'd2m_row_first', 'd2m_rank', 'd2m_emit')
+         'link_matrix', 'd2m_first', 'd2m_count1', 'd2m_scatter1', 'd2m_count2', 'd2m_scatter2', 'd2m_first_repair', 'd2m_row_first', 'd2m_rank', 'd2m_emit')
 
 
 def main():
@@ -48,6 +48,8 @@ def main():
         del m
     _lib.profile_enable(False)
     print(json.dumps({'probe': 'ingest', 'pairs': pairs, 'contigs': int(gen.n), 'nnz': int(nnz), 'wall_ms': wall, 'wall_ms_min': min(wall),
+                      'first_cut': os.environ.get('HHX_D2M_FIRST_CUT'),
+                      'counters': {k: _lib.profile_counter(k) // steps for k in ('d2m_first_reads', 'd2m_first_unsettled')},
                       'kernel_ms': {k: round(_lib.profile_get(k)[0] / steps, 3) for k in NAMES if _lib.profile_get(k)[1]}}))
 
 

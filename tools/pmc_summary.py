@@ -2,7 +2,11 @@
 """rocprofv3 --pmc counter_collection.csv files (one pass per counter group, gpurun_out/pmc_*/) ->
 profiles/pmc_traffic.json + a per-kernel table.  HBM/fabric bytes follow MI355X_MICROARCH.md §HBM:
 FETCH_SIZE / WRITE_SIZE are reported in KB; on gfx950 FETCH_SIZE tallies 128-byte read requests at 64 bytes,
-so streaming reads are doubled (the TCC_MISS x 128 B figure of the same run is printed beside it as a check)."""
+so streaming reads are doubled (the TCC_MISS x 128 B figure of the same run is printed beside it as a check).
+
+usage: pmc_summary.py ROOT CONTIGS PAIRS OUT_JSON OUT_TXT.  CONTIGS and PAIRS are config.contigs and config.pairs_per_gpu of the bench
+line of the profiled command — the generator's contig count (99878 for --contigs 100000), not the --contigs argument: bench.py
+reports roofline.traffic only while both, and the hash of the kernel sources, match its own run."""
 import collections
 import csv
 import json
