@@ -51,6 +51,12 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
   --keep-reference-build     build only: leave parse_fasta and build_final_scaffolds to the reference's per-line and per-60-bases Python loops.  Without the
                              flag a call still goes to the reference's function for a FASTA file with a byte >= 0x80, with a sequence line in front of
                              the first header, with a contig name that repeats, or beyond half of the device's memory, and for --max_width < 1 or --Ns < 0
+  --keep-reference-verdict   sort only: leave compare_fast_sort_and_allhic :645-724 (fast sorting or ALLHiC, per group) to the reference's loop: for each of the
+                             n - 1 rotations of the fast-sort tour two O(n^2) weighted longest-increasing-subsequence passes in Python.  Without the flag the
+                             sums of all rotations come from one device call (haphic_amd/sort.py bind_verdict: one wavefront per rotation, csrc/hhx_sortverdict.hip)
+                             and the ratio rule, the threshold and the log lines stay in Python: same verdict, same log line.  A call still goes to the
+                             reference's function for a group of one contig, an ALLHiC tour that is no permutation of the fast-sort tour, a length that
+                             is not a non-negative int, and beyond 2^18 contigs
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
@@ -112,6 +118,7 @@ def main(argv=None):
     keep_dense = bool(_take(argv, '--keep-reference-dense', False))
     keep_rounds = bool(_take(argv, '--keep-reference-rounds', False))
     keep_build = bool(_take(argv, '--keep-reference-build', False))
+    keep_verdict = bool(_take(argv, '--keep-reference-verdict', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
     scripts = _reference_scripts(ref)
     if stub:
@@ -145,7 +152,7 @@ def main(argv=None):
         import HapHiC_sort as S                                     # needs networkx / scipy, as the reference does
         from . import sort
         sort.DEVICE = device                                        # the pool's threads select it before their first call
-        patch.patch_sort(S)
+        patch.patch_sort(S, verdict=not keep_verdict)
         sys.argv = ['haphic sort'] + argv
         S.run(S.parse_arguments(), 'HapHiC_sort.log')               # == HapHiC_sort.main() :962-967
         return 0

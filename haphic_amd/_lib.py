@@ -219,6 +219,7 @@ SIGNATURES = {
     'hhx_sort_graph_fetch_dense': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     'hhx_sort_graph_stats': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_sort_graph_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_sort_verdict_sums': (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'hhx_fasta_open': (C.c_int, [C.c_char_p, C.c_int, c_vpp]),
     'hhx_fasta_open_bytes': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, c_vpp]),
     'hhx_fasta_counts': (C.c_int, [C.c_void_p, c_i64p, c_i64p, c_i64p]),
@@ -944,6 +945,32 @@ class SortGraph:
             self.close()
         except Exception:
             pass
+
+
+class SortVerdictUnsupported(RuntimeError):
+    """hhx_sort_verdict_sums answered HHX_UNSUPPORTED: the caller takes the reference's function"""
+
+
+SORT_VERDICT_STATS = ('lds_rotations', 'hbm_rotations', 'cell_bytes')
+
+
+def sort_verdict_sums(value, lengths, r0=0, r1=None, want_stats=False):
+    """hhx_sort_verdict_sums: the weighted-LIS sums s[r0 .. r1) of compare_fast_sort_and_allhic (HapHiC_sort.py :696-721) as int64; value[i] = +-(pos + 1)
+    of element i of the fast-sort tour, lengths[i] its contig length; r1 None: n - 1, every rotation the reference looks at.  want_stats: (sums, dict
+    of SORT_VERDICT_STATS).  tests/sort_verdict_cases.py holds a host engine with the same signature.  Raises SortVerdictUnsupported where the library
+    answers HHX_UNSUPPORTED."""
+    v, ln = np.ascontiguousarray(value, np.int32), np.ascontiguousarray(lengths, np.int64)
+    if v.ndim != 1 or v.shape != ln.shape:
+        raise ValueError('sort_verdict_sums: {} values, {} lengths'.format(v.shape, ln.shape))
+    n = int(v.size)
+    r1 = n - 1 if r1 is None else int(r1)
+    sums = np.zeros(max(r1 - int(r0), 0), np.int64)
+    stats = np.zeros(len(SORT_VERDICT_STATS), np.int64)
+    rc = load().hhx_sort_verdict_sums(n, ptr(v), ptr(ln), int(r0), r1, ptr(sums), ptr(stats))
+    if rc == GROUP_STATS_UNSUPPORTED:
+        raise SortVerdictUnsupported(load().hhx_last_error().decode('utf-8', 'replace'))
+    check(rc)
+    return (sums, dict(zip(SORT_VERDICT_STATS, (int(x) for x in stats)))) if want_stats else sums
 
 
 def write_link_pickle_async(path, i, j, count, names):

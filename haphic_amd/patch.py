@@ -208,19 +208,30 @@ SORT_SEAMS = {
 }
 
 
-def patch_sort(S, engine=None):
+# fast sorting or ALLHiC, per group (haphic_amd/sort.py bind_verdict).  OPT-IN, like `allelic` / `statistics` / `dense` above: what patch_sort(S) binds by
+# default stays what it was.
+SORT_VERDICT_SEAMS = {
+    'compare_fast_sort_and_allhic': 'HapHiC_sort.py:645-724',
+}
+
+
+def patch_sort(S, engine=None, verdict=False, verdict_engine=None):
     """S: the imported HapHiC_sort module.  The dense work of fast sorting goes to the device (haphic_amd/sort.py); fast_sort, the spanning forest,
     split_new_scaffold, the .tour writer, the ALLHiC child and run() stay the reference's.  run() :875-876 forks a multiprocessing.Pool: a process
     that has initialised the GPU must not be forked into workers that use it, so S.Pool becomes the ThreadPool (same apply_async / close / join);
     one lock serialises the device part across its threads, the ALLHiC children run beside it.  engine: a stand-in for _lib.SortGraph (the tests'
-    numpy engine).  Returns {name: original}."""
+    numpy engine).  verdict=True: compare_fast_sort_and_allhic :645-724 (which tour final_tours/<group>.tour links to) is re-bound too: the weighted-LIS
+    sums of all rotations come from one library call; verdict_engine: a stand-in for _lib.sort_verdict_sums (the tests' host engine); `python -m
+    haphic_amd sort` asks for it.  Returns {name: original}."""
     from multiprocessing.pool import ThreadPool
     from . import sort
-    if engine is None:
+    if engine is None or (verdict and verdict_engine is None):
         from . import _lib
         _lib.load()
     mirrors = sort.bind(S, engine)
     assert set(mirrors) == set(SORT_SEAMS)
+    if verdict:
+        mirrors['compare_fast_sort_and_allhic'] = sort.bind_verdict(S, verdict_engine)
     saved = {name: getattr(S, name) for name in mirrors}
     saved['Pool'] = S.Pool
     for name, fn in mirrors.items():

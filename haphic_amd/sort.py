@@ -12,7 +12,11 @@ the functions below replace the module globals fast_sort resolves at call time (
 
 What the device path does not cover (weights that are not non-negative integers, an empty dict, a shape below 4) is decided once, in round 1:
 dict_to_matrix then returns the reference's numpy matrix and every seam hands such a group to the original functions.  The new sub_HT_dict is a
-SubHT: a defaultdict that stays arrays until something other than these seams touches it (the pattern of containers.py)."""
+SubHT: a defaultdict that stays arrays until something other than these seams touches it (the pattern of containers.py).
+
+bind_verdict: compare_fast_sort_and_allhic :645-724, which run_haphic_sorting :748 calls per group once fast sorting and ALLHiC have both run.  The
+weighted-LIS sums of the rotations :696-721 come from one library call (_lib.sort_verdict_sums); parse_tours, the ratio rule :683-688, the threshold
+:712-716 and both log lines stay here, in Python ints and floats."""
 import threading
 from itertools import product
 
@@ -264,3 +268,65 @@ def bind(S, engine=None):
 
     return {'dict_to_matrix': dict_to_matrix, 'get_density_graph': get_density_graph, 'get_unfiltered_confidence_graph': get_unfiltered_confidence_graph,
             'filter_confidence_graph': filter_confidence_graph, 'remove_shortest_path': remove_shortest_path, 'update': update, 'fast_sort': fast_sort}
+
+
+# ------------------------------------------------------------------ fast sorting or ALLHiC: compare_fast_sort_and_allhic :645-724
+class VerdictUnsupported(RuntimeError):
+    """raised by a verdict engine for a group it does not serve: the mirror hands the call to the reference's function"""
+
+
+def _default_verdict_engine(value, lengths, r0, r1):
+    from . import _lib
+    if DEVICE is not None:
+        _lib.check(_lib.load().hhx_set_device(DEVICE))
+    try:
+        return _lib.sort_verdict_sums(value, lengths, r0, r1)
+    except _lib.SortVerdictUnsupported as e:
+        raise VerdictUnsupported(str(e))
+
+
+def bind_verdict(S, engine=None):
+    """The mirror of compare_fast_sort_and_allhic for the imported HapHiC_sort module S.  engine(value, lengths, r0, r1) -> the sums s[r0 .. r1) of
+    include/haphic_hip.h's hhx_sort_verdict_sums (the device by default); it may raise VerdictUnsupported.
+
+    Handed to the original function, which then raises or answers as it always did (and parses the tours again, so `Parsing tour files...` is logged
+    once more): fewer than two contigs (:723 raises), a length that is not a non-negative int or lengths summing to 2^62 and more, an ALLHiC tour that
+    is no permutation of the fast-sort tour (.index :699 raises, or longer), an engine that raises VerdictUnsupported."""
+    sums_of = engine or _default_verdict_engine
+    original = S.compare_fast_sort_and_allhic
+
+    def compare_fast_sort_and_allhic(prefix, fa_dict):
+        fast = list(S.parse_tours(['{}.tour.sav'.format(prefix)], fa_dict)[0].values())[0]
+        n = len(fast)
+        lengths = [fa_dict[ctg] for ctg, _ori in fast]
+        if n < 2 or any(type(x) is not int or x < 0 for x in lengths):
+            return original(prefix, fa_dict)
+        group_len = sum(lengths)
+        if group_len >= 1 << 62:
+            return original(prefix, fa_dict)
+        ratio = group_len / max(lengths)
+        if ratio > 50:
+            S.logger.info('{}: choose allhic optimization (group length / longest contig = {})'.format(prefix, ratio))
+            return False
+        allhic = list(S.parse_tours(['{}.tour'.format(prefix)], fa_dict)[0].values())[0]
+        where = {ctg: (j, ori) for j, (ctg, ori) in enumerate(allhic)}
+        if len(allhic) != n or any(ctg not in where for ctg, _ori in fast):
+            return original(prefix, fa_dict)
+        value = [where[ctg][0] + 1 if ori == where[ctg][1] else -where[ctg][0] - 1 for ctg, ori in fast]
+        try:
+            with DEVICE_LOCK:                                  # called from the threads of run()'s pool
+                sums = [int(x) for x in sums_of(value, lengths, 0, 1)]
+            if sums[0] / group_len < 0.9 and n > 2:            # rotation 0 settles it when the tours agree (the reference's early exit :714)
+                with DEVICE_LOCK:
+                    sums += [int(x) for x in sums_of(value, lengths, 1, n - 1)]
+        except VerdictUnsupported:
+            return original(prefix, fa_dict)
+        for max_sum in sums:
+            if max_sum / group_len >= 0.9:
+                S.logger.info('{}: choose allhic optimization (LIS length / group length = {})'.format(prefix, max_sum / group_len))
+                return False
+        # :723 prints the ratio of the last rotation looked at, whatever its wording says
+        S.logger.info('{}: choose fast sorting (maximum LIS length / group length = {})'.format(prefix, sums[-1] / group_len))
+        return True
+    compare_fast_sort_and_allhic.__wrapped__ = original
+    return compare_fast_sort_and_allhic

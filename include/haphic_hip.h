@@ -75,7 +75,10 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * the table in HBM; same bits; hhx_reassign_round orders a row of that many groups in LDS (20 bytes each) and a wider one in HBM);
  * "reassign_window" = the most contigs of the visiting order one evaluation of hhx_reassign_round judges, clamped to [1, 4096] (default 512; same
  * results, other launch counts); "fasta_slab" = bytes of scaffolds.fa that hhx_fasta_emit produces per kernel launch and hands to the file writer
- * in one piece, rounded down to a multiple of 16 in [256, 2^26] (default 2^26; the same file, other seams).  value INT64_MIN: back to the default.  Unset knobs fall back to the
+ * in one piece, rounded down to a multiple of 16 in [256, 2^26] (default 2^26; the same file, other seams); "sort_verdict_lds_n" = the largest n whose
+ * rotations hhx_sort_verdict_sums runs with their tree in LDS, clamped to [0, 40959] (4-byte cells: lengths summing to less than 2^32) or [0, 20479]
+ * (8-byte cells) (default 4095 / 2047: a tree of 16 KiB, above which a CU holds too few rotations to hide a step's latency; 0: every rotation on its
+ * scratch slab in HBM; same bits).  value INT64_MIN: back to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
 int hhx_profile_enable(int on);
@@ -857,6 +860,23 @@ int hhx_sort_graph_patch_cells(hhx_sort_graph *g, int64_t n, const int64_t *cell
 int hhx_sort_graph_fetch_dense(hhx_sort_graph *g, int which, float *out);
 int hhx_sort_graph_stats(const hhx_sort_graph *g, int64_t *values);
 int hhx_sort_graph_destroy(hhx_sort_graph *g);
+
+/* ---------------------------------------------------------------- `haphic sort`: fast sorting or ALLHiC (HapHiC_sort.py compare_fast_sort_and_allhic :645-724)
+ * hhx_sort_verdict_sums — the sums behind the verdict, in place of the rotation loop :696-721 with its two find_lis passes :647-672 and its .index sweep
+ *   :698-705 (csrc/hhx_sortverdict.hip).  value[n]: the compare_list :697-705 of rotation 0, element i of the fast-sort tour -> +(pos + 1) if its
+ *   orientation equals the one in the ALLHiC tour, -(pos + 1) otherwise, pos its index there; the magnitudes are a permutation of 1 .. n.  len[n]: the
+ *   contig lengths (order_len_dict), >= 0, summing to less than 2^62.  Rotation r is the sequence i = (r + k) mod n, k = 0 .. n - 1 (:720-721);
+ *   sums[r - r0] = max(find_lis(forward), find_lis(reverse)) of rotation r for r0 <= r < r1 <= n - 1: the largest total length of a subsequence of one
+ *   sign with strictly increasing signed values, 0 for an empty class — exact int64.  The n-th rotation is never looked at (:696).  The ratio rule
+ *   :683-688, the 0.9 threshold :712-716, the early exit and the log lines stay with the caller, who asks for [0, 1) first and for the rest when that
+ *   does not settle the verdict.  One wavefront per rotation; its Fenwick tree lives in LDS up to n = 4095 (lengths summing to less than 2^32: 4-byte
+ *   cells) or 2047 (8-byte cells) by default, up to 40959 / 20479 with hhx_tune "sort_verdict_lds_n"; above that in a per-workgroup slab of a scratch
+ *   buffer of at most 1 GiB in HBM, rotations taken in turns.  stats[HHX_SORT_VERDICT_N_STATS] (may be null): rotations run in the LDS form, in the HBM form, bytes per tree cell.
+ *   Errors: n < 2, a value of 0 or of magnitude above n, a magnitude twice, a negative length, lengths summing to 2^62 or more, a rotation range
+ *   outside [0, n - 1].  HHX_UNSUPPORTED: n above HHX_SORT_VERDICT_MAX_N (2^18 contigs; a rotation is n sequential steps). */
+#define HHX_SORT_VERDICT_N_STATS 3
+#define HHX_SORT_VERDICT_MAX_N 262144
+int hhx_sort_verdict_sums(int32_t n, const int32_t *value, const int64_t *len, int32_t r0, int32_t r1, int64_t *sums, int64_t *stats);
 
 /* ---------------------------------------------------------------- `haphic build`: FASTA reader and scaffold writer, haphic_amd/csrc/hhx_fasta.hip
  * hhx_fasta_open / hhx_fasta_open_bytes — parse_fasta, scripts/HapHiC_cluster.py:87-113, on a file or on bytes in host memory; the whole text goes
