@@ -37,6 +37,15 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              the link counts are floats or --normalize_by_nlinks is on, a whitelist is given, --min_links is below 1, the log
                              level is DEBUG (the per-contig lines), a link or RE total reaches 2^53, or the cells of contigs x groups do not
                              fit in half of the device's memory
+  --keep-reference-pickle    reassign only: leave parse_pickle :38-50 to pickle.load, which builds full_link_dict as a Python dict of every key of
+                             full_links.pkl (tens of GB of objects at 100k contigs) that parse_link_dict then flattens again.  Without the flag the
+                             file is read into arrays on the device (csrc/hhx_pickleread.hip) and full_link_dict is an array-backed table that
+                             parse_link_dict, the rounds and the agglomerative step consume without turning it into a dict.  A file still goes through
+                             pickle.load when it is not a protocol 4 / 5 pickle of a collections.defaultdict(int), holds any opcode besides names of
+                             at most 255 bytes, 2-tuples, integers of at most 64 bits and floats in MARK .. SETITEMS / SETITEM batches (3-tuple keys,
+                             True / None values, 2^63 ...), refers to a memo slot that holds no name, writes a key twice, ends early, has bytes
+                             after STOP or frames that do not tile it, mixes floats with integers beyond 2^53, or is larger than half of the
+                             device's memory
   --keep-reference-statistics  cluster only: leave output_statistics :2279-2478 (the *_statistics.txt files and statistics.pdf of every inflation) to the
                              reference's per-contig loop over ctg_group_link_dict, which is rebuilt as Python dicts once per inflation.  Without the
                              flag a one-rank job takes the per-contig numbers of all inflations from one device call on the frozen full_link_dict
@@ -117,6 +126,7 @@ def main(argv=None):
     keep_statistics = bool(_take(argv, '--keep-reference-statistics', False))
     keep_dense = bool(_take(argv, '--keep-reference-dense', False))
     keep_rounds = bool(_take(argv, '--keep-reference-rounds', False))
+    keep_pickle = bool(_take(argv, '--keep-reference-pickle', False))
     keep_build = bool(_take(argv, '--keep-reference-build', False))
     keep_verdict = bool(_take(argv, '--keep-reference-verdict', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
@@ -144,7 +154,7 @@ def main(argv=None):
         return 0
     if command == 'reassign':
         import HapHiC_reassign as R                                 # needs pysam / sklearn, as the reference does
-        patch.patch_reassign(R, rounds=not keep_rounds)
+        patch.patch_reassign(R, rounds=not keep_rounds, pickle=not keep_pickle)
         sys.argv = ['haphic reassign'] + argv
         R.run(R.parse_arguments(), 'HapHiC_reassign.log')           # == HapHiC_reassign.main() :919-924
         return 0

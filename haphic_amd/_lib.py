@@ -187,6 +187,10 @@ SIGNATURES = {
     'hhx_clm_split_finish': (C.c_int, [C.c_void_p, c_i64p, c_i64p, C.c_void_p]),
     'hhx_clm_split_stats': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_clm_split_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_pickle_open': (C.c_int, [C.c_char_p, c_vpp]),
+    'hhx_pickle_sizes': (C.c_int, [C.c_void_p, c_i64p, c_i32p, c_i64p, C.POINTER(C.c_int)]),
+    'hhx_pickle_fetch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_pickle_free': (C.c_int, [C.c_void_p]),
     'hhx_files_pending': (C.c_int, [c_i64p, c_i64p]),
     'hhx_files_join': (C.c_int, [c_i64p]),
     'hhx_correct_create': (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, c_vpp]),
@@ -684,6 +688,50 @@ def write_link_pickle(path, i, j, count, names):
     check(load().hhx_write_link_pickle(os.fsencode(path), fi.size, ptr(fi), ptr(fj), ptr(cnt), len(names), ptr(blob), ptr(off),
                                        C.byref(n_bytes)))
     return n_bytes.value
+
+
+PICKLE_NOT_OURS = 2                  # HHX_PICKLE_NOT_OURS
+PICKLE_REFUSALS = []                 # hhx_last_error() of every file read_link_pickle handed back in this process
+
+
+def read_link_pickle(path):
+    """full_links.pkl / HT_links.pkl -> (i, j, value, is_float, names) in dict insertion order, without a Python object per key (hhx_pickle_open):
+    int32 ids into `names` (distinct names in order of first appearance, i before j, key by key), value int64 with is_float None when every
+    value is an integer, else float64 with a bool array saying which keys hold a float.  None: not a file this reader answers (the header lists
+    what that is; the reason goes to PICKLE_REFUSALS) — the caller runs pickle.load.  Integers beyond 2^53 beside floats are handed back too:
+    float64 would not hold them."""
+    L = load()
+    h = C.c_void_p()
+    rc = L.hhx_pickle_open(os.fsencode(path), C.byref(h))
+    if rc == PICKLE_NOT_OURS:
+        PICKLE_REFUSALS.append(L.hhx_last_error().decode('utf-8', 'replace'))
+        return None
+    check(rc)
+    try:
+        n_keys, n_names, n_bytes, any_float = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int(0)
+        check(L.hhx_pickle_sizes(h, C.byref(n_keys), C.byref(n_names), C.byref(n_bytes), C.byref(any_float)))
+        i, j = np.empty(n_keys.value, np.int32), np.empty(n_keys.value, np.int32)
+        value, is_float = np.empty(n_keys.value, np.int64), np.empty(n_keys.value, np.uint8)
+        blob, off = np.empty(max(1, n_bytes.value), np.uint8), np.empty(n_names.value + 1, np.int64)
+        check(L.hhx_pickle_fetch(h, ptr(i), ptr(j), ptr(value), ptr(is_float), ptr(blob), ptr(off)))
+    finally:
+        L.hhx_pickle_free(h)
+    text, bounds = blob.tobytes(), off.tolist()
+    try:
+        names = [text[a:b].decode() for a, b in zip(bounds[:-1], bounds[1:])]
+    except UnicodeDecodeError as e:                                               # pickle.load raises its own error for such a name
+        PICKLE_REFUSALS.append('a name is not UTF-8: %s' % e)
+        return None
+    if not any_float.value:
+        return i, j, value, None, names
+    is_float = is_float.astype(bool)
+    out = value.view(np.float64).copy()
+    ints = value[~is_float]
+    if ((ints > 2 ** 53) | (ints < -2 ** 53)).any():
+        PICKLE_REFUSALS.append('integers beyond 2^53 beside floats')
+        return None
+    out[~is_float] = ints
+    return i, j, out, is_float, names
 
 
 # ---- the file-writer thread of the library (hhx_jobs.hip): output_pickle / output_clm return at once, the files are complete after files_join()

@@ -434,14 +434,21 @@ def reduce_inter_hap_HiC_links(link_dict, read_depth_dict, phasing_weight, targe
 
 
 # ------------------------------------------------------------------ f3: reassign's per-group link sums
+def integral_links(link_dict):
+    """every value of the link dict is an integer.  An array-backed table answers from the dtype of its value array (asking its values would thaw
+    it): int64 counts — or float64 after a weighting step, float64 / object when a pickle held floats (reassign.parse_pickle)."""
+    if _frozen(link_dict):
+        return link_dict.arrays()[2].dtype.kind in 'iu'
+    return all(isinstance(v, (int, np.integer)) for v in link_dict.values())
+
+
 def parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks=False, _original=None):
     """HapHiC_reassign.py parse_link_dict() :217-263.  Integer link counts without normalisation (the default of
     `haphic reassign`): the per-(contig, group) sums come from the device (hhx_group_link_sums), the inner dicts are
     rebuilt in the order their keys first received a contribution, linked_ctg_dict (sets) is built on the host.
     Anything else — normalize_by_nlinks, float links — is float arithmetic whose summation order is the dict order:
     handed back to the reference's own function (`_original`, bound by patch_reassign)."""
-    integral = all(isinstance(v, (int, np.integer)) for v in link_dict.values())
-    if normalize_by_nlinks or not integral:
+    if normalize_by_nlinks or not integral_links(link_dict):
         if _original is None:
             raise ValueError('parse_link_dict on float links / with normalize_by_nlinks stays the reference function')
         return _original(link_dict, ctg_group_dict, normalize_by_nlinks)

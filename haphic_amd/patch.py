@@ -162,18 +162,21 @@ def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics
     return saved
 
 
-def patch_reassign(R, rounds=False, engine=None):
+def patch_reassign(R, rounds=False, engine=None, pickle=False, pickle_engine=None):
     """R: the imported HapHiC_reassign module.  f3: parse_link_dict :217-263 (the per-group link sums behind reassign's
     link densities) on the device for integer link counts; float / normalised links go to the original function.
     split_clm_file :581-622 (paired_links.clm routed line by line to split_clms/<group>.clm) goes through the device too
     (haphic_amd/reassign.py); the cases the reference answers with an exception of its own go to the original function.
     rounds=True: run_reassignment :266-427 and agglomerative_hierarchical_clustering :489-560 are re-bound too and parse_link_dict leaves its
     result in HBM for them (reassign.bind_rounds: what is handed back to the original functions is listed there); engine: a stand-in for
-    _lib.Reassign (the tests' numpy engine), with which the three mirrors run without a GPU.  Returns {name: original}."""
+    _lib.Reassign (the tests' numpy engine), with which the three mirrors run without a GPU.  pickle=True: parse_pickle :38-50 is re-bound too
+    (reassign.bind_pickle): full_links.pkl is read into arrays on the device and full_link_dict is a frozen containers.LinkTable, which the mirrors
+    above consume without thawing; a file the reader does not answer goes through pickle.load.  pickle_engine: a stand-in for
+    _lib.read_link_pickle (the tests' host reader).  Returns {name: original}."""
     from . import reassign
     if not rounds:
         engine = None
-    if engine is None:
+    if engine is None or (pickle and pickle_engine is None):
         from . import _lib
         _lib.load()
     original = R.parse_link_dict
@@ -190,6 +193,8 @@ def patch_reassign(R, rounds=False, engine=None):
     split_clm_file.__wrapped__ = reassign.split_clm_file
     R.split_clm_file = split_clm_file
     saved = {'parse_link_dict': original, 'split_clm_file': original_split}
+    if pickle:
+        mirrors['parse_pickle'] = reassign.bind_pickle(R, pickle_engine)
     for name, fn in mirrors.items():
         saved.setdefault(name, getattr(R, name))
         setattr(R, name, fn)

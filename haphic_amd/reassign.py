@@ -9,7 +9,11 @@ The middle of the step — the rescue and reassignment rounds (run_reassignment 
 share the handle; run_reassignment computes what is elementwise on the host (the RE filter and the length rule as flag bytes, the dismissal as a
 group mask, by the reference's own expressions), runs the round on the device and writes only the changed values back into ctg_group_dict and
 group_RE_dict, which stay real dicts.  Whatever the device does not answer exactly as the reference goes to the original function: containers
-that are not ours, a whitelist, min_links below 1, the per-contig DEBUG lines, totals that reach 2^53, float or normalised links."""
+that are not ours, a whitelist, min_links below 1, the per-contig DEBUG lines, totals that reach 2^53, float or normalised links.
+
+The step's first line — parse_pickle :38-50, pickle.load of full_links.pkl — is bound by patch_reassign(R, pickle=True) to bind_pickle() below:
+the file is read into arrays on the device (haphic_amd/csrc/hhx_pickleread.hip) and full_link_dict is a frozen containers.LinkTable, which the
+mirrors above consume without a Python object per key."""
 import logging
 import os
 from collections import defaultdict
@@ -73,6 +77,59 @@ def split_clm_file(clm_file, group_ctg_dict, ctg_group_dict, subdir, _original=N
     index = {group: g for g, group in enumerate(groups)}
     names = list(ctg_group_dict)
     _device_split(clm_file, names, [index[ctg_group_dict[ctg]] for ctg in names], ['{}/{}.clm'.format(subdir, group) for group in groups])
+
+
+# ------------------------------------------------------------------ parse_pickle :38-50 (patch_reassign(R, pickle=True))
+class PickleSession:
+    """what a containers.LinkTable needs of its session, over the arrays of one link pickle (_lib.read_link_pickle): ids into `names` and the values
+    in dict order.  value: int64 when every value of the file is an integer; float64 when all are floats; an object array of Python int / float per
+    key when the file mixes them (a thaw then gives every key the type pickle.load gives it)."""
+
+    def __init__(self, i, j, value, is_float, names):
+        if is_float is not None and not is_float.all():
+            mixed = np.empty(len(value), object)
+            mixed[:] = value.tolist()
+            at = np.flatnonzero(~is_float)
+            mixed[at] = value[at].astype(np.int64).tolist()                      # exact: read_link_pickle hands back integers beyond 2^53 beside floats
+            value = mixed
+        self.i, self.j, self.value, self.names = i, j, value, names
+        self.thawed = False
+
+    def n_keys(self, _kind):
+        return len(self.i)
+
+    def link_arrays(self, _kind):
+        return self.i, self.j, self.value, self.names
+
+    def note_thawed(self):
+        self.thawed = True
+        self.i = self.j = self.value = self.names = None                         # the dict holds them now
+
+
+def bind_pickle(R, engine=None):
+    """-> the mirror of parse_pickle :38-50 for the imported HapHiC_reassign module R: the same log line, sorted_ctg_list and RE_site_dict by the
+    reference's own expressions, full_link_dict as a frozen containers.LinkTable over the arrays the device read from the file — no dict of every
+    key (tens of GB of Python objects at 100k contigs) that parse_link_dict would flatten again.  A file the reader hands back (include/haphic_hip.h
+    lists them: another header or protocol, other opcodes, names of 256 bytes and more, integers beyond 64 bits, a truncated file, bytes after
+    STOP ...) goes through pickle.load, so that Python's own result or error is what the caller sees.  engine: a stand-in for _lib.read_link_pickle
+    (the tests' host reader)."""
+    import pickle
+    read = engine if engine is not None else _lib.read_link_pickle
+
+    def parse_pickle(fa_dict, pickle_file):
+        R.logger.info('Parsing input pickle file...')
+        arrays = read(pickle_file)
+        if arrays is None:
+            with open(pickle_file, 'rb') as f:
+                full_link_dict = pickle.load(f)
+        else:
+            full_link_dict = containers.LinkTable(PickleSession(*arrays), 'full')
+        # sort by contig length
+        sorted_ctg_list = sorted([(ctg, fa_dict[ctg][1]) for ctg in fa_dict], key=lambda x: x[1], reverse=True)
+        RE_site_dict = {ctg: ctg_info[2] for ctg, ctg_info in fa_dict.items()}
+        return full_link_dict, sorted_ctg_list, RE_site_dict
+
+    return parse_pickle
 
 
 # ------------------------------------------------------------------ the rounds and the agglomerative step (patch_reassign(R, rounds=True))
@@ -150,7 +207,7 @@ def bind_rounds(R, engine=None):
         return cluster.parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks, _original=original_parse)
 
     def parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks=False):
-        if normalize_by_nlinks or not all(isinstance(v, (int, np.integer)) for v in link_dict.values()):
+        if normalize_by_nlinks or not cluster.integral_links(link_dict):
             return original_parse(link_dict, ctg_group_dict, normalize_by_nlinks)
         names = {}
         fi, fj, val = cluster._dict_arrays(link_dict, names)

@@ -78,7 +78,8 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * in one piece, rounded down to a multiple of 16 in [256, 2^26] (default 2^26; the same file, other seams); "sort_verdict_lds_n" = the largest n whose
  * rotations hhx_sort_verdict_sums runs with their tree in LDS, clamped to [0, 40959] (4-byte cells: lengths summing to less than 2^32) or [0, 20479]
  * (8-byte cells) (default 4095 / 2047: a tree of 16 KiB, above which a CU holds too few rotations to hide a step's latency; 0: every rotation on its
- * scratch slab in HBM; same bits).  value INT64_MIN: back to the default.  Unset knobs fall back to the
+ * scratch slab in HBM; same bits); "pkl_chunk" = bytes per chunk of the opcode-boundary search of hhx_pickle_open, clamped to [512, 16384] (default 4096;
+ * the same arrays, other seams).  value INT64_MIN: back to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
 int hhx_profile_enable(int on);
@@ -760,6 +761,28 @@ int hhx_clm_split_stats(hhx_clm_split *s, int64_t *values);
 int hhx_clm_split_destroy(hhx_clm_split *s);
 int hhx_files_pending(int64_t *n_pending, int64_t *n_done);
 int hhx_files_join(int64_t *n_failed);
+
+/* ---------------------------------------------------------------- full_links.pkl / HT_links.pkl back into arrays (haphic_amd/csrc/hhx_pickleread.hip)
+ * HapHiC_reassign.py parse_pickle :38-50 is `pickle.load(f)`: a defaultdict(int) {(name, name): value} of every key, which the next step flattens
+ * again.  hhx_pickle_open reads the file into HBM (pinned read-ahead of hhx_text_reader_open_raw), finds the opcode boundaries on the device, validates
+ * the stream token by token and leaves, in dict insertion order: name_i / name_j [n_keys] (int32 ids), the 64 bits of every value (two's complement of
+ * an int, IEEE-754 of a float) with is_float [n_keys], and the distinct names — compared as bytes, numbered in order of first appearance, i before j,
+ * key by key — as names_blob + name_off [n_names + 1].  Accepted: protocol 4 or 5; an optional FRAME; the construction of
+ * collections.defaultdict(builtins.int) as the pickler and hhx_write_link_pickle spell it; then any interleaving of FRAME, MARK, SETITEMS, SETITEM and
+ * MEMOIZE that a sequential reader accepts around the items *name, name, TUPLE2, value*; STOP as the last byte.  name = SHORT_BINUNICODE, or BINGET /
+ * LONG_BINGET of a slot a name literal was memoised into; value = BININT1, BININT2, BININT, LONG1 of at most 8 bytes, BINFLOAT.  Everything else — another
+ * header or protocol, any other opcode (BINUNICODE of a name of 256 bytes and more, LONG1 of 9 bytes and more, TUPLE3, NEWTRUE, NONE ...), a memo
+ * reference to a tuple or to one of the header's slots, a MEMOIZE of anything but a name literal or a key, a key written twice, frames that do not
+ * tile the file, a file that ends early, bytes after STOP, a file beyond half of the device's memory — returns HHX_PICKLE_NOT_OURS with the reason in
+ * hhx_last_error() and *out = NULL: the caller runs pickle.load, so that Python's own answer is what the user sees.  Any other non-zero return is a
+ * failure (I/O, memory).  The boundary search works on chunks of hhx_tune "pkl_chunk" bytes.  hhx_pickle_fetch copies into host arrays (any may be
+ * NULL); hhx_pickle_free(NULL) is fine. */
+#define HHX_PICKLE_NOT_OURS 2
+typedef struct hhx_pickle hhx_pickle;
+int hhx_pickle_open(const char *path, hhx_pickle **out);
+int hhx_pickle_sizes(hhx_pickle *p, int64_t *n_keys, int32_t *n_names, int64_t *names_bytes, int *any_float);
+int hhx_pickle_fetch(hhx_pickle *p, int32_t *name_i, int32_t *name_j, int64_t *value_bits, uint8_t *is_float, uint8_t *names_blob, int64_t *name_off);
+int hhx_pickle_free(hhx_pickle *p);
 
 /* ---------------------------------------------------------------- assembly correction (--correct_nrounds), haphic_amd/csrc/hhx_correct.hip
  * Pass one — parse_pairs_for_correction :1300-1344 / parse_bam_for_correction :1362-1398.  hhx_correct_create: contig c (fa_dict order, ctg_len
