@@ -13,7 +13,9 @@ and so do the rescue and reassignment rounds (run_reassignment :266-427) and the
 (patch_reassign(R, rounds=True)); run() :752-916 is the reference's, called as its main() :919-924 calls it.
 `python -m haphic_amd sort <arguments of "haphic sort">` wraps HapHiC_sort.py: the dense work of fast sorting (link matrix, density graph, confidence
 graph and the link re-aggregation of every round, haphic_amd/sort.py) runs on the device (haphic_amd.patch.patch_sort); fast_sort's loop, the spanning
-forest, the ALLHiC child per group and run() :847-959 are the reference's, its process pool replaced by threads; called as its main() :962-967 does.  `sort` with nothing after it has nothing to hand on and exits with a usage message.
+forest, the ALLHiC child per group and run() :847-959 are the reference's, its process pool replaced by threads; called as its main() :962-967 does.
+The front of run() :898-923 runs on the device too: HT_links.pkl is read into arrays that stay there and each group's sub_HT_dict / HT_index_dict
+(get_sub_HT_dict :117-143) comes from two streaming passes over them and a sort of the survivors (patch_sort(S, heads=True)).  `sort` with nothing after it has nothing to hand on and exits with a usage message.
 `python -m haphic_amd build <arguments of "haphic build">` wraps HapHiC_build.py: parse_fasta (HapHiC_cluster.py:87-113: the FASTA text goes to HBM in one piece
 and is compacted there into the contigs' sequences, haphic_amd/scaffolds.py) and build_final_scaffolds :74-179 (scaffolds.fa gathered, reverse-complemented and
 wrapped on the device, written slab by slab; both AGP files from the host arrays) run on the device (haphic_amd.patch.patch_build); parse_tours, the juicebox
@@ -66,6 +68,14 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              and the ratio rule, the threshold and the log lines stay in Python: same verdict, same log line.  A call still goes to the
                              reference's function for a group of one contig, an ALLHiC tour that is no permutation of the fast-sort tour, a length that
                              is not a non-negative int, and beyond 2^18 contigs
+  --keep-reference-heads     sort only: leave the front of run() :898-923 to the reference: pickle.load builds HT_link_dict as a Python dict of every key of
+                             HT_links.pkl (tens of GB of objects at 100k contigs) and get_sub_HT_dict :117-143 does four dict look-ups for every pair of
+                             contigs of every group.  Without the flag the file is read into arrays on the device (csrc/hhx_pickleread.hip), HT_link_dict is
+                             an array-backed table that stays there, and each group's sub_HT_dict comes from two streaming passes over those arrays (haphic_amd/sort.py
+                             bind_heads): the same items and HT_index_dict in the same order, the same tour files.  `del HT_link_dict` :922 frees the
+                             device memory.  A file still goes through pickle.load when the reader does not answer it (as --keep-reference-pickle lists),
+                             and a group goes to the reference's function — on the table turned into the dict pickle.load gives — when a contig is listed
+                             twice, the table holds float values, or 2 n is beyond int32
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
@@ -129,6 +139,7 @@ def main(argv=None):
     keep_pickle = bool(_take(argv, '--keep-reference-pickle', False))
     keep_build = bool(_take(argv, '--keep-reference-build', False))
     keep_verdict = bool(_take(argv, '--keep-reference-verdict', False))
+    keep_heads = bool(_take(argv, '--keep-reference-heads', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
     scripts = _reference_scripts(ref)
     if stub:
@@ -163,6 +174,8 @@ def main(argv=None):
         from . import sort
         sort.DEVICE = device                                        # the pool's threads select it before their first call
         patch.patch_sort(S, verdict=not keep_verdict)
+        if not keep_heads:
+            patch.patch_sort_heads(S)                               # == patch_sort(S, ..., heads=True)
         sys.argv = ['haphic sort'] + argv
         S.run(S.parse_arguments(), 'HapHiC_sort.log')               # == HapHiC_sort.main() :962-967
         return 0

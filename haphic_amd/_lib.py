@@ -191,6 +191,8 @@ SIGNATURES = {
     'hhx_pickle_sizes': (C.c_int, [C.c_void_p, c_i64p, c_i32p, c_i64p, C.POINTER(C.c_int)]),
     'hhx_pickle_fetch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_pickle_free': (C.c_int, [C.c_void_p]),
+    'hhx_pickle_group_heads': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, c_i64p]),
+    'hhx_pickle_group_heads_fetch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_files_pending': (C.c_int, [c_i64p, c_i64p]),
     'hhx_files_join': (C.c_int, [c_i64p]),
     'hhx_correct_create': (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, c_vpp]),
@@ -694,44 +696,103 @@ PICKLE_NOT_OURS = 2                  # HHX_PICKLE_NOT_OURS
 PICKLE_REFUSALS = []                 # hhx_last_error() of every file read_link_pickle handed back in this process
 
 
+class LinkPickle:
+    """hhx_pickle: full_links.pkl / HT_links.pkl read into arrays that stay in the memory of the device (hhx_pickle_open) until close().
+    LinkPickle.open(path) -> the handle, or None for a file the reader does not answer (the reason goes to PICKLE_REFUSALS; the caller runs
+    pickle.load).  tests/sort_heads_cases.py holds a host engine with the same interface."""
+
+    def __init__(self, h):
+        self.h = h
+        n_keys, n_names, n_bytes, any_float = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int(0)
+        check(load().hhx_pickle_sizes(h, C.byref(n_keys), C.byref(n_names), C.byref(n_bytes), C.byref(any_float)))
+        self.n_keys, self.n_names, self.names_bytes, self.any_float = n_keys.value, n_names.value, n_bytes.value, bool(any_float.value)
+
+    @classmethod
+    def open(cls, path):
+        L = load()
+        h = C.c_void_p()
+        rc = L.hhx_pickle_open(os.fsencode(path), C.byref(h))
+        if rc == PICKLE_NOT_OURS:
+            PICKLE_REFUSALS.append(L.hhx_last_error().decode('utf-8', 'replace'))
+            return None
+        check(rc)
+        try:
+            return cls(h)
+        except BaseException:
+            L.hhx_pickle_free(h)
+            raise
+
+    def _decode(self, blob, off):
+        text, bounds = blob.tobytes(), off.tolist()
+        return [text[a:b].decode() for a, b in zip(bounds[:-1], bounds[1:])]
+
+    def names(self):
+        """the distinct names in order of first appearance (the names alone: the keys stay on the device); UnicodeDecodeError for a name that is
+        not UTF-8"""
+        blob, off = np.empty(max(1, self.names_bytes), np.uint8), np.empty(self.n_names + 1, np.int64)
+        check(load().hhx_pickle_fetch(self.h, None, None, None, None, ptr(blob), ptr(off)))
+        return self._decode(blob, off)
+
+    def arrays(self):
+        """(i, j, value, is_float, names) as read_link_pickle returns them, or None where it returns None"""
+        i, j = np.empty(self.n_keys, np.int32), np.empty(self.n_keys, np.int32)
+        value, is_float = np.empty(self.n_keys, np.int64), np.empty(self.n_keys, np.uint8)
+        blob, off = np.empty(max(1, self.names_bytes), np.uint8), np.empty(self.n_names + 1, np.int64)
+        check(load().hhx_pickle_fetch(self.h, ptr(i), ptr(j), ptr(value), ptr(is_float), ptr(blob), ptr(off)))
+        try:
+            names = self._decode(blob, off)
+        except UnicodeDecodeError as e:                                           # pickle.load raises its own error for such a name
+            PICKLE_REFUSALS.append('a name is not UTF-8: %s' % e)
+            return None
+        if not self.any_float:
+            return i, j, value, None, names
+        is_float = is_float.astype(bool)
+        out = value.view(np.float64).copy()
+        ints = value[~is_float]
+        if ((ints > 2 ** 53) | (ints < -2 ** 53)).any():
+            PICKLE_REFUSALS.append('integers beyond 2^53 beside floats')
+            return None
+        out[~is_float] = ints
+        return i, j, out, is_float, names
+
+    def group_heads(self, n_ctg, slot, rank):
+        """hhx_pickle_group_heads: get_sub_HT_dict :117-143 for one group -> (ei, ej, w): int32 index pairs and int64 values in the reference's
+        insertion order.  slot [n_names] and rank [n_ctg] as include/haphic_hip.h describes them."""
+        slot, rank = np.ascontiguousarray(slot, np.int32), np.ascontiguousarray(rank, np.int32)
+        if slot.size != self.n_names or rank.size != n_ctg:
+            raise ValueError('LinkPickle.group_heads: {} slots for {} names, {} ranks for {} contigs'.format(slot.size, self.n_names, rank.size, n_ctg))
+        n = C.c_int64(0)
+        check(load().hhx_pickle_group_heads(self.h, int(n_ctg), ptr(slot), ptr(rank), C.byref(n)))
+        ei, ej, w = np.empty(n.value, np.int32), np.empty(n.value, np.int32), np.empty(n.value, np.int64)
+        if n.value:
+            check(load().hhx_pickle_group_heads_fetch(self.h, ptr(ei), ptr(ej), ptr(w)))
+        return ei, ej, w
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            load().hhx_pickle_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def read_link_pickle(path):
     """full_links.pkl / HT_links.pkl -> (i, j, value, is_float, names) in dict insertion order, without a Python object per key (hhx_pickle_open):
     int32 ids into `names` (distinct names in order of first appearance, i before j, key by key), value int64 with is_float None when every
     value is an integer, else float64 with a bool array saying which keys hold a float.  None: not a file this reader answers (the header lists
     what that is; the reason goes to PICKLE_REFUSALS) — the caller runs pickle.load.  Integers beyond 2^53 beside floats are handed back too:
     float64 would not hold them."""
-    L = load()
-    h = C.c_void_p()
-    rc = L.hhx_pickle_open(os.fsencode(path), C.byref(h))
-    if rc == PICKLE_NOT_OURS:
-        PICKLE_REFUSALS.append(L.hhx_last_error().decode('utf-8', 'replace'))
+    h = LinkPickle.open(path)
+    if h is None:
         return None
-    check(rc)
     try:
-        n_keys, n_names, n_bytes, any_float = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int(0)
-        check(L.hhx_pickle_sizes(h, C.byref(n_keys), C.byref(n_names), C.byref(n_bytes), C.byref(any_float)))
-        i, j = np.empty(n_keys.value, np.int32), np.empty(n_keys.value, np.int32)
-        value, is_float = np.empty(n_keys.value, np.int64), np.empty(n_keys.value, np.uint8)
-        blob, off = np.empty(max(1, n_bytes.value), np.uint8), np.empty(n_names.value + 1, np.int64)
-        check(L.hhx_pickle_fetch(h, ptr(i), ptr(j), ptr(value), ptr(is_float), ptr(blob), ptr(off)))
+        return h.arrays()
     finally:
-        L.hhx_pickle_free(h)
-    text, bounds = blob.tobytes(), off.tolist()
-    try:
-        names = [text[a:b].decode() for a, b in zip(bounds[:-1], bounds[1:])]
-    except UnicodeDecodeError as e:                                               # pickle.load raises its own error for such a name
-        PICKLE_REFUSALS.append('a name is not UTF-8: %s' % e)
-        return None
-    if not any_float.value:
-        return i, j, value, None, names
-    is_float = is_float.astype(bool)
-    out = value.view(np.float64).copy()
-    ints = value[~is_float]
-    if ((ints > 2 ** 53) | (ints < -2 ** 53)).any():
-        PICKLE_REFUSALS.append('integers beyond 2^53 beside floats')
-        return None
-    out[~is_float] = ints
-    return i, j, out, is_float, names
+        h.close()
 
 
 # ---- the file-writer thread of the library (hhx_jobs.hip): output_pickle / output_clm return at once, the files are complete after files_join()

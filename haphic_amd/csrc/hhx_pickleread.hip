@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "hhx_sort.h"
 #include "hhx_textscan.h"
 
 using namespace hhx;
@@ -375,6 +376,10 @@ struct hhx_pickle {
     DevBuf<i64> val;
     DevBuf<unsigned char> isf, blob;
     std::vector<i64> name_off;
+    // the last hhx_pickle_group_heads: the group's edges in the reference's order
+    i64 heads_n = 0;
+    DevBuf<i32> heads_i, heads_j;
+    DevBuf<u64> heads_w;
 };
 
 static int pickle_read(const char *path, hhx_pickle *h) {
@@ -626,5 +631,209 @@ extern "C" int hhx_pickle_fetch(hhx_pickle *p, int32_t *name_i, int32_t *name_j,
 
 extern "C" int hhx_pickle_free(hhx_pickle *p) {
     delete p;
+    return 0;
+}
+
+// ------------------------------------------------------------------ one group's H/T links from the open table
+// HapHiC_sort.py get_sub_HT_dict :117-143 for one group of run() :912-920, on id_i / id_j / val as hhx_pickle_open left them (the rule: include/haphic_hip.h).
+// The caller numbers the names: slot[name id] = 2 * position + suffix for the 2 n names ctg + '_H' / '_T' the file holds, -1 for every other name, and
+// rank[position] = the contig's place among the sorted names.  k_heads_pass streams the keys, four per lane as two 16-byte loads: both ends are tested
+// against a bitmap of the slotted names held in LDS (hhx_tune "heads_bitmap"; as hhx_partition.h does for frag_set) before the slots are gathered, and the
+// value is loaded for a key of two slotted names of two contigs only.  Every wavefront owns one contiguous range of the table, walks it in steps of 64
+// quads with the next step's ids loaded ahead, and compacts its survivors (key of the reference's insertion order, value) with ballot and prefix.  No
+// counter is shared between wavefronts — atomics of the whole grid on one address would bound the pass — so the pass runs twice: once to
+// count per wavefront, then, after a scan of those counts, to write at the wavefront's own running offset.  The stable radix sort of hhx_sort.h then puts
+// the survivors in the reference's order on as many bits as the order key has — the keys are distinct — and k_heads_finish turns every order key into
+// its two indices.
+namespace {
+
+constexpr int HD_T = 256, HD_PER = 4, HD_WAVES = HD_T / HHX_WAVE;
+constexpr i64 HD_BITMAP_BYTES = 64 << 10;     // the most names (2^19) whose bitmap a workgroup holds in LDS; more: the plain gather
+constexpr unsigned HD_GRID = 256 * 6;         // six workgroups a CU: what fits beside a bitmap of 25 KB each; every workgroup reads the whole bitmap once (hhx_tune "heads_grid": fewer)
+
+// member bit (id & 63) of word (id >> 6): slot[id] >= 0
+__global__ __launch_bounds__(HD_T) void k_heads_bitmap(const i32 *__restrict__ slot, i64 n_names, i64 n_words, u64 *__restrict__ member) {
+    for (i64 base = (i64)blockIdx.x * HD_T; base < n_words * 64; base += (i64)gridDim.x * HD_T) {
+        const i64 id = base + threadIdx.x;
+        const u64 m = __ballot(id < n_names && slot[id] >= 0);
+        if (lane_id() == 0 && (id >> 6) < n_words) member[id >> 6] = m;
+    }
+}
+
+__device__ __forceinline__ bool bit_of(const u64 *bits, i32 id) { return (bits[id >> 6] >> (id & 63)) & 1ull; }
+
+// wavefront w of the grid takes the quads (four keys) [w * per_wave, (w + 1) * per_wave), 64 consecutive quads per step.  EMIT = false: counts[w] = its
+// survivors; EMIT = true: they are written from offs[w] on (offs: the exclusive scan of counts, so every position lies below the total)
+template <bool BITMAP, bool EMIT>
+__global__ __launch_bounds__(HD_T) void k_heads_pass(const i32 *__restrict__ id_i, const i32 *__restrict__ id_j, const i64 *__restrict__ val, i64 n_keys,
+                                                     i64 per_wave, const i32 *__restrict__ slot, const i32 *__restrict__ rank, i64 n,
+                                                     const u64 *__restrict__ member, i64 n_words, i64 *__restrict__ counts, const i64 *__restrict__ offs,
+                                                     u64 *__restrict__ okey, u64 *__restrict__ oval) {
+    extern __shared__ u64 bits[];
+    if (BITMAP) {
+        for (i64 w = threadIdx.x; w < n_words; w += HD_T) bits[w] = member[w];
+        __syncthreads();
+    }
+    const int lane = lane_id();
+    const u64 lt = (1ull << lane) - 1ull;
+    const i64 wave = (i64)blockIdx.x * HD_WAVES + threadIdx.x / HHX_WAVE;
+    const i64 q0 = wave * per_wave, q1 = min((n_keys + HD_PER - 1) / HD_PER, q0 + per_wave);
+    i64 at = EMIT ? offs[wave] : 0;                                                                      // the same in every lane
+    // the ids of the quad (-1: past the range or the table); id_i / id_j start on 16-byte boundaries
+    auto load = [&](i64 quad, int4 &va, int4 &vb) {
+        const i64 k0 = quad * HD_PER;
+        if (quad < q1 && k0 + HD_PER <= n_keys) {
+            va = *reinterpret_cast<const int4 *>(id_i + k0);
+            vb = *reinterpret_cast<const int4 *>(id_j + k0);
+        } else {
+            i32 x[HD_PER], y[HD_PER];
+#pragma unroll
+            for (int q = 0; q < HD_PER; ++q) {
+                const bool in = quad < q1 && k0 + q < n_keys;
+                x[q] = in ? id_i[k0 + q] : -1;
+                y[q] = in ? id_j[k0 + q] : -1;
+            }
+            va = make_int4(x[0], x[1], x[2], x[3]);
+            vb = make_int4(y[0], y[1], y[2], y[3]);
+        }
+    };
+    int4 na = make_int4(-1, -1, -1, -1), nb = na;
+    if (q0 < q1) load(q0 + lane, na, nb);
+    for (i64 base = q0; base < q1; base += HHX_WAVE) {                                                   // the bound is the same for the whole wavefront
+        const i64 k0 = (base + lane) * HD_PER;
+        const i32 a[HD_PER] = {na.x, na.y, na.z, na.w}, b[HD_PER] = {nb.x, nb.y, nb.z, nb.w};
+        if (base + HHX_WAVE < q1) load(base + HHX_WAVE + lane, na, nb);                                 // the next step's ids are on their way while this one's slots are gathered
+#pragma unroll
+        for (int q = 0; q < HD_PER; ++q) {
+            bool keep = false;
+            u64 key = 0;
+            i64 v = 0;
+            if (a[q] >= 0 && (!BITMAP || (bit_of(bits, a[q]) && bit_of(bits, b[q])))) {
+                const i32 sa = slot[a[q]];
+                const i32 sb = sa >= 0 ? slot[b[q]] : -1;
+                if (sb >= 0) {
+                    const i64 pa = sa >> 1, pb = sb >> 1;                                                // positions in ctgs, below n
+                    if (pa != pb && rank[pa] < rank[pb]) {                                              // two contigs, the smaller name first
+                        v = val[k0 + q];
+                        key = (u64)(min(pa, pb) * n + max(pa, pb)) << 2 | (u64)(2 * (sa & 1) + (sb & 1));
+                        keep = v != 0;
+                    }
+                }
+            }
+            const u64 m = __ballot(keep);
+            if (EMIT && keep) {
+                const i64 pos = at + __popcll(m & lt);
+                okey[pos] = key;
+                oval[pos] = (u64)v;
+            }
+            at += __popcll(m);
+        }
+    }
+    if (!EMIT && lane == 0) counts[wave] = at;
+}
+
+// lo_H = 0, hi_H = 1, hi_T = 2, lo_T = 3 for lo, hi = sorted(ctgs[:2]); ctgs[k]_H = 2 k, ctgs[k]_T = 2 k + 1 from k = 2 on
+__device__ __forceinline__ i32 head_index(i64 pos, int suffix, int lo_pos) {
+    if (pos >= 2) return (i32)(2 * pos + suffix);
+    return pos == lo_pos ? (suffix ? 3 : 0) : (suffix ? 2 : 1);
+}
+__global__ __launch_bounds__(HD_T) void k_heads_finish(const u64 *__restrict__ key, i64 m, i64 n, const i32 *__restrict__ rank, int lo_pos, i32 *__restrict__ ei,
+                                                       i32 *__restrict__ ej) {
+    for (i64 t = (i64)blockIdx.x * HD_T + threadIdx.x; t < m; t += (i64)gridDim.x * HD_T) {
+        const u64 k = key[t];
+        const i64 cell = (i64)(k >> 2), a = cell / n, b = cell - a * n;                                  // a < b < n by construction
+        const bool a_first = rank[a] < rank[b];
+        ei[t] = head_index(a_first ? a : b, (int)(k >> 1) & 1, lo_pos);
+        ej[t] = head_index(a_first ? b : a, (int)k & 1, lo_pos);
+    }
+}
+
+}  // namespace
+
+extern "C" int hhx_pickle_group_heads(hhx_pickle *p, int32_t n_ctg, const int32_t *slot, const int32_t *rank, int64_t *n_edges) {
+    if (!p) return fail("hhx_pickle_group_heads: null handle");
+    if (!slot || !rank || !n_edges) return fail("hhx_pickle_group_heads: null pointer");
+    *n_edges = 0;
+    p->heads_n = 0;
+    if (n_ctg < 2 || n_ctg >= (1 << 30)) return fail("hhx_pickle_group_heads: %d contigs (2 .. 2^30 - 1 are served)", n_ctg);
+    if (p->any_float) return fail("hhx_pickle_group_heads: the table holds float values");
+    const i64 n = n_ctg, n_names = p->n_names, n_keys = p->n_keys;
+    // what the kernels index with: every slot below 2 n, rank a permutation of 0 .. n - 1
+    for (i64 k = 0; k < n_names; ++k)
+        if (slot[k] < -1 || slot[k] >= 2 * n) return fail("hhx_pickle_group_heads: slot[%lld] = %d is outside -1 .. %lld", (long long)k, slot[k], (long long)(2 * n - 1));
+    {
+        std::vector<unsigned char> seen((size_t)n, 0);
+        for (i64 k = 0; k < n; ++k) {
+            if (rank[k] < 0 || rank[k] >= n || seen[(size_t)rank[k]]) return fail("hhx_pickle_group_heads: rank is no permutation of 0 .. %lld", (long long)(n - 1));
+            seen[(size_t)rank[k]] = 1;
+        }
+    }
+    if (n_keys == 0 || n_names == 0) return 0;
+
+    const i64 n_words = (n_names + 63) / 64;
+    const bool bitmap = tune_get("heads_bitmap", 1) != 0 && n_words * (i64)sizeof(u64) <= HD_BITMAP_BYTES;
+    const i64 n_quads = (n_keys + HD_PER - 1) / HD_PER;
+    const unsigned grid = std::min(grid_for(n_quads, HD_T), (unsigned)std::min<i64>(HD_GRID, std::max<i64>(1, tune_get("heads_grid", HD_GRID))));
+    const i64 n_waves = (i64)grid * HD_WAVES;
+    const i64 per_wave = ((n_quads + n_waves - 1) / n_waves + HHX_WAVE - 1) / HHX_WAVE * HHX_WAVE;         // whole steps: every wavefront's range starts on a 1 KiB boundary
+    DevBuf<i32> dslot, drank;
+    DevBuf<u64> member, key, value;
+    DevBuf<i64> counts, offs;
+    if (dslot.alloc((size_t)n_names) || drank.alloc((size_t)n) || member.alloc((size_t)n_words) || counts.alloc((size_t)n_waves) || offs.alloc((size_t)n_waves + 1))
+        return 1;
+    HHX_HIP(hipMemcpyAsync(dslot.p, slot, sizeof(i32) * (size_t)n_names, hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemcpyAsync(drank.p, rank, sizeof(i32) * (size_t)n, hipMemcpyHostToDevice, g_stream));
+    const size_t lds = bitmap ? (size_t)n_words * sizeof(u64) : 0;
+    i64 m = 0;
+    {
+        KTimer kt("heads_pass", bitmap ? 2 : 1);
+        if (bitmap) {
+            k_heads_bitmap<<<grid_for(n_words * 64, HD_T), HD_T, 0, g_stream>>>(dslot.p, n_names, n_words, member.p);
+            k_heads_pass<true, false><<<grid, HD_T, lds, g_stream>>>(p->id_i.p, p->id_j.p, p->val.p, n_keys, per_wave, dslot.p, drank.p, n, member.p, n_words, counts.p,
+                                                                    nullptr, nullptr, nullptr);
+        } else {
+            k_heads_pass<false, false><<<grid, HD_T, 0, g_stream>>>(p->id_i.p, p->id_j.p, p->val.p, n_keys, per_wave, dslot.p, drank.p, n, nullptr, 0, counts.p, nullptr,
+                                                                   nullptr, nullptr);
+        }
+        HHX_LAUNCH_CHECK();
+    }
+    HHX_TRY(exclusive_scan_i64(counts.p, offs.p, n_waves, &m));                    // synchronises: m is the number of survivors
+    prof_count("heads_keys", n_keys);
+    if (m == 0) return 0;
+    if (m > n_keys) return fail("hhx_pickle_group_heads: %lld survivors of %lld keys", (long long)m, (long long)n_keys);
+    if (key.alloc((size_t)m) || value.alloc((size_t)m)) return 1;
+    {
+        KTimer kt("heads_pass");
+        if (bitmap)
+            k_heads_pass<true, true><<<grid, HD_T, lds, g_stream>>>(p->id_i.p, p->id_j.p, p->val.p, n_keys, per_wave, dslot.p, drank.p, n, member.p, n_words, nullptr,
+                                                                   offs.p, key.p, value.p);
+        else
+            k_heads_pass<false, true><<<grid, HD_T, 0, g_stream>>>(p->id_i.p, p->id_j.p, p->val.p, n_keys, per_wave, dslot.p, drank.p, n, nullptr, 0, nullptr, offs.p,
+                                                                  key.p, value.p);
+        HHX_LAUNCH_CHECK();
+    }
+    int bits = 2;                                                                  // 2 * ceil(log2 n) + 2
+    while ((1ll << ((bits - 2) / 2)) < n) bits += 2;
+    DevBuf<u64> skey;
+    if (skey.alloc((size_t)m) || p->heads_w.alloc((size_t)m) || p->heads_i.alloc((size_t)m) || p->heads_j.alloc((size_t)m)) return 1;
+    {
+        KTimer kt("heads_sort", 2 * ((bits + 7) / 8) + 1);
+        HHX_TRY(stable_sort_pairs_u64(key.p, skey.p, value.p, p->heads_w.p, m, bits));
+        k_heads_finish<<<grid_for(m, HD_T), HD_T, 0, g_stream>>>(skey.p, m, n, drank.p, rank[0] < rank[1] ? 0 : 1, p->heads_i.p, p->heads_j.p);
+        HHX_LAUNCH_CHECK();
+    }
+    HHX_HIP(hipStreamSynchronize(g_stream));                                       // skey / drank are read until here
+    p->heads_n = m;
+    *n_edges = m;
+    return 0;
+}
+
+extern "C" int hhx_pickle_group_heads_fetch(hhx_pickle *p, int32_t *ei, int32_t *ej, int64_t *w) {
+    if (!p) return fail("hhx_pickle_group_heads_fetch: null handle");
+    const size_t m = (size_t)p->heads_n;
+    if (m && ei) HHX_HIP(hipMemcpyAsync(ei, p->heads_i.p, sizeof(i32) * m, hipMemcpyDeviceToHost, g_stream));
+    if (m && ej) HHX_HIP(hipMemcpyAsync(ej, p->heads_j.p, sizeof(i32) * m, hipMemcpyDeviceToHost, g_stream));
+    if (m && w) HHX_HIP(hipMemcpyAsync(w, p->heads_w.p, sizeof(i64) * m, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
     return 0;
 }

@@ -220,14 +220,24 @@ SORT_VERDICT_SEAMS = {
 }
 
 
-def patch_sort(S, engine=None, verdict=False, verdict_engine=None):
+# each group's H/T links from HT_links.pkl (haphic_amd/sort.py bind_heads): run()'s `pickle.load` :898-901 answers an array-backed table that stays on the
+# device, and get_sub_HT_dict extracts a group from it there.  OPT-IN at this level, like the verdict; `python -m haphic_amd sort` asks for it.
+SORT_HEADS_SEAMS = {
+    'pickle': 'HapHiC_sort.py:17 (pickle.load :898-901)',
+    'get_sub_HT_dict': 'HapHiC_sort.py:117-143',
+}
+
+
+def patch_sort(S, engine=None, verdict=False, verdict_engine=None, heads=False, heads_engine=None):
     """S: the imported HapHiC_sort module.  The dense work of fast sorting goes to the device (haphic_amd/sort.py); fast_sort, the spanning forest,
     split_new_scaffold, the .tour writer, the ALLHiC child and run() stay the reference's.  run() :875-876 forks a multiprocessing.Pool: a process
     that has initialised the GPU must not be forked into workers that use it, so S.Pool becomes the ThreadPool (same apply_async / close / join);
     one lock serialises the device part across its threads, the ALLHiC children run beside it.  engine: a stand-in for _lib.SortGraph (the tests'
     numpy engine).  verdict=True: compare_fast_sort_and_allhic :645-724 (which tour final_tours/<group>.tour links to) is re-bound too: the weighted-LIS
     sums of all rotations come from one library call; verdict_engine: a stand-in for _lib.sort_verdict_sums (the tests' host engine); `python -m
-    haphic_amd sort` asks for it.  Returns {name: original}."""
+    haphic_amd sort` asks for it.  heads=True: S.pickle becomes a proxy of the pickle module whose load() reads HT_links.pkl into arrays on the device
+    (run() :898-901) and get_sub_HT_dict :117-143 is re-bound to extract every group from them there (SORT_HEADS_SEAMS; sort.bind_heads lists what
+    goes to the reference's function); heads_engine: a stand-in for _lib.LinkPickle.open (the tests' host reader).  Returns {name: original}."""
     from multiprocessing.pool import ThreadPool
     from . import sort
     if engine is None or (verdict and verdict_engine is None):
@@ -242,6 +252,20 @@ def patch_sort(S, engine=None, verdict=False, verdict_engine=None):
     for name, fn in mirrors.items():
         setattr(S, name, fn)
     S.Pool = ThreadPool
+    if heads:
+        saved.update(patch_sort_heads(S, heads_engine))
+    return saved
+
+
+def patch_sort_heads(S, engine=None):
+    """The two seams of SORT_HEADS_SEAMS alone (patch_sort(S, heads=True) ends here; the wrapper command calls it after patch_sort unless
+    --keep-reference-heads is given).  Returns {name: original}."""
+    from . import sort
+    if engine is None:
+        from . import _lib
+        _lib.load()
+    saved = {name: getattr(S, name, None) for name in SORT_HEADS_SEAMS}
+    S.pickle, S.get_sub_HT_dict = sort.bind_heads(S, engine)
     return saved
 
 

@@ -16,7 +16,10 @@ SubHT: a defaultdict that stays arrays until something other than these seams to
 
 bind_verdict: compare_fast_sort_and_allhic :645-724, which run_haphic_sorting :748 calls per group once fast sorting and ALLHiC have both run.  The
 weighted-LIS sums of the rotations :696-721 come from one library call (_lib.sort_verdict_sums); parse_tours, the ratio rule :683-688, the threshold
-:712-716 and both log lines stay here, in Python ints and floats."""
+:712-716 and both log lines stay here, in Python ints and floats.
+
+bind_heads: the front of run() :898-923.  S.pickle becomes a PickleProxy whose load() reads HT_links.pkl into arrays on the device (HTTable) and
+get_sub_HT_dict :117-143 extracts each group from them there (HeadsHT, which round 1 of dict_to_matrix takes as arrays)."""
 import threading
 from itertools import product
 
@@ -130,7 +133,7 @@ def bind(S, engine=None):
         if g is not None and _frozen(dict_) and dict_._session is g and not g.host_mode:
             return g                                       # the link matrix is already on the device (update)
         if g is None and not isinstance(dict_, SubHT):
-            arrays = _round1_arrays(dict_, shape)
+            arrays = dict_.round1_arrays(shape) if _frozen_heads(dict_) else _round1_arrays(dict_, shape)     # None: the reference's path (a HeadsHT thaws)
             if arrays is not None:
                 g = Graph(make_engine(shape, *arrays), shape, dict_, *arrays)
                 _tls.graph = g
@@ -183,13 +186,13 @@ def bind(S, engine=None):
             return original['remove_shortest_path'](index_pairs, sub_HT_dict, density_graph)
         g = density_graph
         a, b = index_pairs.pop(-1)
-        if _frozen(sub_HT_dict):
+        if _frozen(sub_HT_dict) or _frozen_heads(sub_HT_dict):
             sub_HT_dict.drop_touching(a, b)
         else:
             for key in [key for key in sub_HT_dict if a in key or b in key]:
                 sub_HT_dict.pop(key)
-            if sub_HT_dict is g.source:
-                g.alive &= ~((g.ei == a) | (g.ei == b) | (g.ej == a) | (g.ej == b))
+        if sub_HT_dict is g.source:                        # either branch: a frozen HeadsHT of round 1 is g.source too (a SubHT never is)
+            g.alive &= ~((g.ei == a) | (g.ei == b) | (g.ej == a) | (g.ej == b))
         g.engine.drop(a, b)                                # the last two rows and columns leave the view; no copy
         return g
 
@@ -330,3 +333,158 @@ def bind_verdict(S, engine=None):
         return True
     compare_fast_sort_and_allhic.__wrapped__ = original
     return compare_fast_sort_and_allhic
+
+
+# ------------------------------------------------------------------ each group's H/T links from HT_links.pkl: run() :898-923, get_sub_HT_dict :117-143
+class _HeadsSession:
+    """what the containers below need of a session; the table's one also owns the open file (engine: _lib.LinkPickle or a stand-in)"""
+
+    def __init__(self, engine=None):
+        self.engine = engine
+        self.thaws = 0
+
+    def note_thawed(self):
+        self.thaws += 1
+        engine, self.engine = self.engine, None
+        if engine is not None:
+            engine.close()                                 # the dict holds every key now
+
+
+class HTTable(containers._Frozen):
+    """HT_link_dict of run() :899-901 while it is the arrays hhx_pickle_open left in the memory of the device: {(name, name): links}.  The
+    get_sub_HT_dict mirror works on the open handle; ANY other access thaws it into the defaultdict(int) pickle.load builds from the file, key by
+    key in the file's order.  When the table goes away (`del HT_link_dict; gc.collect()` :922-923) a finalizer closes the handle."""
+
+    def __init__(self, engine):
+        import weakref
+        containers._Frozen.__init__(self, int, _HeadsSession(engine), 'HT_links')
+        self._ids = None
+        self._finalizer = weakref.finalize(self, engine.close)
+
+    def _n(self):
+        return int(self._session.engine.n_keys)
+
+    def name_ids(self):
+        """{name: id}, from one fetch of the names alone"""
+        if self._ids is None:
+            names = self._session.engine.names()
+            self._ids = dict(zip(names, range(len(names))))
+        return self._ids
+
+    def _source_items(self):
+        from . import reassign
+        arrays = self._session.engine.arrays()
+        if arrays is None:
+            raise RuntimeError('HT_links: the table on the device cannot be turned into a dict (a name that is not UTF-8, or integers beyond 2^53 beside floats)')
+        return containers.LinkTable(reassign.PickleSession(*arrays), 'full')._source_items()
+
+
+class HeadsHT(containers._Frozen):
+    """The sub_HT_dict of get_sub_HT_dict :117-143: {(index, index): links} in the reference's insertion order — three arrays (int32, int32, int64)
+    until something other than the seams touches it; then the defaultdict(int) of Python ints the reference builds."""
+
+    def __init__(self, i, j, w):
+        containers._Frozen.__init__(self, int, _HeadsSession(), 'sub_HT_heads')
+        self.i, self.j, self.w = i, j, w
+
+    def _n(self):
+        return int(self.i.size)
+
+    def _source_items(self):
+        return zip(zip(self.i.tolist(), self.j.tolist()), self.w.tolist())
+
+    def drop_touching(self, a, b):
+        keep = ~((self.i == a) | (self.i == b) | (self.j == a) | (self.j == b))
+        self.i, self.j, self.w = self.i[keep], self.j[keep], self.w[keep]
+
+    def round1_arrays(self, shape):
+        """what _round1_arrays answers for the thawed dict, from the arrays"""
+        n = self.i.size
+        if n == 0 or shape < 4 or shape % 2 or int(self.w.min()) < 0 or int(self.w.max()) > 2 ** 53:
+            return None
+        if int(self.i.max()) >= shape or int(self.j.max()) >= shape:
+            return None
+        return self.i, self.j, self.w
+
+
+def _frozen_heads(d):
+    return isinstance(d, HeadsHT) and d.frozen
+
+
+class PickleProxy:
+    """What S.pickle is re-bound to: the pickle module, except that load(f) of a real file open for reading at its start goes through the device
+    reader and answers an HTTable; a file the reader refuses, and every other call, is pickle's own."""
+
+    def __init__(self, module, open_engine):
+        self._module, self._open = module, open_engine
+        self.tables = []                                   # the session of every table made here: .engine (None once closed by a thaw), .thaws
+
+    def __getattr__(self, name):                           # only what the proxy itself does not have
+        return getattr(self._module, name)
+
+    def load(self, file, *args, **kwargs):
+        import os
+        path = getattr(file, 'name', None)
+        try:
+            ours = (not args and not kwargs and isinstance(path, (str, bytes)) and os.path.isfile(path) and 'b' in getattr(file, 'mode', '')
+                    and file.tell() == 0)
+        except (OSError, ValueError):
+            ours = False
+        engine = self._open(path) if ours else None
+        if engine is None:
+            return self._module.load(file, *args, **kwargs)
+        file.seek(0, 2)                                    # as after pickle.load: the file has been read
+        table = HTTable(engine)
+        self.tables.append(table._session)
+        return table
+
+
+def _default_heads_engine(path):
+    from . import _lib
+    if DEVICE is not None:
+        _lib.check(_lib.load().hhx_set_device(DEVICE))
+    return _lib.LinkPickle.open(path)
+
+
+def bind_heads(S, engine=None):
+    """-> (the pickle proxy, the mirror of get_sub_HT_dict :117-143) for the imported HapHiC_sort module S.  engine(path): a stand-in for
+    _lib.LinkPickle.open (the tests' host reader): an object with n_keys, n_names, any_float, names(), arrays(), group_heads(n, slot, rank) and
+    close(), or None for a file it does not answer.  proxy.tables lists the session of every table the proxy made (engine None after a thaw;
+    thaws counts the thaws).
+
+    get_sub_HT_dict(ctgs, HT_link_dict) for a frozen HTTable: HT_index_dict is the real dict, by its closed form; sub_HT_dict is a HeadsHT over the
+    arrays of one hhx_pickle_group_heads call (the host does 2 n dict look-ups for the slots and one sort of the names).  Fewer than two contigs:
+    the two empty results, no device call.  Handed to the reference's function — on the thawed table when it was one of ours: a plain dict, a
+    table that was thawed, a contig listed twice or one that is no str, a table with float values, 2 n beyond int32."""
+    import pickle
+    from collections import defaultdict
+    original = getattr(S, 'get_sub_HT_dict', None)
+    proxy = PickleProxy(pickle, engine or _default_heads_engine)
+
+    def get_sub_HT_dict(ctgs, HT_link_dict):
+        if not (isinstance(HT_link_dict, HTTable) and HT_link_dict.frozen):
+            return original(ctgs, HT_link_dict)
+        n = len(ctgs)
+        if n < 2:
+            return defaultdict(int), dict()
+        eng = HT_link_dict._session.engine
+        if eng.any_float or 2 * n > 2 ** 31 - 1 or any(type(c) is not str for c in ctgs) or len(set(ctgs)) != n:
+            return original(ctgs, HT_link_dict)
+        ids = HT_link_dict.name_ids()
+        slot = np.full(eng.n_names, -1, np.int32)
+        for pos, ctg in enumerate(ctgs):
+            for suffix, tail in enumerate(('_H', '_T')):
+                k = ids.get(ctg + tail)
+                if k is not None:
+                    slot[k] = 2 * pos + suffix
+        rank = np.empty(n, np.int32)
+        rank[sorted(range(n), key=ctgs.__getitem__)] = np.arange(n, dtype=np.int32)
+        ei, ej, w = eng.group_heads(n, slot, rank)
+        lo, hi = sorted(ctgs[:2])
+        HT_index_dict = {lo + '_H': 0, hi + '_H': 1, hi + '_T': 2, lo + '_T': 3}
+        for k in range(2, n):
+            HT_index_dict[ctgs[k] + '_H'] = 2 * k
+            HT_index_dict[ctgs[k] + '_T'] = 2 * k + 1
+        return HeadsHT(ei, ej, w), HT_index_dict
+    get_sub_HT_dict.__wrapped__ = original
+    return proxy, get_sub_HT_dict

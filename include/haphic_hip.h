@@ -79,7 +79,11 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * rotations hhx_sort_verdict_sums runs with their tree in LDS, clamped to [0, 40959] (4-byte cells: lengths summing to less than 2^32) or [0, 20479]
  * (8-byte cells) (default 4095 / 2047: a tree of 16 KiB, above which a CU holds too few rotations to hide a step's latency; 0: every rotation on its
  * scratch slab in HBM; same bits); "pkl_chunk" = bytes per chunk of the opcode-boundary search of hhx_pickle_open, clamped to [512, 16384] (default 4096;
- * the same arrays, other seams).  value INT64_MIN: back to the default.  Unset knobs fall back to the
+ * the same arrays, other seams); "heads_bitmap" 0 = hhx_pickle_group_heads gathers the slot of both names of every key instead of testing them
+ * against the bitmap of the group's names in LDS first (default 1; tables of more than 2^19 names always gather; same arrays;
+ * tools/sort_heads_bench.py times both); "heads_grid" = the most workgroups (four wavefronts each, every wavefront one contiguous range of the table)
+ * of the passes of hhx_pickle_group_heads, clamped to [1, 1536] (default 1536; fewer: more steps per wavefront; same arrays).  value INT64_MIN: back
+ * to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
 int hhx_profile_enable(int on);
@@ -783,6 +787,22 @@ int hhx_pickle_open(const char *path, hhx_pickle **out);
 int hhx_pickle_sizes(hhx_pickle *p, int64_t *n_keys, int32_t *n_names, int64_t *names_bytes, int *any_float);
 int hhx_pickle_fetch(hhx_pickle *p, int32_t *name_i, int32_t *name_j, int64_t *value_bits, uint8_t *is_float, uint8_t *names_blob, int64_t *name_off);
 int hhx_pickle_free(hhx_pickle *p);
+/* One group's H/T links from the open table: HapHiC_sort.py get_sub_HT_dict :117-143, which run() :898-901 / :912-920 calls per group on the dict
+ * pickle.load built from HT_links.pkl.  For ctgs in the order parse_group returns them (n = n_ctg distinct names, 2 <= n < 2^30) the caller passes
+ * slot [n_names] = 2 * position + suffix (0: '_H', 1: '_T') for the names ctg + '_H' / ctg + '_T' the file holds (whole names: nothing is stripped from a
+ * name of the file) and -1 for every other name, and rank [n] = the place of every position among the sorted names (Python's string order; a
+ * permutation).  A key (x, y): v of the table is kept exactly when x and y are slotted names of two different contigs c1, c2, c1 < c2 as strings
+ * (rank), and v != 0; keys written the other way round, keys between the two ends of one contig and zero values never are.  A kept key becomes
+ * (index[x], index[y]): v with HT_index_dict's closed form — lo, hi = sorted(ctgs[:2]): lo_H = 0, hi_H = 1, hi_T = 2, lo_T = 3; ctgs[k]_H = 2 k,
+ * ctgs[k]_T = 2 k + 1 from k = 2 on — and the edges are left in the handle in the reference's insertion order: ascending in
+ * ((a * n + b) << 2) | (2 * [x ends in T] + [y ends in T]), a < b the positions of the two contigs.  On the device: a streaming pass over the ids of
+ * the table (both ends are first tested against a bitmap of the slotted names in LDS: hhx_tune "heads_bitmap") that counts the survivors of every
+ * wavefront's range, the same pass again to write them (ballot and prefix inside the wavefront, no counter shared between wavefronts), and a stable
+ * radix sort on the 2 * ceil(log2 n) + 2 bits of that order key; nothing of slot / rank is kept between calls.  *n_edges: the edges found;
+ * hhx_pickle_group_heads_fetch copies the last call's ei / ej (int32 indices) and w (int64 values) into host arrays (any may be NULL).  A table with
+ * float values, n_ctg outside 2 .. 2^30 - 1, a slot outside -1 .. 2 n - 1 and a rank that is no permutation are errors. */
+int hhx_pickle_group_heads(hhx_pickle *p, int32_t n_ctg, const int32_t *slot, const int32_t *rank, int64_t *n_edges);
+int hhx_pickle_group_heads_fetch(hhx_pickle *p, int32_t *ei, int32_t *ej, int64_t *w);
 
 /* ---------------------------------------------------------------- assembly correction (--correct_nrounds), haphic_amd/csrc/hhx_correct.hip
  * Pass one — parse_pairs_for_correction :1300-1344 / parse_bam_for_correction :1362-1398.  hhx_correct_create: contig c (fa_dict order, ctg_len
