@@ -12,8 +12,9 @@ split_clm_file (paired_links.clm split into split_clms/<group>.clm, haphic_amd/r
 and so do the rescue and reassignment rounds (run_reassignment :266-427) and the group-pair sums of the agglomerative step (:489-560) between them
 (patch_reassign(R, rounds=True)); run() :752-916 is the reference's, called as its main() :919-924 calls it.
 `python -m haphic_amd sort <arguments of "haphic sort">` wraps HapHiC_sort.py: the dense work of fast sorting (link matrix, density graph, confidence
-graph and the link re-aggregation of every round, haphic_amd/sort.py) runs on the device (haphic_amd.patch.patch_sort); fast_sort's loop, the spanning
-forest, the ALLHiC child per group and run() :847-959 are the reference's, its process pool replaced by threads; called as its main() :962-967 does.
+graph and the link re-aggregation of every round, haphic_amd/sort.py) runs on the device (haphic_amd.patch.patch_sort), and so does the forest block of every round (:567-595: filter, maximum spanning forest, the position of every node
+along its path; patch_sort(S, forest=True)), from which the host builds the small networkx graph that settles the order and direction of the paths;
+fast_sort's loop, the ALLHiC child per group and run() :847-959 are the reference's, its process pool replaced by threads; called as its main() :962-967 does.
 The front of run() :898-923 runs on the device too: HT_links.pkl is read into arrays that stay there and each group's sub_HT_dict / HT_index_dict
 (get_sub_HT_dict :117-143) comes from two streaming passes over them and a sort of the survivors (patch_sort(S, heads=True)).  `sort` with nothing after it has nothing to hand on and exits with a usage message.
 `python -m haphic_amd build <arguments of "haphic build">` wraps HapHiC_build.py: parse_fasta (HapHiC_cluster.py:87-113: the FASTA text goes to HBM in one piece
@@ -76,6 +77,16 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              device memory.  A file still goes through pickle.load when the reader does not answer it (as --keep-reference-pickle lists),
                              and a group goes to the reference's function — on the table turned into the dict pickle.load gives — when a contig is listed
                              twice, the table holds float values, or 2 n is beyond int32
+  --keep-reference-forest    sort only: leave the forest block of every round of fast_sort (:567-595) to the reference: the 8 * shape^2 byte confidence array is
+                             copied to the host, networkx.Graph() scans all its cells in Python, Kruskal sorts tuples and shortest_path computes all pairs of
+                             every tree to read one path.  Without the flag the array stays on the device, one call filters it and builds the maximum
+                             spanning forest with every node's tree and position along its path (haphic_amd/sort.py bind_forest, csrc/hhx_sort.hip), and the
+                             host builds the networkx graph of the chosen edges alone, asks networkx for the components and their ends, and reads each path
+                             off the positions: the same paths in the same order and direction, the same tour files and log lines.  A round still goes to
+                             the reference's block, on the array fetched from the device, when its forest is no set of paths (a cutoff below 1 can fork a
+                             tree; the reference then fails its assert as before), when the group runs the reference's functions already (as
+                             dict_to_matrix decides in round 1, or after foreign code touched its sub_HT_dict or the confidence token), beyond shape
+                             65535, and when maximum_spanning_tree is called with anything but algorithm='kruskal'
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
                              (the .pairs path needs neither; BAM input then fails loudly inside the reference)
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
@@ -140,6 +151,7 @@ def main(argv=None):
     keep_build = bool(_take(argv, '--keep-reference-build', False))
     keep_verdict = bool(_take(argv, '--keep-reference-verdict', False))
     keep_heads = bool(_take(argv, '--keep-reference-heads', False))
+    keep_forest = bool(_take(argv, '--keep-reference-forest', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
     scripts = _reference_scripts(ref)
     if stub:
@@ -174,6 +186,8 @@ def main(argv=None):
         from . import sort
         sort.DEVICE = device                                        # the pool's threads select it before their first call
         patch.patch_sort(S, verdict=not keep_verdict)
+        if not keep_forest:
+            patch.patch_sort_forest(S)                              # == patch_sort(S, ..., forest=True)
         if not keep_heads:
             patch.patch_sort_heads(S)                               # == patch_sort(S, ..., heads=True)
         sys.argv = ['haphic sort'] + argv

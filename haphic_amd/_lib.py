@@ -225,6 +225,11 @@ SIGNATURES = {
     'hhx_sort_graph_fetch_dense': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     'hhx_sort_graph_stats': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_sort_graph_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_sort_graph_confidence_device': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_fetch_confidence': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_forest': (C.c_int, [C.c_void_p, C.c_double, c_i64p, c_i32p]),
+    'hhx_sort_graph_fetch_forest': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_sort_graph_forest_stats': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_sort_verdict_sums': (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'hhx_fasta_open': (C.c_int, [C.c_char_p, C.c_int, c_vpp]),
     'hhx_fasta_open_bytes': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, c_vpp]),
@@ -964,6 +969,7 @@ class SortGraph:
     Built from the round-1 edges (index pairs, integer weights); tests/sort_cases.py holds a numpy engine with the same interface."""
     METHODS = {'sum': 0, 'multiplication': 1, 'geometric_mean': 2}
     STATS = ('lds_aggregations', 'global_aggregations', 'cells_over', 'pairs_flagged')
+    FOREST_STATS = ('lds_forests', 'hbm_forests', 'boruvka_rounds', 'jump_rounds', 'confidence_copies')
 
     def __init__(self, shape, ei, ej, w):
         ei, ej = np.ascontiguousarray(ei, np.int32), np.ascontiguousarray(ej, np.int32)
@@ -1005,6 +1011,36 @@ class SortGraph:
         buf = np.empty(n * n + 1, np.float64)
         check(load().hhx_sort_graph_confidence(self.h, pa.size, ptr(pa) if pa.size else None, ptr(pb) if pb.size else None, ptr(buf)))
         return buf[:n * n].reshape(n, n), buf[n * n]
+
+    def confidence_device(self, pair_a, pair_b):
+        """confidence() without the copy: the array stays on the device (forest, fetch_confidence) -> MAXS as numpy.float64"""
+        pa, pb = np.ascontiguousarray(pair_a, np.int32), np.ascontiguousarray(pair_b, np.int32)
+        maxs = np.empty(1, np.float64)
+        check(load().hhx_sort_graph_confidence_device(self.h, pa.size, ptr(pa) if pa.size else None, ptr(pb) if pb.size else None, ptr(maxs)))
+        return maxs[0]
+
+    def fetch_confidence(self):
+        """the confidence array as it is on the device now (filtered, once forest() ran)"""
+        n = self.shape
+        out = np.empty((n, n), np.float64)
+        check(load().hhx_sort_graph_fetch_confidence(self.h, ptr(out)))
+        return out
+
+    def forest(self, cutoff):
+        """filter_confidence_graph + the maximum spanning forest of networkx's Kruskal on the device -> (eu, ev, label, pos, not_paths): the chosen
+        edges (u < v) in Kruskal's order, the smallest index of every node's tree, the position along its path from the smaller-index end (-1
+        everywhere when not_paths: some node has no edge or more than two)"""
+        nch, bad = C.c_int64(0), C.c_int32(0)
+        check(load().hhx_sort_graph_forest(self.h, float(cutoff), C.byref(nch), C.byref(bad)))
+        n = self.shape
+        eu, ev, label, pos = np.empty(nch.value, np.int32), np.empty(nch.value, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+        check(load().hhx_sort_graph_fetch_forest(self.h, ptr(eu) if nch.value else None, ptr(ev) if nch.value else None, ptr(label), ptr(pos)))
+        return eu, ev, label, pos, bool(bad.value)
+
+    def forest_stats(self):
+        v = np.zeros(len(self.FOREST_STATS), np.int64)
+        check(load().hhx_sort_graph_forest_stats(self.h, ptr(v)))
+        return dict(zip(self.FOREST_STATS, (int(x) for x in v)))
 
     def drop(self, a, b):
         check(load().hhx_sort_graph_drop(self.h, int(a), int(b)))

@@ -228,7 +228,18 @@ SORT_HEADS_SEAMS = {
 }
 
 
-def patch_sort(S, engine=None, verdict=False, verdict_engine=None, heads=False, heads_engine=None):
+# the forest block of fast_sort :567-595 (haphic_amd/sort.py bind_forest).  OPT-IN at this level: patch_sort(S, forest=True); `python -m haphic_amd sort`
+# asks for it unless --keep-reference-forest is given.
+SORT_FOREST_SEAMS = {
+    'get_unfiltered_confidence_graph': 'HapHiC_sort.py:195-244',      # no copy of the array: a token and MAXS
+    'filter_confidence_graph': 'HapHiC_sort.py:247-255',              # records the cutoff; the device call filters
+    'Graph': 'HapHiC_sort.py:24 (Graph(confidence_graph) :570)',
+    'nxtree': 'HapHiC_sort.py:25 (nxtree.maximum_spanning_tree :570)',
+    'shortest_path': 'HapHiC_sort.py:24 (dict(shortest_path(tree))[source][target] :590)',
+}
+
+
+def patch_sort(S, engine=None, verdict=False, verdict_engine=None, heads=False, heads_engine=None, forest=False):
     """S: the imported HapHiC_sort module.  The dense work of fast sorting goes to the device (haphic_amd/sort.py); fast_sort, the spanning forest,
     split_new_scaffold, the .tour writer, the ALLHiC child and run() stay the reference's.  run() :875-876 forks a multiprocessing.Pool: a process
     that has initialised the GPU must not be forked into workers that use it, so S.Pool becomes the ThreadPool (same apply_async / close / join);
@@ -237,7 +248,9 @@ def patch_sort(S, engine=None, verdict=False, verdict_engine=None, heads=False, 
     sums of all rotations come from one library call; verdict_engine: a stand-in for _lib.sort_verdict_sums (the tests' host engine); `python -m
     haphic_amd sort` asks for it.  heads=True: S.pickle becomes a proxy of the pickle module whose load() reads HT_links.pkl into arrays on the device
     (run() :898-901) and get_sub_HT_dict :117-143 is re-bound to extract every group from them there (SORT_HEADS_SEAMS; sort.bind_heads lists what
-    goes to the reference's function); heads_engine: a stand-in for _lib.LinkPickle.open (the tests' host reader).  Returns {name: original}."""
+    goes to the reference's function); heads_engine: a stand-in for _lib.LinkPickle.open (the tests' host reader).  forest=True: the forest block
+    :567-595 runs on the device too (SORT_FOREST_SEAMS; sort.bind_forest lists what goes back to the reference's block); the engine needs
+    confidence_device / forest / fetch_confidence, with one that has no forest() every round is the reference's.  Returns {name: original}."""
     from multiprocessing.pool import ThreadPool
     from . import sort
     if engine is None or (verdict and verdict_engine is None):
@@ -252,8 +265,23 @@ def patch_sort(S, engine=None, verdict=False, verdict_engine=None, heads=False, 
     for name, fn in mirrors.items():
         setattr(S, name, fn)
     S.Pool = ThreadPool
+    if forest:
+        saved.update(patch_sort_forest(S))
     if heads:
         saved.update(patch_sort_heads(S, heads_engine))
+    return saved
+
+
+def patch_sort_forest(S):
+    """The seams of SORT_FOREST_SEAMS alone, for a module patch_sort has been applied to (patch_sort(S, forest=True) ends here; the wrapper command
+    calls it after patch_sort unless --keep-reference-forest is given).  Returns {name: what
+    was bound before} for the names patch_sort has not saved yet."""
+    from . import sort
+    mirrors = sort.bind_forest(S)
+    assert set(mirrors) == set(SORT_FOREST_SEAMS)
+    saved = {name: getattr(S, name, None) for name in ('Graph', 'nxtree', 'shortest_path')}
+    for name, fn in mirrors.items():
+        setattr(S, name, fn)
     return saved
 
 

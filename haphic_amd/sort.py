@@ -1,6 +1,7 @@
 """`haphic sort` (scripts/HapHiC_sort.py), fast sorting on the MI355X library: the dense work of fast_sort :470-615 per group and round.
 
-fast_sort itself, the spanning forest :570-595, split_new_scaffold, output_tour_file, the ALLHiC optimisation and run() stay the reference's code;
+fast_sort itself, split_new_scaffold, output_tour_file, the ALLHiC optimisation and run() stay the reference's code, and so does the spanning
+forest :570-595 unless bind_forest is asked for;
 the functions below replace the module globals fast_sort resolves at call time (patch.patch_sort):
 
     dict_to_matrix :60-88                     round 1: the dict's edges go to the device once (_lib.SortGraph), later rounds: the handle again
@@ -19,7 +20,14 @@ weighted-LIS sums of the rotations :696-721 come from one library call (_lib.sor
 :712-716 and both log lines stay here, in Python ints and floats.
 
 bind_heads: the front of run() :898-923.  S.pickle becomes a PickleProxy whose load() reads HT_links.pkl into arrays on the device (HTTable) and
-get_sub_HT_dict :117-143 extracts each group from them there (HeadsHT, which round 1 of dict_to_matrix takes as arrays)."""
+get_sub_HT_dict :117-143 extracts each group from them there (HeadsHT, which round 1 of dict_to_matrix takes as arrays).
+
+bind_forest (opt-in): the forest block :567-595.  The confidence array stays on the device (a ConfidenceToken stands for it), one library call
+filters it and builds the maximum spanning forest with every node's tree and position along its path (_lib.SortGraph.forest); the host builds the
+networkx graph of the chosen edges, asks networkx itself for components, ends and their order, and reads each path off the positions.  Handed back to
+the reference's block on the fetched array: a forest that is no set of paths (the reference asserts), an engine without forest(), a group in
+host_mode or whose sub_HT_dict is no longer the device's edge list, a token thawed by foreign code, a shape above 65535, a maximum_spanning_tree
+call that is not (token, algorithm='kruskal')."""
 import threading
 from itertools import product
 
@@ -55,6 +63,8 @@ class Graph:
         self.host_mode = False                            # a SubHT was thawed by foreign code: the rest of the group runs the reference's functions
         self._lookup = None
         self.thaws = 0
+        self.forest_rounds = 0                            # bind_forest: rounds whose forest came from the device ...
+        self.forest_thaws = 0                             # ... and confidence arrays fetched for the reference's own block
 
     def note_thawed(self):
         self.thaws += 1
@@ -271,6 +281,176 @@ def bind(S, engine=None):
 
     return {'dict_to_matrix': dict_to_matrix, 'get_density_graph': get_density_graph, 'get_unfiltered_confidence_graph': get_unfiltered_confidence_graph,
             'filter_confidence_graph': filter_confidence_graph, 'remove_shortest_path': remove_shortest_path, 'update': update, 'fast_sort': fast_sort}
+
+
+# ------------------------------------------------------------------ the spanning forest and its paths: fast_sort :567-595
+FOREST_KEY = 'hhx_forest'             # T.graph[FOREST_KEY] = (label, pos) on the networkx graph the forest mirror returns
+FOREST_MAX_SHAPE = 65535              # hhx_sort_graph_forest's limit (its sort key holds u * shape + v in 32 bits)
+
+
+class ConfidenceToken:
+    """What get_unfiltered_confidence_graph hands to fast_sort in place of the float64 array while that array stays on the device.  The forest seams
+    recognise it; ANYTHING else done to it (numpy.asarray, indexing, an attribute) thaws it into the array through one fetch_confidence, after
+    which the round is the reference's: Graph(token) is networkx's Graph of that array."""
+
+    def __init__(self, graph, shape):
+        self.__dict__.update(_graph=graph, _shape=shape, _pending=None, _filtered=False, _array=None)
+
+    def _record(self, sub_HT_dict, cutoff, host_filter):
+        self.__dict__['_pending'] = (sub_HT_dict, cutoff, host_filter)
+
+    def _thaw(self):
+        d = self.__dict__
+        if d['_array'] is None:
+            d['_array'] = d['_graph'].engine.fetch_confidence()
+            d['_graph'].forest_thaws += 1
+            if d['_pending'] is not None and not d['_filtered']:      # the cutoff was recorded, the device call that applies it never ran
+                sub_HT_dict, cutoff, host_filter = d['_pending']
+                host_filter(d['_array'], sub_HT_dict, cutoff)
+            d['_filtered'] = True
+        return d['_array']
+
+    def __array__(self, dtype=None, copy=None):
+        a = self._thaw()
+        return a if dtype is None else a.astype(dtype)
+
+    def __getattr__(self, name):                           # only what the token itself does not have
+        if name.startswith('__') and name.endswith('__'):
+            raise AttributeError(name)
+        return getattr(self._thaw(), name)
+
+    def __getitem__(self, key):
+        return self._thaw()[key]
+
+    def __setitem__(self, key, value):
+        self._thaw()[key] = value
+
+    def __len__(self):
+        return len(self._thaw())
+
+    def __iter__(self):
+        return iter(self._thaw())
+
+
+class _PathsFrom:
+    def __init__(self, paths, source):
+        self._paths, self._source = paths, source
+
+    def __getitem__(self, target):
+        return self._paths.path(self._source, target)
+
+    def keys(self):
+        return self._paths.keys()
+
+
+class ForestPaths:
+    """dict(shortest_path(tree))[source][target] for a tree of the forest mirror's T: a mapping whose values are mappings, every path read off `pos`
+    when it is asked for — O(path length), where networkx computes all pairs."""
+
+    def __init__(self, tree, pos):
+        self._nodes = list(tree)
+        self._pos = pos
+        self._along = None
+
+    def keys(self):
+        return list(self._nodes)
+
+    def __iter__(self):                                    # networkx 3.5: an iterator of (source, {target: path}) pairs; dict() takes either
+        return iter(self._nodes)
+
+    def __len__(self):
+        return len(self._nodes)
+
+    def __getitem__(self, source):
+        return _PathsFrom(self, source)
+
+    def path(self, source, target):
+        if self._along is None:
+            along = [None] * len(self._nodes)
+            for v in self._nodes:
+                along[self._pos[v]] = v
+            self._along = along
+        a, b = self._pos[source], self._pos[target]
+        return self._along[a:b + 1] if a <= b else self._along[b:a + 1][::-1]
+
+
+class NxTreeProxy:
+    """What S.nxtree is re-bound to: networkx.tree, except maximum_spanning_tree(token, algorithm='kruskal')."""
+
+    def __init__(self, module, forest):
+        self._module, self._forest = module, forest
+
+    def __getattr__(self, name):
+        return getattr(self._module, name)
+
+    def maximum_spanning_tree(self, G, *args, **kwargs):
+        return self._forest(G, args, kwargs)
+
+
+def bind_forest(S):
+    """The forest block of fast_sort :567-595 on the device, for a module S that bind()'s mirrors are already bound to -> {name: object} for the
+    globals fast_sort resolves at call time: get_unfiltered_confidence_graph (answers a ConfidenceToken and MAXS: no copy of the array),
+    filter_confidence_graph (records the cutoff), Graph (passes the token on), nxtree (NxTreeProxy: one engine.forest(cutoff) call, then the real
+    networkx graph T — nodes 0 .. shape - 1, then the chosen edges in Kruskal's order — which networkx's own connected_components / subgraph /
+    degree answer on as they do on the reference's forest, so that the direction of every path is the reference's) and shortest_path (ForestPaths
+    for a subgraph of such a T).  connected_components stays networkx's.
+
+    A round goes to the reference's block, on the array fetched from the device, when: the forest is no set of paths (not_paths: the reference then
+    fails its assert :586 as before); the engine has no forest(); the group is in host_mode or its sub_HT_dict is no longer the arrays the device
+    holds; the token was thawed by foreign code; the shape exceeds 65535; maximum_spanning_tree is called with anything but algorithm='kruskal'."""
+    prev_conf, prev_filter = getattr(S, 'get_unfiltered_confidence_graph', None), getattr(S, 'filter_confidence_graph', None)
+    nx_graph, nx_tree, nx_shortest = getattr(S, 'Graph', None), getattr(S, 'nxtree', None), getattr(S, 'shortest_path', None)
+
+    def _ours(sub_HT_dict, g):
+        return _frozen(sub_HT_dict) or (sub_HT_dict is g.source and not g.host_mode)      # the edges bind()'s filter_confidence_graph works on
+
+    def get_unfiltered_confidence_graph(shape, index_pairs, sub_HT_dict, density_graph):
+        g = density_graph
+        if (not isinstance(g, Graph) or g.host_mode or not hasattr(g.engine, 'forest') or shape > FOREST_MAX_SHAPE or not _ours(sub_HT_dict, g)):
+            return prev_conf(shape, index_pairs, sub_HT_dict, density_graph)
+        pairs = np.array(index_pairs, np.int32).reshape(-1, 2)
+        maxs = g.engine.confidence_device(pairs[:, 0], pairs[:, 1])
+        return ConfidenceToken(g, shape), maxs
+
+    def filter_confidence_graph(confidence_graph, sub_HT_dict, confidence_cutoff):
+        if not isinstance(confidence_graph, ConfidenceToken):
+            return prev_filter(confidence_graph, sub_HT_dict, confidence_cutoff)
+        d = confidence_graph.__dict__
+        if d['_array'] is not None or not _ours(sub_HT_dict, d['_graph']):
+            return prev_filter(confidence_graph._thaw(), sub_HT_dict, confidence_cutoff)
+        confidence_graph._record(sub_HT_dict, confidence_cutoff, prev_filter)
+
+    def graph(data=None, **attr):
+        if isinstance(data, ConfidenceToken):
+            return data if data.__dict__['_array'] is None else nx_graph(data.__dict__['_array'], **attr)
+        return nx_graph(data, **attr)
+
+    def forest(G, args, kwargs):
+        if not isinstance(G, ConfidenceToken):
+            return nx_tree.maximum_spanning_tree(G, *args, **kwargs)
+        d = G.__dict__
+        if d['_array'] is None and d['_pending'] is not None and not args and kwargs == {'algorithm': 'kruskal'}:
+            g = d['_graph']
+            eu, ev, label, pos, not_paths = g.engine.forest(d['_pending'][1])
+            d['_filtered'] = True
+            if not not_paths:
+                g.forest_rounds += 1
+                T = nx_graph()                             # networkx.Graph, as the module imported it
+                T.add_nodes_from(range(d['_shape']))
+                T.add_edges_from(zip(eu.tolist(), ev.tolist()))
+                T.graph[FOREST_KEY] = (label.tolist(), pos.tolist())
+                return T
+        return nx_tree.maximum_spanning_tree(nx_graph(G._thaw()), *args, **kwargs)
+
+    def shortest_path(G, *args, **kwargs):
+        held = getattr(G, 'graph', None)
+        held = held.get(FOREST_KEY) if isinstance(held, dict) else None
+        if held is None or args or kwargs:
+            return nx_shortest(G, *args, **kwargs)
+        return ForestPaths(G, held[1])
+
+    return {'get_unfiltered_confidence_graph': get_unfiltered_confidence_graph, 'filter_confidence_graph': filter_confidence_graph, 'Graph': graph,
+            'nxtree': NxTreeProxy(nx_tree, forest), 'shortest_path': shortest_path}
 
 
 # ------------------------------------------------------------------ fast sorting or ALLHiC: compare_fast_sort_and_allhic :645-724

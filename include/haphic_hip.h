@@ -82,7 +82,8 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * the same arrays, other seams); "heads_bitmap" 0 = hhx_pickle_group_heads gathers the slot of both names of every key instead of testing them
  * against the bitmap of the group's names in LDS first (default 1; tables of more than 2^19 names always gather; same arrays;
  * tools/sort_heads_bench.py times both); "heads_grid" = the most workgroups (four wavefronts each, every wavefront one contiguous range of the table)
- * of the passes of hhx_pickle_group_heads, clamped to [1, 1536] (default 1536; fewer: more steps per wavefront; same arrays).  value INT64_MIN: back
+ * of the passes of hhx_pickle_group_heads, clamped to [1, 1536] (default 1536; fewer: more steps per wavefront; same arrays); "sort_forest_lds" = the largest shape whose hhx_sort_graph_forest runs as one
+ * workgroup on LDS arrays, clamped to [0, 2048] (default 2048; 0: always the multi-launch form in HBM; same arrays).  value INT64_MIN: back
  * to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
@@ -886,8 +887,21 @@ int hhx_remap_destroy(hhx_remap *r);
  *   them in the reference's order and hands the values to hhx_sort_graph_patch_cells (ordinal: the edge's position in the list).
  * hhx_sort_graph_fetch_dense: the leading shape x shape block of the link matrix (which = 0) or the density graph (1), row-major float32.
  * hhx_sort_graph_stats: values[HHX_SORT_GRAPH_N_STATS] = re-aggregations through LDS, through global atomics, cells above 2^24 of the last one, flagged
- *   pairs of the last density call. */
+ *   pairs of the last density call.
+ * hhx_sort_graph_confidence_device — hhx_sort_graph_confidence without the copy: the matrix stays on the device, *maxs receives MAXS (8 bytes).
+ *   hhx_sort_graph_fetch_confidence copies the shape x shape matrix as it is now (filtered, once hhx_sort_graph_forest ran) into out[shape * shape].
+ * hhx_sort_graph_forest — fast_sort :567-570 on the matrix of the last confidence call: filter_confidence_graph :247-255 (cells of the current edges
+ *   with C <= cutoff become 0, both triangles), then the forest nxtree.maximum_spanning_tree(Graph(C), algorithm='kruskal') returns: the unique maximum
+ *   spanning forest under the strict order (weight descending, u ascending, v ascending), u < v, over the non-zero cells of the current edges and the
+ *   sister pairs (a pair that is both counts once).  *n_chosen: its edges; *not_paths: 1 when some node has no edge or more than two (fast_sort then
+ *   fails its assert :586).  One workgroup on LDS arrays while shape <= 2048 and the edges fit beside the node arrays (12 bytes an edge slot, a power
+ *   of two of slots, 48 bytes a node, 160 KiB in all: 4096 edges at shape 2048), hhx_tune "sort_forest_lds"; one launch per phase on HBM arrays above.
+ *   shape <= 65535.  hhx_sort_graph_fetch_forest: eu / ev[n_chosen] (u < v) in the order Kruskal emits them, label[shape] = the smallest index of the
+ *   node's tree, pos[shape] = the node's position along its path counted from the end with the smaller index (-1 everywhere when not_paths).
+ * hhx_sort_graph_forest_stats: values[HHX_SORT_FOREST_N_STATS] = forests through LDS, through HBM, Boruvka rounds and pointer-doubling rounds of the
+ *   last one, copies of the confidence matrix to the host (hhx_sort_graph_confidence and hhx_sort_graph_fetch_confidence). */
 #define HHX_SORT_GRAPH_N_STATS 4
+#define HHX_SORT_FOREST_N_STATS 5
 typedef struct hhx_sort_graph hhx_sort_graph;
 int hhx_sort_graph_create(int32_t shape, int64_t n_edges, const int32_t *ei, const int32_t *ej, const int64_t *w, hhx_sort_graph **out);
 int hhx_sort_graph_shape(const hhx_sort_graph *g, int32_t *shape, int64_t *ld, int64_t *n_edges);
@@ -903,6 +917,11 @@ int hhx_sort_graph_patch_cells(hhx_sort_graph *g, int64_t n, const int64_t *cell
 int hhx_sort_graph_fetch_dense(hhx_sort_graph *g, int which, float *out);
 int hhx_sort_graph_stats(const hhx_sort_graph *g, int64_t *values);
 int hhx_sort_graph_destroy(hhx_sort_graph *g);
+int hhx_sort_graph_confidence_device(hhx_sort_graph *g, int32_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double *maxs);
+int hhx_sort_graph_fetch_confidence(hhx_sort_graph *g, double *out);
+int hhx_sort_graph_forest(hhx_sort_graph *g, double cutoff, int64_t *n_chosen, int32_t *not_paths);
+int hhx_sort_graph_fetch_forest(hhx_sort_graph *g, int32_t *eu, int32_t *ev, int32_t *label, int32_t *pos);
+int hhx_sort_graph_forest_stats(const hhx_sort_graph *g, int64_t *values);
 
 /* ---------------------------------------------------------------- `haphic sort`: fast sorting or ALLHiC (HapHiC_sort.py compare_fast_sort_and_allhic :645-724)
  * hhx_sort_verdict_sums — the sums behind the verdict, in place of the rotation loop :696-721 with its two find_lis passes :647-672 and its .index sweep

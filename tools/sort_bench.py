@@ -4,6 +4,12 @@ profiles/sort_bench.json.  A record, not a gate.
 
     python tools/sort_bench.py [--contigs 3000] [--out profiles/sort_bench.json]
     python tools/sort_bench.py --reference-only --reference path/to/HapHiC/scripts [--prefix 600]      (no GPU: times the reference alone)
+    python tools/sort_bench.py --forest-bench [--sizes 3000,10000] [--repeats 3] [--parent FILE]       (writes profiles/sort_forest_bench.json)
+
+--forest-bench times the forest block of every round both ways on the same groups in one process: the host way (the confidence array copied to the
+host, filtered there, networkx's Graph / maximum_spanning_tree / one shortest_path per tree) and the device way of haphic_amd/sort.py bind_forest
+(confidence_device, one forest() call, the networkx graph of the chosen edges with networkx's components and ends, the paths read off the
+positions).  --parent: a JSON file {contigs: [wall seconds ...]} measured with this tool's loop at the parent commit in the same session.
 
 The group: --contigs contigs (default 3000, shape 6000) planted as a chain in a random order and orientation (tests/sort_cases.chain_case: strong
 links between neighbours, weaker ones two and three steps away, noise), default density method ('multiplication'), cutoff 1, no flanking region.
@@ -30,6 +36,7 @@ from tests import sort_cases as sc      # noqa: E402
 
 KERNELS = ('sort_matrix', 'sort_density', 'sort_confidence', 'sort_aggregate', 'sort_emit')
 COPIES = ('sort_confidence_copy',)
+FOREST_KERNELS = ('sort_forest_lds', 'sort_forest_edges', 'sort_forest_round', 'sort_forest_emit', 'sort_forest_jump')      # the radix sort of the HBM form is untimed
 SEED = 4242
 
 
@@ -67,9 +74,12 @@ def edges_of(case):
     return 2 * len(info), (keys[:, 0], keys[:, 1], np.array(list(case.links.values()), np.int64)), np.repeat([ln / 2 for _, ln in info], 2)
 
 
-def device_run(case, cutoff=1.0, profile=True):
+def device_run(case, cutoff=1.0, profile=True, forest='host'):
+    """forest: 'host' — the array comes to the host and networkx builds the forest; 'device' — SortGraph.forest and the read-out of bind_forest"""
     import networkx as nx
     from haphic_amd import _lib
+    from haphic_amd import sort as hsort
+    kernels = KERNELS + (FOREST_KERNELS if forest == 'device' else ())
     shape, (ei, ej, w), end_len = edges_of(case)
     clock = time.perf_counter
     rounds = []
@@ -80,7 +90,7 @@ def device_run(case, cutoff=1.0, profile=True):
         t0 = clock()
         eng = _lib.SortGraph(shape, ei, ej, w)
         create_s = clock() - t0
-        create_events = {k: _lib.profile_get(k)[0] for k in KERNELS + COPIES}
+        create_events = {k: _lib.profile_get(k)[0] for k in kernels + COPIES}
         members = [[k] for k in range(shape)]            # the old ends behind every current index
         cur_i, cur_j = ei.astype(np.int64), ej.astype(np.int64)
         pairs = np.arange(shape, dtype=np.int32).reshape(-1, 2)
@@ -93,13 +103,16 @@ def device_run(case, cutoff=1.0, profile=True):
                 eng.density([float(sum(end_len[m] for m in ms)) for ms in members], 'multiplication')
                 rec['density_call_s'] = clock() - t0
             t0 = clock()
-            C, maxs = eng.confidence(pairs[:, 0], pairs[:, 1])
+            if forest == 'device':
+                C, maxs = None, eng.confidence_device(pairs[:, 0], pairs[:, 1])
+            else:
+                C, maxs = eng.confidence(pairs[:, 0], pairs[:, 1])
+                rec['confidence_bytes'] = int(C.nbytes)
             rec['confidence_call_s'] = clock() - t0
-            rec['confidence_bytes'] = int(C.nbytes)
             rec['maxs'] = float(maxs)
             if maxs <= cutoff:
                 if len(pairs) <= 2:
-                    rec['events_ms'] = {k: _lib.profile_get(k)[0] for k in KERNELS + COPIES}
+                    rec['events_ms'] = {k: _lib.profile_get(k)[0] for k in kernels + COPIES}
                     rounds.append(rec)
                     break
                 a, b = (int(v) for v in pairs[-1])
@@ -109,26 +122,47 @@ def device_run(case, cutoff=1.0, profile=True):
                 eng.drop(a, b)
                 fresh = False
                 rec['removed'] = True
-                rec['events_ms'] = {k: _lib.profile_get(k)[0] for k in KERNELS + COPIES}
+                rec['events_ms'] = {k: _lib.profile_get(k)[0] for k in kernels + COPIES}
                 rounds.append(rec)
                 continue
-            t0 = clock()
-            low = C[cur_i, cur_j] <= cutoff
-            C[cur_i[low], cur_j[low]] = 0
-            C[cur_j[low], cur_i[low]] = 0
-            rec['filter_s'] = clock() - t0
-            t0 = clock()
-            forest = nx.tree.maximum_spanning_tree(nx.Graph(C), algorithm='kruskal')
-            rec['forest_s'] = clock() - t0
-            t0 = clock()
             paths = []
-            for nodes in nx.connected_components(forest):
-                tree = forest.subgraph(nodes)
-                ends = [v for v, d in tree.degree() if d == 1]
-                path = nx.shortest_path(tree, ends[0], ends[1])
-                paths.append((path, sum(end_len[m] for v in path for m in members[v])))
+            if forest == 'device':
+                t0 = clock()
+                eu, ev, _label, pos, not_paths = eng.forest(cutoff)
+                rec['forest_call_s'] = clock() - t0
+                assert not not_paths
+                t0 = clock()
+                T = nx.Graph()
+                T.add_nodes_from(range(eng.shape))
+                T.add_edges_from(zip(eu.tolist(), ev.tolist()))
+                pos = pos.tolist()
+                trees = []
+                for nodes in nx.connected_components(T):
+                    tree = T.subgraph(nodes)
+                    trees.append((tree, [v for v, d in tree.degree() if d == 1]))
+                rec['tree_ends_s'] = clock() - t0
+                t0 = clock()
+                for tree, ends in trees:
+                    path = dict(hsort.ForestPaths(tree, pos))[ends[0]][ends[1]]
+                    paths.append((path, sum(end_len[m] for v in path for m in members[v])))
+                rec['paths_s'] = clock() - t0
+            else:
+                t0 = clock()
+                low = C[cur_i, cur_j] <= cutoff
+                C[cur_i[low], cur_j[low]] = 0
+                C[cur_j[low], cur_i[low]] = 0
+                rec['filter_s'] = clock() - t0
+                t0 = clock()
+                host_forest = nx.tree.maximum_spanning_tree(nx.Graph(C), algorithm='kruskal')
+                rec['forest_s'] = clock() - t0
+                t0 = clock()
+                for nodes in nx.connected_components(host_forest):
+                    tree = host_forest.subgraph(nodes)
+                    ends = [v for v, d in tree.degree() if d == 1]
+                    path = nx.shortest_path(tree, ends[0], ends[1])
+                    paths.append((path, sum(end_len[m] for v in path for m in members[v])))
+                rec['paths_s'] = clock() - t0
             paths.sort(key=lambda p: -p[1])
-            rec['paths_s'] = clock() - t0
             t0 = clock()
             index_map = np.full(shape, -1, np.int32)
             new_members = []
@@ -153,25 +187,30 @@ def device_run(case, cutoff=1.0, profile=True):
             pairs = np.arange(2 * len(paths), dtype=np.int32).reshape(-1, 2)[:, ::-1].copy()
             fresh = True
             rec['new_shape'] = 2 * len(paths)
-            rec['events_ms'] = {k: _lib.profile_get(k)[0] for k in KERNELS + COPIES}
+            rec['events_ms'] = {k: _lib.profile_get(k)[0] for k in kernels + COPIES}
             rounds.append(rec)
         stats = eng.stats()
+        if forest == 'device':
+            stats.update(eng.forest_stats())
         eng.close()
     finally:
         _lib.profile_enable(False)
     total_s = clock() - t_all
     tot = lambda key: round(sum(r.get(key, 0.0) for r in rounds), 6)      # noqa: E731
-    events = {k: round(create_events[k] + sum(r['events_ms'][k] for r in rounds), 3) for k in KERNELS + COPIES}
+    events = {k: round(create_events[k] + sum(r['events_ms'][k] for r in rounds), 3) for k in kernels + COPIES}
     for r in rounds:
         for k, v in list(r.items()):
             if isinstance(v, float):
                 r[k] = round(v, 6)
         r['events_ms'] = {k: round(v, 3) for k, v in r['events_ms'].items()}
-    totals = {'wall_s': round(total_s, 3), 'create_call_s': round(create_s, 6), 'kernels_ms': round(sum(events[k] for k in KERNELS), 3),
+    totals = {'wall_s': round(total_s, 3), 'create_call_s': round(create_s, 6), 'kernels_ms': round(sum(events[k] for k in kernels), 3),
               'copies_ms': round(sum(events[k] for k in COPIES), 3), 'events_ms_by_class': events, 'density_calls_s': tot('density_call_s'),
               'confidence_calls_s': tot('confidence_call_s'), 'aggregate_calls_s': tot('aggregate_call_s'), 'filter_s': tot('filter_s'),
               'forest_s': tot('forest_s'), 'paths_s': tot('paths_s'), 'update_host_s': tot('update_host_s')}
-    parts = {k: totals[k] for k in ('density_calls_s', 'confidence_calls_s', 'aggregate_calls_s', 'filter_s', 'forest_s', 'paths_s', 'update_host_s')}
+    if forest == 'device':
+        totals.update(forest_calls_s=tot('forest_call_s'), tree_ends_s=tot('tree_ends_s'), forest_events_ms=round(sum(events[k] for k in FOREST_KERNELS), 3))
+    parts = {k: totals[k] for k in ('density_calls_s', 'confidence_calls_s', 'aggregate_calls_s', 'filter_s', 'forest_s', 'paths_s', 'update_host_s',
+                                    'forest_calls_s', 'tree_ends_s') if k in totals}
     totals['largest_part'] = max(parts, key=parts.get)
     return {'what': 'one synthetic group through _lib.SortGraph, round loop of tools/sort_bench.py (profiling on: every call also records HIP events)',
             'box': '%s, %d CPUs' % (platform.processor() or platform.machine(), os.cpu_count()), 'contigs': len(case.ctgs), 'shape': shape,
@@ -217,14 +256,62 @@ def reference_run(scripts, case):
             'rest_of_fast_sort_s': round(total_s - sum(spent.values()), 3)}
 
 
+def forest_bench(sizes, repeats, parent, out):
+    """both ways of the forest block on the same groups, interleaved, `repeats` times each (profiling off), then one profiled run of each for the split"""
+    res = {'what': 'tools/sort_bench.py --forest-bench: the round loop of this tool on one synthetic chain group per size, whole-loop wall seconds',
+           'box': '%s, %d CPUs' % (platform.processor() or platform.machine(), os.cpu_count()), 'repeats': repeats, 'sizes': {}}
+    device_run(group(200), forest='device')              # warm-up: library, pool, networkx, both forms of the forest
+    device_run(group(200))
+    for n in sizes:
+        case = group(n)
+        device_run(case, profile=False, forest='device')                       # every shape of the timed runs
+        walls = {'seam_on': [], 'seam_off': []}
+        tours = set()
+        for _ in range(repeats):
+            for name, mode in (('seam_off', 'host'), ('seam_on', 'device')):
+                run = device_run(case, profile=False, forest=mode)
+                walls[name].append(run['totals']['wall_s'])
+                tours.add(tuple((r['shape'], r.get('new_shape')) for r in run['rounds']))
+        assert len(tours) == 1, 'the two ways took different rounds'
+        rec = {'contigs': n, 'shape': 2 * n}
+        for name, w in walls.items():
+            rec[name] = {'wall_s': w, 'median_s': sorted(w)[len(w) // 2], 'spread_s': round(max(w) - min(w), 3)}
+        if parent and str(n) in parent:
+            w = parent[str(n)]
+            rec['parent_commit'] = {'wall_s': w, 'median_s': sorted(w)[len(w) // 2], 'spread_s': round(max(w) - min(w), 3)}
+        for name, mode in (('seam_off_profiled', 'host'), ('seam_on_profiled', 'device')):
+            run = device_run(case, forest=mode)
+            rec[name] = {'totals': run['totals'], 'counters': run['counters'],
+                         'rounds': [{k: r[k] for k in ('shape', 'edges', 'confidence_call_s', 'filter_s', 'forest_s', 'forest_call_s', 'tree_ends_s', 'paths_s',
+                                                      'removed') if k in r} | {'forest_events_ms': round(sum(r['events_ms'].get(k, 0.0) for k in FOREST_KERNELS), 3),
+                                                                              'confidence_copy_ms': r['events_ms']['sort_confidence_copy']}
+                                    for r in run['rounds']]}
+        res['sizes'][str(n)] = rec
+        print(json.dumps({k: v for k, v in rec.items() if not k.endswith('_profiled')}), flush=True)
+    with open(out, 'w') as f:
+        json.dump(res, f, indent=1)
+        f.write('\n')
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--forest-bench', action='store_true', help='time the forest block on the host and on the device (profiles/sort_forest_bench.json)')
+    ap.add_argument('--sizes', default='3000,10000')
+    ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--parent', help='JSON {contigs: [wall seconds]} of the parent commit, measured in the same session')
     ap.add_argument('--contigs', type=int, default=3000)
     ap.add_argument('--prefix', type=int, default=600, help='contigs of the prefix the reference is timed on')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'sort_bench.json'))
     ap.add_argument('--reference', default=os.environ.get('HAPHIC_REFERENCE'), help="HapHiC's scripts/ directory: time its fast_sort too")
     ap.add_argument('--reference-only', action='store_true', help='no GPU: the reference record alone (the other records of --out are kept)')
     args = ap.parse_args()
+    if args.forest_bench:
+        parent = None
+        if args.parent:
+            with open(args.parent) as f:
+                parent = json.load(f)
+        out = args.out if args.out != os.path.join(ROOT, 'profiles', 'sort_bench.json') else os.path.join(ROOT, 'profiles', 'sort_forest_bench.json')
+        return forest_bench([int(x) for x in args.sizes.split(',')], args.repeats, parent, out)
     res = {}
     for p in (args.out, os.path.join(ROOT, 'profiles', 'sort_bench.json')):
         if os.path.exists(p):
