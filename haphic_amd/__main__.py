@@ -10,7 +10,8 @@ matrix and the median behind vmax; `log10` / `none`: the median alone) run on th
 `python -m haphic_amd reassign <arguments of "haphic reassign">` wraps HapHiC_reassign.py: parse_link_dict (the per-group link sums) and
 split_clm_file (paired_links.clm split into split_clms/<group>.clm, haphic_amd/reassign.py) run on the device (haphic_amd.patch.patch_reassign),
 and so do the rescue and reassignment rounds (run_reassignment :266-427) and the group-pair sums of the agglomerative step (:489-560) between them
-(patch_reassign(R, rounds=True)); run() :752-916 is the reference's, called as its main() :919-924 calls it.
+(patch_reassign(R, rounds=True)); the front of run() — parse_fasta, parse_pickle and the preparation of parse_link_dict — stays on the device as well
+(fasta=True, pickle=True, resident=True); run() :752-916 is the reference's, called as its main() :919-924 calls it.
 `python -m haphic_amd sort <arguments of "haphic sort">` wraps HapHiC_sort.py: the dense work of fast sorting (link matrix, density graph, confidence
 graph and the link re-aggregation of every round, haphic_amd/sort.py) runs on the device (haphic_amd.patch.patch_sort), and so does the forest block of every round (:567-595: filter, maximum spanning forest, the position of every node
 along its path; patch_sort(S, forest=True)), from which the host builds the small networkx graph that settles the order and direction of the paths;
@@ -49,6 +50,18 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              True / None values, 2^63 ...), refers to a memo slot that holds no name, writes a key twice, ends early, has bytes
                              after STOP or frames that do not tile it, mixes floats with integers beyond 2^53, or is larger than half of the
                              device's memory
+  --keep-reference-fasta     reassign only: leave parse_fasta (HapHiC_cluster.py:87-113) to the reference's per-line loop, which joins every sequence
+                             into a Python string and counts its RE sites one contig after the other.  Without the flag the file is parsed and the RE
+                             sites of all contigs are counted on the device (csrc/hhx_fasta.hip, csrc/hhx_resites.hip) and fa_dict is a plain dict
+                             whose rows hold length and RE sites; a row copies its sequence from the device only if something reads it (run() never
+                             does).  The reference's function still takes a file with a byte >= 0x80, with a sequence line before the first header,
+                             with repeated contig names, or beyond half of the device's memory
+  --keep-host-keys           reassign only: copy the keys of full_links.pkl to the host after reading, as parse_link_dict's host passes over them
+                             need (renumbering, the check for a key that names one contig twice, the total).  Without the flag the table stays open
+                             on the device, those checks are one pass over the keys there and the handle of the rounds is built from them by
+                             device-to-device copies; the keys come to the host only if something turns full_link_dict into a dict.  Tables with a
+                             float or negative value, a key that names one contig twice or totals beyond 2^52 take the host passes as before.  No
+                             effect with --keep-reference-pickle or --keep-reference-rounds
   --keep-reference-statistics  cluster only: leave output_statistics :2279-2478 (the *_statistics.txt files and statistics.pdf of every inflation) to the
                              reference's per-contig loop over ctg_group_link_dict, which is rebuilt as Python dicts once per inflation.  Without the
                              flag a one-rank job takes the per-contig numbers of all inflations from one device call on the frozen full_link_dict
@@ -148,6 +161,8 @@ def main(argv=None):
     keep_dense = bool(_take(argv, '--keep-reference-dense', False))
     keep_rounds = bool(_take(argv, '--keep-reference-rounds', False))
     keep_pickle = bool(_take(argv, '--keep-reference-pickle', False))
+    keep_fasta = bool(_take(argv, '--keep-reference-fasta', False))
+    keep_host_keys = bool(_take(argv, '--keep-host-keys', False))
     keep_build = bool(_take(argv, '--keep-reference-build', False))
     keep_verdict = bool(_take(argv, '--keep-reference-verdict', False))
     keep_heads = bool(_take(argv, '--keep-reference-heads', False))
@@ -177,7 +192,8 @@ def main(argv=None):
         return 0
     if command == 'reassign':
         import HapHiC_reassign as R                                 # needs pysam / sklearn, as the reference does
-        patch.patch_reassign(R, rounds=not keep_rounds, pickle=not keep_pickle)
+        patch.patch_reassign(R, rounds=not keep_rounds, pickle=not keep_pickle, resident=not (keep_pickle or keep_rounds or keep_host_keys),
+                             fasta=not keep_fasta)
         sys.argv = ['haphic reassign'] + argv
         R.run(R.parse_arguments(), 'HapHiC_reassign.log')           # == HapHiC_reassign.main() :919-924
         return 0

@@ -156,6 +156,7 @@ SIGNATURES = {
                                      C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]),
     'hhx_reassign_pair_sums': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'hhx_reassign_destroy': (C.c_int, [C.c_void_p]),
+    'hhx_reassign_create_from_pickle': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int), c_vpp]),
     'hhx_group_stats': (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_ingest_link_matrix': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, c_i32p, c_vpp]),
@@ -238,6 +239,8 @@ SIGNATURES = {
     'hhx_fasta_sequences': (C.c_int, [C.c_void_p, C.c_void_p]),
     'hhx_fasta_emit': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                  c_i64p]),
+    'hhx_fasta_re_counts': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_fasta_fetch': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'hhx_fasta_close': (C.c_int, [C.c_void_p]),
     'hhx_dmat_from_host': (C.c_int, [C.c_int32, C.c_void_p, c_vpp]),
     'hhx_dmat_from_csr': (C.c_int, [C.c_void_p, c_vpp]),
@@ -1178,6 +1181,9 @@ class Reassign:
     class Unsupported(RuntimeError):
         pass
 
+    REFUSALS = []                       # (flags, hhx_last_error()) of every table from_pickle handed back in this process
+    REFUSED_SELF_KEY, REFUSED_FLOAT, REFUSED_NEGATIVE, REFUSED_TOTAL, REFUSED_KEYS = 1, 2, 4, 8, 16    # HHX_REFUSED_*
+
     def __init__(self, frag_i, frag_j, links, n_ctg, group, n_groups):
         fi, fj = np.ascontiguousarray(frag_i, np.int32), np.ascontiguousarray(frag_j, np.int32)
         lk, grp = np.ascontiguousarray(links, np.int64), np.ascontiguousarray(group, np.int32)
@@ -1188,6 +1194,26 @@ class Reassign:
         self.launches = 0               # launch pairs of the last round
         self.h = C.c_void_p()
         self._check(load().hhx_reassign_create(fi.size, ptr(fi), ptr(fj), ptr(lk), self.n_ctg, ptr(grp), self.n_groups, C.byref(self.h)))
+
+    @classmethod
+    def from_pickle(cls, link_pickle, n_ctg, group, n_groups):
+        """the handle from the keys of an open LinkPickle where they lie in HBM (hhx_reassign_create_from_pickle): ids = the pickle's name ids,
+        n_ctg >= its name count.  -> a Reassign, or None when the pass over the keys finds what the host path has to answer (a key naming one contig
+        twice, a float or negative value, totals reaching 2^52, 2^31 keys); the reason goes to REFUSALS.  Unsupported: the cells of n_ctg x n_groups
+        beyond half of the device's memory, as for Reassign(...)"""
+        grp = np.ascontiguousarray(group, np.int32)
+        if grp.size != int(n_ctg) or int(n_ctg) < link_pickle.n_names:
+            raise ValueError('Reassign.from_pickle: {} groups for {} contigs, {} names in the table'.format(grp.size, n_ctg, link_pickle.n_names))
+        self = cls.__new__(cls)
+        self.n_ctg, self.n_groups = int(n_ctg), int(n_groups)
+        self.rounds = self.launches = 0
+        self.h = C.c_void_p()
+        refused = C.c_int(0)
+        self._check(load().hhx_reassign_create_from_pickle(link_pickle.h, self.n_ctg, ptr(grp), self.n_groups, C.byref(refused), C.byref(self.h)))
+        if refused.value:
+            cls.REFUSALS.append((refused.value, load().hhx_last_error().decode('utf-8', 'replace')))
+            return None
+        return self
 
     def _check(self, rc):
         if rc == GROUP_STATS_UNSUPPORTED:
@@ -1286,6 +1312,25 @@ class Fasta:
     def re_counts(self, sites):
         """occurrences of the (N-expanded, bytes) sites per contig, int64 (count_RE_sites :75-84)"""
         return count_re_sites(self.sequences(), self.seq_off, self.seq_len, sites)
+
+    def re_counts_device(self, sites, seg_off=None, seg_len=None):
+        """re_counts on the sequences where they lie in HBM (hhx_fasta_re_counts): no sequence byte is copied.  Segments in the handle's sequence
+        coordinates; by default the whole contigs"""
+        off = np.ascontiguousarray(self.seq_off if seg_off is None else seg_off, np.int64)
+        ln = np.ascontiguousarray(self.seq_len if seg_len is None else seg_len, np.int64)
+        if off.shape != ln.shape or off.ndim != 1:
+            raise ValueError('Fasta.re_counts_device: {} offsets, {} lengths'.format(off.shape, ln.shape))
+        pats = np.frombuffer(b''.join(sites), np.uint8) if sites else np.zeros(1, np.uint8)
+        plen = np.array([len(x) for x in sites], np.int32) if sites else np.zeros(1, np.int32)
+        out = np.zeros(max(off.size, 1), np.int64)
+        check(load().hhx_fasta_re_counts(self.h, off.size, ptr(off), ptr(ln), len(sites), ptr(pats), ptr(plen), ptr(out)))
+        return out[:off.size]
+
+    def fetch(self, off, len):
+        """bytes [off, off + len) of the resident sequences (hhx_fasta_fetch); a range outside them raises"""
+        out = np.zeros(max(min(int(len), self.n_seq_bytes), 1), np.uint8)        # (a longer range is refused before a byte is written)
+        check(load().hhx_fasta_fetch(self.h, int(off), int(len), ptr(out)))
+        return out[:max(int(len), 0)].tobytes()
 
     def emit(self, path, rec_names, piece_off, piece_ctg, piece_rev, Ns, max_width):
         """writes the records (rec_names: list of str; record r: pieces [piece_off[r], piece_off[r + 1]) = (contig id, reversed?)) as a FASTA file

@@ -234,3 +234,67 @@ class FastaTable(dict):
 for _name in ('__getitem__', '__setitem__', '__delitem__', '__reversed__', 'keys', 'values', 'items', 'get', 'pop', 'popitem', 'setdefault', 'update',
               'clear', '__eq__', '__ne__', '__repr__', '__or__', '__ror__', '__ior__'):
     setattr(FastaTable, _name, _thawing(_name))
+
+
+# ------------------------------------------------------------------ fa_dict rows of `haphic reassign` (haphic_amd/reassign.py bind_fasta)
+class FastaRow(list):
+    """One value of fa_dict (parse_fasta, HapHiC_cluster.py:87-113): [sequence, length, RE sites + 1] whose sequence stays in the memory of the
+    device until somebody looks at it.  row[1], row[2], len(row) and assignments to single elements (row[0] = None included) never fetch; whatever
+    observes element 0 — index 0 or -3, a slice that covers it, iteration and unpacking, comparison, repr, copy, pickling, sort, reverse,
+    concatenation — and every change of the list's shape fetches it first (fetch(key) -> str), after which the row is the reference's list.  A copy or
+    an unpickled row is a plain list."""
+
+    __slots__ = ('_fetch', '_key')
+
+    def __init__(self, fetch, key, length, re_sites):
+        list.__init__(self, (None, length, re_sites))
+        self._fetch, self._key = fetch, key
+
+    def _load(self):
+        fetch = self._fetch
+        if fetch is not None:
+            list.__setitem__(self, 0, fetch(self._key))
+            self._fetch = self._key = None
+
+    def __getitem__(self, index):
+        if self._fetch is not None and (0 in range(3)[index] if isinstance(index, slice) else index in (0, -3)):
+            self._load()
+        return list.__getitem__(self, index)
+
+    def __setitem__(self, index, value):
+        if self._fetch is not None:
+            if isinstance(index, slice):
+                self._load()
+            elif index in (0, -3):
+                self._fetch = self._key = None                  # replaced unseen
+        list.__setitem__(self, index, value)
+
+    def __copy__(self):
+        self._load()
+        return list(self)
+
+    copy = __copy__
+
+    def __reduce_ex__(self, protocol):
+        self._load()
+        return list, (), None, list.__iter__(self)
+
+    __reduce__ = lambda self: self.__reduce_ex__(2)             # noqa: E731
+
+
+def _loading(name):
+    def method(self, *args, **kwargs):
+        self._load()
+        for other in args:                                       # list's own methods read the other operand's slots in C
+            if type(other) is FastaRow:
+                other._load()
+        return getattr(list, name)(self, *args, **kwargs)
+    method.__name__ = name
+    return method
+
+
+for _name in ('__iter__', '__reversed__', '__contains__', '__eq__', '__ne__', '__lt__', '__le__', '__gt__', '__ge__', '__repr__', '__add__', '__mul__',
+              '__rmul__', '__iadd__', '__imul__', '__delitem__', 'index', 'count', 'sort', 'reverse', 'append', 'extend', 'insert', 'pop', 'remove',
+              'clear'):
+    setattr(FastaRow, _name, _loading(_name))
+FastaRow.__radd__ = lambda self, other: other + list(self)      # plain list + row reads the row's slots in C otherwise

@@ -35,6 +35,7 @@
 #include <memory>
 
 #include "hhx_filesink.h"
+#include "hhx_internal.h"
 #include "hhx_textscan.h"
 
 using namespace hhx;
@@ -505,6 +506,24 @@ extern "C" int hhx_fasta_sequences(hhx_fasta *f, uint8_t *out) {
     if (!f) return fail("hhx_fasta_sequences: null handle");
     if (f->n_seq && !out) return fail("hhx_fasta_sequences: null pointer");
     if (f->n_seq) HHX_HIP(hipMemcpyAsync(out, f->bases(), (size_t)f->n_seq, hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+// count_RE_sites :75-84 on the sequences where they lie: behind the n_seq bytes stand SEQ_PAD readable ones, which the matcher's core asks for
+extern "C" int hhx_fasta_re_counts(hhx_fasta *f, int64_t n_seg, const int64_t *seg_off, const int64_t *seg_len, int32_t n_sites, const uint8_t *sites,
+                                   const int32_t *site_len, int64_t *counts_host) {
+    if (!f) return fail("hhx_fasta_re_counts: null handle");
+    return hhx_count_re_sites_device("hhx_fasta_re_counts", f->bases(), f->n_seq, n_seg, seg_off, seg_len, n_sites, sites, site_len, counts_host);
+}
+
+extern "C" int hhx_fasta_fetch(hhx_fasta *f, int64_t off, int64_t len, uint8_t *out_host) {
+    if (!f) return fail("hhx_fasta_fetch: null handle");
+    if (off < 0 || len < 0 || len > f->n_seq || off > f->n_seq - len)
+        return fail("hhx_fasta_fetch: bytes [%lld, +%lld) of %lld", (long long)off, (long long)len, (long long)f->n_seq);
+    if (len == 0) return 0;
+    if (!out_host) return fail("hhx_fasta_fetch: null pointer");
+    HHX_HIP(hipMemcpyAsync(out_host, f->bases() + off, (size_t)len, hipMemcpyDeviceToHost, g_stream));
     HHX_HIP(hipStreamSynchronize(g_stream));
     return 0;
 }

@@ -22,6 +22,17 @@ void hhx_expand_last_demand(i64 *out, i64 *cand);
 // how the dense block of all rows is stored — 1: the square, 2: the upper block triangle, 0: neither fits
 int hhx_dense_layout(i32 n_rows, i32 n_cols, i64 nnz_b);
 
+// ---- hhx_resites.hip
+// hhx_count_re_sites on sequence bytes that lie in device memory already (seq_len of them and one readable byte behind): segments and sites from the
+// host, counts back to it; `who` names the entry in the error text
+int hhx_count_re_sites_device(const char *who, const unsigned char *seq, i64 seq_len, i64 n_seg, const i64 *seg_off, const i64 *seg_len, i32 n_sites,
+                              const uint8_t *sites, const i32 *site_len, i64 *counts_host);
+
+// ---- hhx_reassign.hip
+// hhx_reassign_create with the three key arrays in device memory (copied device to device)
+int hhx_reassign_create_device(const char *who, i64 n_keys, const i32 *frag_i, const i32 *frag_j, const i64 *links, i32 n_ctg, const i32 *group_host,
+                               i32 n_groups, hhx_reassign **out);
+
 // ---- hhx_ingest.hip
 // the dict-ordered tables (made on first use)
 int hhx_ingest_ordered_full_device(hhx_ingest *h, const i32 **fi, const i32 **fj);

@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "hhx_internal.h"
 #include "hhx_sort.h"
 #include "hhx_textscan.h"
 
@@ -632,6 +633,82 @@ extern "C" int hhx_pickle_fetch(hhx_pickle *p, int32_t *name_i, int32_t *name_j,
 extern "C" int hhx_pickle_free(hhx_pickle *p) {
     delete p;
     return 0;
+}
+
+// ------------------------------------------------------------------ the handle of the reassignment rounds from the open table
+// What parse_link_dict's mirror (haphic_amd/reassign.py) decides on host arrays before it builds a handle — a key that names one contig twice, totals
+// that leave the exact range of float64 — decided here in one pass over id_i / id_j / val / isf where they lie.  The total cannot wrap: the low and
+// the high 32 bits of the non-negative integer values are added apart, each sum below 2^63 for fewer than 2^31 keys, and put together on the host.
+namespace {
+
+constexpr int RC_T = 256;
+constexpr unsigned RC_GRID = 256 * 8;         // eight workgroups a CU keep the three streams in flight (hhx_tune "reassign_check_grid": fewer)
+enum { RC_LO = 0, RC_HI, RC_FLAGS, RC_WORDS };
+
+__global__ __launch_bounds__(RC_T) void k_reassign_check(const i32 *__restrict__ id_i, const i32 *__restrict__ id_j, const i64 *__restrict__ val,
+                                                         const unsigned char *__restrict__ isf, i64 n, unsigned long long *__restrict__ out) {
+    __shared__ i64 s_lo[RC_T / HHX_WAVE], s_hi[RC_T / HHX_WAVE];
+    __shared__ i32 s_fl[RC_T / HHX_WAVE];
+    i64 lo = 0, hi = 0;
+    i32 fl = 0;
+    for (i64 k = (i64)blockIdx.x * RC_T + threadIdx.x; k < n; k += (i64)gridDim.x * RC_T) {
+        const i64 v = val[k];
+        if (isf[k]) fl |= HHX_REFUSED_FLOAT;                     // v holds the bits of a double
+        else if (v < 0) fl |= HHX_REFUSED_NEGATIVE;
+        else { lo += v & 0xffffffffll; hi += v >> 32; }
+        if (id_i[k] == id_j[k]) fl |= HHX_REFUSED_SELF_KEY;
+    }
+    lo = wave_sum_i64(lo);
+    hi = wave_sum_i64(hi);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) fl |= __shfl_down(fl, o, HHX_WAVE);
+    if (lane_id() == 0) { s_lo[threadIdx.x / HHX_WAVE] = lo; s_hi[threadIdx.x / HHX_WAVE] = hi; s_fl[threadIdx.x / HHX_WAVE] = fl; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < RC_T / HHX_WAVE; ++w) { lo += s_lo[w]; hi += s_hi[w]; fl |= s_fl[w]; }
+        if (lo) atomicAdd(&out[RC_LO], (unsigned long long)lo);
+        if (hi) atomicAdd(&out[RC_HI], (unsigned long long)hi);
+        if (fl) atomicOr(&out[RC_FLAGS], (unsigned long long)fl);
+    }
+}
+
+}  // namespace
+
+extern "C" int hhx_reassign_create_from_pickle(hhx_pickle *p, int32_t n_ctg, const int32_t *group_host, int32_t n_groups, int *refused, hhx_reassign **out) {
+    if (!p) return fail("hhx_reassign_create_from_pickle: null handle");
+    if (!refused || !out) return fail("hhx_reassign_create_from_pickle: null pointer");
+    *refused = 0;
+    *out = nullptr;
+    if (n_ctg < p->n_names) return fail("hhx_reassign_create_from_pickle: %d contigs, the table names %d", n_ctg, p->n_names);
+    const i64 n = p->n_keys;
+    if (n >= (i64)1 << 31) {                                     // the pass adds 32-bit halves in 64-bit words
+        fail("reassign: not the device's table: 2^31 keys and more;");
+        *refused = HHX_REFUSED_KEYS;
+        return 0;
+    }
+    unsigned long long acc[RC_WORDS] = {0, 0, 0};
+    if (n) {
+        DevBuf<unsigned long long> d_acc;
+        if (d_acc.alloc(RC_WORDS)) return 1;
+        HHX_HIP(hipMemsetAsync(d_acc.p, 0, sizeof acc, g_stream));
+        const unsigned grid = std::min(grid_for(n, RC_T), (unsigned)std::min<i64>(RC_GRID, std::max<i64>(1, tune_get("reassign_check_grid", RC_GRID))));
+        { KTimer kt("reassign_check");
+        k_reassign_check<<<grid, RC_T, 0, g_stream>>>(p->id_i.p, p->id_j.p, p->val.p, p->isf.p, n, d_acc.p); }
+        HHX_LAUNCH_CHECK();
+        HHX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, g_stream));
+        HHX_HIP(hipStreamSynchronize(g_stream));
+    }
+    int why = (int)acc[RC_FLAGS];
+    const unsigned __int128 total = ((unsigned __int128)acc[RC_HI] << 32) + acc[RC_LO];
+    if (total >= (unsigned __int128)1 << 52) why |= HHX_REFUSED_TOTAL;            // 2 * total reaches 2^53
+    if (why) {
+        fail("reassign: not the device's table:%s%s%s%s", why & HHX_REFUSED_SELF_KEY ? " a key names one contig twice;" : "",
+             why & HHX_REFUSED_FLOAT ? " a value is a float;" : "", why & HHX_REFUSED_NEGATIVE ? " a value is negative;" : "",
+             why & HHX_REFUSED_TOTAL ? " twice the total of the values reaches 2^53;" : "");
+        *refused = why;
+        return 0;
+    }
+    return hhx_reassign_create_device("hhx_reassign_create_from_pickle", n, p->id_i.p, p->id_j.p, p->val.p, n_ctg, group_host, n_groups, out);
 }
 
 // ------------------------------------------------------------------ one group's H/T links from the open table

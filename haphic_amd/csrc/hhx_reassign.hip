@@ -19,6 +19,7 @@
 #include <memory>
 
 #include "hhx_groupstats.h"
+#include "hhx_internal.h"
 
 namespace {
 
@@ -210,14 +211,17 @@ struct hhx_reassign {
     GsAdjacency adj;
 };
 
-extern "C" int hhx_reassign_create(int64_t n_keys, const int32_t *frag_i, const int32_t *frag_j, const int64_t *links, int32_t n_ctg,
-                                   const int32_t *group_host, int32_t n_groups, hhx_reassign **out) {
-    if (!out) return fail("hhx_reassign_create: null pointer");
+namespace {
+
+// keys: where frag_i / frag_j / links lie (hipMemcpyHostToDevice or hipMemcpyDeviceToDevice)
+int ra_create(const char *who, hipMemcpyKind keys, int64_t n_keys, const int32_t *frag_i, const int32_t *frag_j, const int64_t *links, int32_t n_ctg,
+              const int32_t *group_host, int32_t n_groups, hhx_reassign **out) {
+    if (!out) return fail("%s: null pointer", who);
     *out = nullptr;
-    if (n_keys < 0 || n_ctg < 0 || n_groups < 0) return fail("hhx_reassign_create: bad arguments");
-    if ((n_ctg && !group_host) || (n_keys && (!frag_i || !frag_j || !links))) return fail("hhx_reassign_create: null pointer");
+    if (n_keys < 0 || n_ctg < 0 || n_groups < 0) return fail("%s: bad arguments", who);
+    if ((n_ctg && !group_host) || (n_keys && (!frag_i || !frag_j || !links))) return fail("%s: null pointer", who);
     for (i32 c = 0; c < n_ctg; ++c)
-        if (group_host[c] < -1 || group_host[c] >= n_groups) return fail("hhx_reassign_create: group id %d of contig %d (n_groups %d)", group_host[c], c, n_groups);
+        if (group_host[c] < -1 || group_host[c] >= n_groups) return fail("%s: group id %d of contig %d (n_groups %d)", who, group_host[c], c, n_groups);
     const size_t cells = (size_t)n_ctg * (size_t)n_groups;
     size_t free_b = 0, total_b = 0;
     HHX_HIP(hipMemGetInfo(&free_b, &total_b));
@@ -229,9 +233,9 @@ extern "C" int hhx_reassign_create(int64_t n_keys, const int32_t *frag_i, const 
         h->dismissed.alloc((size_t)n_groups + 1) || h->state.alloc(ST_WORDS) || h->sum.alloc(cells + 1) || h->stamp.alloc(cells + 1) ||
         h->verdict.alloc(RA_WINDOW_MAX) || h->target.alloc(RA_WINDOW_MAX)) return 1;
     if (n_keys) {
-        HHX_HIP(hipMemcpyAsync(h->fi.p, frag_i, sizeof(i32) * (size_t)n_keys, hipMemcpyHostToDevice, g_stream));
-        HHX_HIP(hipMemcpyAsync(h->fj.p, frag_j, sizeof(i32) * (size_t)n_keys, hipMemcpyHostToDevice, g_stream));
-        HHX_HIP(hipMemcpyAsync(h->links.p, links, sizeof(i64) * (size_t)n_keys, hipMemcpyHostToDevice, g_stream));
+        HHX_HIP(hipMemcpyAsync(h->fi.p, frag_i, sizeof(i32) * (size_t)n_keys, keys, g_stream));
+        HHX_HIP(hipMemcpyAsync(h->fj.p, frag_j, sizeof(i32) * (size_t)n_keys, keys, g_stream));
+        HHX_HIP(hipMemcpyAsync(h->links.p, links, sizeof(i64) * (size_t)n_keys, keys, g_stream));
     }
     if (n_ctg) HHX_HIP(hipMemcpyAsync(h->group.p, group_host, sizeof(i32) * (size_t)n_ctg, hipMemcpyHostToDevice, g_stream));
     HHX_HIP(hipMemsetAsync(h->state.p, 0, sizeof(i64) * ST_WORDS, g_stream));
@@ -240,12 +244,24 @@ extern "C" int hhx_reassign_create(int64_t n_keys, const int32_t *frag_i, const 
     GsSource src{};
     src.n = n_keys;
     src.fi = h->fi.p; src.fj = h->fj.p; src.links = h->links.p;
-    HHX_TRY(gs_build_adjacency("hhx_reassign_create", src, n_ctg, h->adj));          // checks every contig id, so that no kernel below indexes out of bounds
+    HHX_TRY(gs_build_adjacency(who, src, n_ctg, h->adj));                           // checks every contig id, so that no kernel below indexes out of bounds
     h->adj.ps.release();                                                            // the positions live on as stamps
     if (cells) HHX_TRY(launch_group_link_sums(n_keys, h->fi.p, h->fj.p, h->links.p, h->group.p, n_groups, h->sum.p, h->stamp.p));
     HHX_HIP(hipStreamSynchronize(g_stream));
     *out = h.release();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int hhx_reassign_create(int64_t n_keys, const int32_t *frag_i, const int32_t *frag_j, const int64_t *links, int32_t n_ctg,
+                                   const int32_t *group_host, int32_t n_groups, hhx_reassign **out) {
+    return ra_create("hhx_reassign_create", hipMemcpyHostToDevice, n_keys, frag_i, frag_j, links, n_ctg, group_host, n_groups, out);
+}
+
+int hhx_reassign_create_device(const char *who, i64 n_keys, const i32 *frag_i, const i32 *frag_j, const i64 *links, i32 n_ctg, const i32 *group_host,
+                               i32 n_groups, hhx_reassign **out) {
+    return ra_create(who, hipMemcpyDeviceToDevice, n_keys, frag_i, frag_j, links, n_ctg, group_host, n_groups, out);
 }
 
 extern "C" int hhx_reassign_cells(hhx_reassign *h, int64_t *sums_host, int64_t *first_host) {

@@ -12,7 +12,7 @@
 // scanned, and every segment end point is resolved with one partial-block recount by a wavefront.  Segments may
 // overlap arbitrarily (flank prefix and suffix of the same contig) at no extra cost.
 // Sites WITH a border (e.g. GCGC, AAAA) take the exact sequential greedy scan, one thread per (segment, site).
-#include "hhx_common.h"
+#include "hhx_internal.h"
 
 using namespace hhx;
 
@@ -103,22 +103,28 @@ bool has_border(const unsigned char *p, int len) {
     return false;
 }
 
-}  // namespace
-
-extern "C" int hhx_count_re_sites(const uint8_t *seq_host, i64 seq_len, i64 n_seg, const i64 *seg_off, const i64 *seg_len,
-                                  i32 n_sites, const uint8_t *sites, const i32 *site_len, i64 *counts_host) {
-    if (seq_len < 0 || n_seg < 0 || n_sites < 0 || (n_seg && (!seg_off || !seg_len || !counts_host))) return fail("hhx_count_re_sites: bad argument");
-    if (n_seg == 0) return 0;
-    for (i64 s = 0; s < n_seg; ++s)
-        if (seg_off[s] < 0 || seg_len[s] < 0 || seg_off[s] + seg_len[s] > seq_len) return fail("hhx_count_re_sites: segment %lld out of range", (long long)s);
-    // split the sites: border-free ones grouped by length, the rest to the greedy kernel
+// what both entries check and prepare on the host before anything is allocated: the border-free sites grouped by length, the rest for the greedy kernel
+struct RePlan {
     std::vector<SiteSet> sets;
     std::vector<unsigned char> gpat;
     std::vector<i32> glen;
+};
+
+// 0 with *empty set: nothing to count (n_seg == 0)
+int re_plan(const char *who, i64 seq_len, i64 n_seg, const i64 *seg_off, const i64 *seg_len, i32 n_sites, const uint8_t *sites, const i32 *site_len,
+            const i64 *counts_host, RePlan &P, bool *empty) {
+    *empty = false;
+    if (seq_len < 0 || n_seg < 0 || n_sites < 0 || (n_seg && (!seg_off || !seg_len || !counts_host))) return fail("%s: bad argument", who);
+    if (n_seg == 0) { *empty = true; return 0; }
+    for (i64 s = 0; s < n_seg; ++s)
+        if (seg_off[s] < 0 || seg_len[s] < 0 || seg_len[s] > seq_len || seg_off[s] > seq_len - seg_len[s]) return fail("%s: segment %lld out of range", who, (long long)s);
+    std::vector<SiteSet> &sets = P.sets;
+    std::vector<unsigned char> &gpat = P.gpat;
+    std::vector<i32> &glen = P.glen;
     size_t off = 0;
     for (i32 k = 0; k < n_sites; ++k) {
         const i32 L = site_len[k];
-        if (L <= 0 || L > RS_MAX_LEN) return fail("hhx_count_re_sites: site length %d not in [1, %d]", L, RS_MAX_LEN);
+        if (L <= 0 || L > RS_MAX_LEN) return fail("%s: site length %d not in [1, %d]", who, L, RS_MAX_LEN);
         const unsigned char *p = sites + off;
         off += (size_t)L;
         if (has_border(p, L)) {
@@ -133,10 +139,16 @@ extern "C" int hhx_count_re_sites(const uint8_t *seq_host, i64 seq_len, i64 n_se
         if (!dst) { sets.emplace_back(); dst = &sets.back(); dst->n = 0; dst->len = L; memset(dst->pat, 0, sizeof dst->pat); }
         memcpy(dst->pat[dst->n++], p, (size_t)L);
     }
-    DevBuf<unsigned char> seq;
+    return 0;
+}
+
+// seq: seq_len sequence bytes in device memory with one readable byte behind them
+int re_run(const unsigned char *seq, i64 seq_len, i64 n_seg, const i64 *seg_off, const i64 *seg_len, const RePlan &P, i64 *counts_host) {
+    const std::vector<SiteSet> &sets = P.sets;
+    const std::vector<unsigned char> &gpat = P.gpat;
+    const std::vector<i32> &glen = P.glen;
     DevBuf<i64> d_off, d_len, d_out;
-    if (seq.alloc((size_t)seq_len + 1) || d_off.alloc((size_t)n_seg) || d_len.alloc((size_t)n_seg) || d_out.alloc((size_t)n_seg)) return 1;
-    if (seq_len) HHX_HIP(hipMemcpyAsync(seq.p, seq_host, (size_t)seq_len, hipMemcpyHostToDevice, g_stream));
+    if (d_off.alloc((size_t)n_seg) || d_len.alloc((size_t)n_seg) || d_out.alloc((size_t)n_seg)) return 1;
     HHX_HIP(hipMemcpyAsync(d_off.p, seg_off, sizeof(i64) * (size_t)n_seg, hipMemcpyHostToDevice, g_stream));
     HHX_HIP(hipMemcpyAsync(d_len.p, seg_len, sizeof(i64) * (size_t)n_seg, hipMemcpyHostToDevice, g_stream));
     HHX_HIP(hipMemsetAsync(d_out.p, 0, sizeof(i64) * (size_t)n_seg, g_stream));
@@ -145,11 +157,11 @@ extern "C" int hhx_count_re_sites(const uint8_t *seq_host, i64 seq_len, i64 n_se
         DevBuf<i64> cnt, pre;
         if (cnt.alloc((size_t)n_blocks + 1) || pre.alloc((size_t)n_blocks + 2)) return 1;
         { KTimer kt("re_block_counts");
-        k_block_counts<<<(unsigned)std::min<i64>(n_blocks, 256 * 16), 256, 0, g_stream>>>(seq.p, seq_len, S, n_blocks, cnt.p); }
+        k_block_counts<<<(unsigned)std::min<i64>(n_blocks, 256 * 16), 256, 0, g_stream>>>(seq, seq_len, S, n_blocks, cnt.p); }
         HHX_LAUNCH_CHECK();
         HHX_TRY(exclusive_scan_i64(cnt.p, pre.p, n_blocks, nullptr));
         k_segment_counts<<<(unsigned)std::max<i64>(1, std::min<i64>((2 * n_seg + 3) / 4, 256 * 16)), 256, 0, g_stream>>>(
-            seq.p, seq_len, S, pre.p, n_seg, d_off.p, d_len.p, d_out.p);
+            seq, seq_len, S, pre.p, n_seg, d_off.p, d_len.p, d_out.p);
         HHX_LAUNCH_CHECK();
         HHX_HIP(hipStreamSynchronize(g_stream));                 // cnt / pre die here
     }
@@ -161,11 +173,34 @@ extern "C" int hhx_count_re_sites(const uint8_t *seq_host, i64 seq_len, i64 n_se
         HHX_HIP(hipMemcpyAsync(d_plen.p, glen.data(), sizeof(i32) * glen.size(), hipMemcpyHostToDevice, g_stream));
         const i64 work = n_seg * (i64)glen.size();
         k_greedy_counts<<<(unsigned)std::max<i64>(1, std::min<i64>((work + 255) / 256, 256 * 16)), 256, 0, g_stream>>>(
-            seq.p, n_seg, d_off.p, d_len.p, (int)glen.size(), d_pat.p, d_plen.p, d_out.p);
+            seq, n_seg, d_off.p, d_len.p, (int)glen.size(), d_pat.p, d_plen.p, d_out.p);
         HHX_LAUNCH_CHECK();
         HHX_HIP(hipStreamSynchronize(g_stream));
     }
     HHX_HIP(hipMemcpyAsync(counts_host, d_out.p, sizeof(i64) * (size_t)n_seg, hipMemcpyDeviceToHost, g_stream));
     HHX_HIP(hipStreamSynchronize(g_stream));
     return 0;
+}
+
+}  // namespace
+
+// the core behind hhx_fasta_re_counts: the sequences lie in device memory already
+int hhx_count_re_sites_device(const char *who, const unsigned char *seq, i64 seq_len, i64 n_seg, const i64 *seg_off, const i64 *seg_len, i32 n_sites,
+                              const uint8_t *sites, const i32 *site_len, i64 *counts_host) {
+    RePlan P;
+    bool empty = false;
+    HHX_TRY(re_plan(who, seq_len, n_seg, seg_off, seg_len, n_sites, sites, site_len, counts_host, P, &empty));
+    return empty ? 0 : re_run(seq, seq_len, n_seg, seg_off, seg_len, P, counts_host);
+}
+
+extern "C" int hhx_count_re_sites(const uint8_t *seq_host, i64 seq_len, i64 n_seg, const i64 *seg_off, const i64 *seg_len,
+                                  i32 n_sites, const uint8_t *sites, const i32 *site_len, i64 *counts_host) {
+    RePlan P;
+    bool empty = false;
+    HHX_TRY(re_plan("hhx_count_re_sites", seq_len, n_seg, seg_off, seg_len, n_sites, sites, site_len, counts_host, P, &empty));
+    if (empty) return 0;
+    DevBuf<unsigned char> seq;
+    if (seq.alloc((size_t)seq_len + 1)) return 1;
+    if (seq_len) HHX_HIP(hipMemcpyAsync(seq.p, seq_host, (size_t)seq_len, hipMemcpyHostToDevice, g_stream));
+    return re_run(seq.p, seq_len, n_seg, seg_off, seg_len, P, counts_host);
 }

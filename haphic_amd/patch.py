@@ -162,7 +162,7 @@ def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics
     return saved
 
 
-def patch_reassign(R, rounds=False, engine=None, pickle=False, pickle_engine=None):
+def patch_reassign(R, rounds=False, engine=None, pickle=False, pickle_engine=None, resident=False, fasta=False, fasta_engine=None):
     """R: the imported HapHiC_reassign module.  f3: parse_link_dict :217-263 (the per-group link sums behind reassign's
     link densities) on the device for integer link counts; float / normalised links go to the original function.
     split_clm_file :581-622 (paired_links.clm routed line by line to split_clms/<group>.clm) goes through the device too
@@ -172,11 +172,15 @@ def patch_reassign(R, rounds=False, engine=None, pickle=False, pickle_engine=Non
     _lib.Reassign (the tests' numpy engine), with which the three mirrors run without a GPU.  pickle=True: parse_pickle :38-50 is re-bound too
     (reassign.bind_pickle): full_links.pkl is read into arrays on the device and full_link_dict is a frozen containers.LinkTable, which the mirrors
     above consume without thawing; a file the reader does not answer goes through pickle.load.  pickle_engine: a stand-in for
-    _lib.read_link_pickle (the tests' host reader).  Returns {name: original}."""
+    _lib.read_link_pickle (the tests' host reader).  resident=True (with pickle=True): the table stays open on the device and its keys come to
+    the host only when somebody asks for the arrays; with rounds=True parse_link_dict builds its handle from it there (reassign.bind_pickle,
+    reassign.bind_rounds); pickle_engine is then a stand-in for _lib.LinkPickle.open.  fasta=True: parse_fasta (HapHiC_cluster.py:87-113, imported
+    :23) is re-bound too (reassign.bind_fasta): the file is parsed and its RE sites counted on the device, fa_dict is a plain dict of
+    containers.FastaRow whose sequences stay there; fasta_engine: a stand-in for _lib.Fasta.  Returns {name: original}."""
     from . import reassign
     if not rounds:
         engine = None
-    if engine is None or (pickle and pickle_engine is None):
+    if engine is None or (pickle and pickle_engine is None) or (fasta and fasta_engine is None):
         from . import _lib
         _lib.load()
     original = R.parse_link_dict
@@ -194,7 +198,9 @@ def patch_reassign(R, rounds=False, engine=None, pickle=False, pickle_engine=Non
     R.split_clm_file = split_clm_file
     saved = {'parse_link_dict': original, 'split_clm_file': original_split}
     if pickle:
-        mirrors['parse_pickle'] = reassign.bind_pickle(R, pickle_engine)
+        mirrors['parse_pickle'] = reassign.bind_pickle(R, pickle_engine, resident) if resident else reassign.bind_pickle(R, pickle_engine)
+    if fasta:
+        mirrors['parse_fasta'] = reassign.bind_fasta(R, fasta_engine)
     for name, fn in mirrors.items():
         saved.setdefault(name, getattr(R, name))
         setattr(R, name, fn)

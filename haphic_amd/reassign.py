@@ -13,7 +13,12 @@ that are not ours, a whitelist, min_links below 1, the per-contig DEBUG lines, t
 
 The step's first line — parse_pickle :38-50, pickle.load of full_links.pkl — is bound by patch_reassign(R, pickle=True) to bind_pickle() below:
 the file is read into arrays on the device (haphic_amd/csrc/hhx_pickleread.hip) and full_link_dict is a frozen containers.LinkTable, which the
-mirrors above consume without a Python object per key."""
+mirrors above consume without a Python object per key.  With resident=True the table stays open on the device (ResidentSession) and the
+parse_link_dict mirror builds the handle of the rounds from it there (hhx_reassign_create_from_pickle): no key comes to the host unless something
+turns full_link_dict into a dict.
+
+run()'s very first line — parse_fasta, HapHiC_cluster.py:87-113 — is bound by patch_reassign(R, fasta=True) to bind_fasta() below: the file is
+parsed and its RE sites are counted on the device, fa_dict is a plain dict of containers.FastaRow whose sequences stay there (run() never reads one)."""
 import logging
 import os
 from collections import defaultdict
@@ -106,30 +111,125 @@ class PickleSession:
         self.i = self.j = self.value = self.names = None                         # the dict holds them now
 
 
-def bind_pickle(R, engine=None):
+class ResidentSession:
+    """PickleSession over a link pickle that stays open on the device (_lib.LinkPickle or a stand-in with its interface): n_keys, any_float and the
+    names are the handle's own, known without a key; (i, j, value) come to the host when link_arrays is asked for the first time — a thaw, the host
+    passes of parse_link_dict, the thaw of linked_ctg_dict — and `fetches` counts those copies.  Only tables without a float value are kept
+    resident (bind_pickle), so value is int64."""
+
+    resident = True
+
+    def __init__(self, handle, names):
+        self.handle, self.names = handle, names
+        self.any_float = bool(handle.any_float)
+        self.keys = handle.n_keys
+        self.fetches = 0
+        self.thawed = False
+        self._arrays = None
+
+    def n_keys(self, _kind):
+        return self.keys
+
+    def link_arrays(self, _kind):
+        if self._arrays is None:
+            i, j, value, _is_float, _names = self.handle.arrays()
+            self.fetches += 1
+            self._arrays = (i, j, value)
+        return self._arrays + (self.names,)
+
+    def note_thawed(self):
+        self.thawed = True
+        self._arrays = self.names = None                                         # the dict holds them now
+        self.handle.close()
+        self.handle = None
+
+
+def bind_pickle(R, engine=None, resident=False):
     """-> the mirror of parse_pickle :38-50 for the imported HapHiC_reassign module R: the same log line, sorted_ctg_list and RE_site_dict by the
     reference's own expressions, full_link_dict as a frozen containers.LinkTable over the arrays the device read from the file — no dict of every
     key (tens of GB of Python objects at 100k contigs) that parse_link_dict would flatten again.  A file the reader hands back (include/haphic_hip.h
     lists them: another header or protocol, other opcodes, names of 256 bytes and more, integers beyond 64 bits, a truncated file, bytes after
     STOP ...) goes through pickle.load, so that Python's own result or error is what the caller sees.  engine: a stand-in for _lib.read_link_pickle
-    (the tests' host reader)."""
+    (the tests' host reader).
+    resident=True: the table stays open on the device behind a ResidentSession and no key comes to the host until somebody asks for the arrays;
+    the parse_link_dict of bind_rounds builds its handle from it there.  engine is then a stand-in for _lib.LinkPickle.open.  A table with a float
+    value is read as without `resident`: whether it can be served at all is decided on its values."""
     import pickle
-    read = engine if engine is not None else _lib.read_link_pickle
+    read = engine if engine is not None else _lib.LinkPickle.open if resident else _lib.read_link_pickle
+
+    def read_table(pickle_file):
+        """-> a session, or None for a file that goes through pickle.load"""
+        if not resident:
+            arrays = read(pickle_file)
+            return None if arrays is None else PickleSession(*arrays)
+        handle = read(pickle_file)
+        if handle is None:
+            return None
+        if handle.any_float:
+            try:
+                arrays = handle.arrays()
+            finally:
+                handle.close()
+            return None if arrays is None else PickleSession(*arrays)
+        try:
+            return ResidentSession(handle, handle.names())
+        except UnicodeDecodeError:                                               # pickle.load raises its own error for such a name
+            handle.close()
+            return None
 
     def parse_pickle(fa_dict, pickle_file):
         R.logger.info('Parsing input pickle file...')
-        arrays = read(pickle_file)
-        if arrays is None:
+        session = read_table(pickle_file)
+        if session is None:
             with open(pickle_file, 'rb') as f:
                 full_link_dict = pickle.load(f)
         else:
-            full_link_dict = containers.LinkTable(PickleSession(*arrays), 'full')
+            full_link_dict = containers.LinkTable(session, 'full')
         # sort by contig length
         sorted_ctg_list = sorted([(ctg, fa_dict[ctg][1]) for ctg in fa_dict], key=lambda x: x[1], reverse=True)
         RE_site_dict = {ctg: ctg_info[2] for ctg, ctg_info in fa_dict.items()}
         return full_link_dict, sorted_ctg_list, RE_site_dict
 
     return parse_pickle
+
+
+# ------------------------------------------------------------------ parse_fasta (patch_reassign(R, fasta=True))
+def bind_fasta(R, engine=None):
+    """-> the mirror of parse_fasta (HapHiC_cluster.py:87-113, as HapHiC_reassign imports it :23) for the module R.  run() :782-916 never reads a
+    sequence: it asks fa_dict for lengths, RE sites, iteration and `in`.  So the file is parsed on the device (_lib.Fasta), the RE sites of all
+    contigs are counted there in one call on the sequences where they lie (re_counts_device), and fa_dict is a plain dict {name: containers.FastaRow}
+    in file order whose rows fetch their sequence only if somebody looks at it.  The log line is the reference's, through the logger given.  The
+    original function takes the call for a file the reader refuses (a byte >= 0x80, a sequence line before the first header, a text beyond half of
+    the device's memory), for repeated contig names, and for a path that is no file (its own exception is raised).  engine: a stand-in for _lib.Fasta
+    (the tests' numpy engine)."""
+    Engine = engine if engine is not None else _lib.Fasta
+    original = R.parse_fasta
+    try:
+        import inspect
+        default_logger = inspect.signature(original).parameters['logger'].default
+    except (KeyError, TypeError, ValueError):
+        default_logger = R.logger
+
+    def parse_fasta(fasta, RE='GATC', keep_letter_case=False, logger=default_logger):
+        if isinstance(fasta, (str, os.PathLike)) and not os.path.isfile(fasta):
+            return original(fasta, RE, keep_letter_case, logger)
+        try:
+            fa = Engine(fasta, keep_letter_case=keep_letter_case)
+        except Engine.Unsupported:
+            return original(fasta, RE, keep_letter_case, logger)
+        names = fa.names()
+        if len(set(names)) != len(names):                                         # fa_dict[ctg] = list() :99 on a name seen before
+            fa.close()
+            return original(fasta, RE, keep_letter_case, logger)
+        logger.info('Parsing input FASTA file...')
+        counts = fa.re_counts_device(cluster._sites_of(RE)) if names else np.zeros(0, np.int64)
+        off, lengths = np.asarray(fa.seq_off, np.int64).tolist(), np.asarray(fa.seq_len, np.int64).tolist()
+
+        def fetch(k):
+            return fa.fetch(off[k], lengths[k]).decode('ascii')
+        return dict(zip(names, map(containers.FastaRow, [fetch] * len(names), range(len(names)), lengths, (counts + 1).tolist())))    # :110
+
+    return parse_fasta
 
 
 # ------------------------------------------------------------------ the rounds and the agglomerative step (patch_reassign(R, rounds=True))
@@ -206,7 +306,38 @@ def bind_rounds(R, engine=None):
     def todays_parse(link_dict, ctg_group_dict, normalize_by_nlinks):
         return cluster.parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks, _original=original_parse)
 
+    def resident_parse(link_dict, session, ctg_group_dict):
+        """the tables from a link pickle that is still open on the device, without a key on the host: the numbering below is the one _dict_arrays
+        gives (the reader numbers the names in order of first appearance, i before j, key by key).  None: a case of the code below"""
+        names = session.names
+        if any(c not in ctg_group_dict for c in names):
+            return None
+        named = set(names)
+        id_names = list(names) + [c for c in ctg_group_dict if c not in named]    # contigs no key names are visited too
+        groups = {}
+        grp = np.fromiter((-1 if ctg_group_dict[c] == 'ungrouped' else groups.setdefault(ctg_group_dict[c], len(groups)) for c in id_names),
+                          np.int32, len(id_names))
+        group_names = list(groups)
+        if not group_names:
+            return None
+        try:
+            handle = Engine.from_pickle(session.handle, len(id_names), grp, len(group_names))
+        except unsupported as e:                                                   # the cells do not fit: what the code below would meet after its host passes
+            logger.info('parse_link_dict: %s; the reference function takes the call', e)
+            return original_parse(link_dict, ctg_group_dict, False)
+        if handle is None:                                                         # a key naming one contig twice, a negative value, totals beyond 2^52
+            return None
+        job = _Job(handle, link_dict, id_names, group_names)
+        jobs[:] = [job]
+        return RoundTable(dict, job, 'ctg_group_link_dict'), RoundTable(set, job, 'linked_ctg_dict')
+
     def parse_link_dict(link_dict, ctg_group_dict, normalize_by_nlinks=False):
+        session = getattr(link_dict, '_session', None) if cluster._frozen(link_dict, 'full') else None
+        if (not normalize_by_nlinks and getattr(session, 'resident', False) and session.handle is not None and not session.any_float
+                and hasattr(Engine, 'from_pickle')):
+            tables = resident_parse(link_dict, session, ctg_group_dict)           # ahead of integral_links, which asks for the arrays
+            if tables is not None:
+                return tables
         if normalize_by_nlinks or not cluster.integral_links(link_dict):
             return original_parse(link_dict, ctg_group_dict, normalize_by_nlinks)
         names = {}

@@ -83,7 +83,9 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * against the bitmap of the group's names in LDS first (default 1; tables of more than 2^19 names always gather; same arrays;
  * tools/sort_heads_bench.py times both); "heads_grid" = the most workgroups (four wavefronts each, every wavefront one contiguous range of the table)
  * of the passes of hhx_pickle_group_heads, clamped to [1, 1536] (default 1536; fewer: more steps per wavefront; same arrays); "sort_forest_lds" = the largest shape whose hhx_sort_graph_forest runs as one
- * workgroup on LDS arrays, clamped to [0, 2048] (default 2048; 0: always the multi-launch form in HBM; same arrays).  value INT64_MIN: back
+ * workgroup on LDS arrays, clamped to [0, 2048] (default 2048; 0: always the multi-launch form in HBM; same arrays); "reassign_check_grid" = the
+ * most workgroups of the pass over the keys that hhx_reassign_create_from_pickle runs before it builds a handle, clamped to [1, 2048] (default 2048;
+ * fewer: more steps per lane; same answers).  value INT64_MIN: back
  * to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
@@ -660,6 +662,21 @@ int hhx_reassign_round(hhx_reassign *h, int32_t *group_host, int64_t *group_re_h
 int hhx_reassign_pair_sums(hhx_reassign *h, const uint8_t *member_host, const int32_t *group_of_ctg_host, int32_t n_groups, int64_t *sums_host,
                            int64_t *first_host);
 int hhx_reassign_destroy(hhx_reassign *h);
+/* hhx_reassign_create_from_pickle: the handle hhx_reassign_create makes, from the ids and values of an open hhx_pickle (declared below) where they
+ * lie in HBM: device-to-device copies, no key crosses the bus.  The ids are the pickle's name ids; n_ctg >= its name count (the contigs no key names
+ * follow the names; group_host [n_ctg]).  One pass over the keys first decides what the mirror of parse_link_dict decides on host arrays
+ * (haphic_amd/reassign.py): *refused = an OR of the flags below when a key names one contig twice, a value is a float, a value is negative, or twice
+ * the total of the values reaches 2^53 (the low and the high 32 bits of the values are added apart and put together in 128 bits, so the pass's own
+ * sum cannot wrap), or the table holds 2^31 keys and more.  Then *out = NULL, the return value is 0 and hhx_last_error() holds the reason: the
+ * caller takes the host path.  HHX_UNSUPPORTED as for hhx_reassign_create: the cells beyond half of the device's memory.
+ * The pass is grid-stride; hhx_tune "reassign_check_grid" caps its workgroups. */
+#define HHX_REFUSED_SELF_KEY 1
+#define HHX_REFUSED_FLOAT 2
+#define HHX_REFUSED_NEGATIVE 4
+#define HHX_REFUSED_TOTAL 8
+#define HHX_REFUSED_KEYS 16
+struct hhx_pickle;
+int hhx_reassign_create_from_pickle(struct hhx_pickle *p, int32_t n_ctg, const int32_t *group_host, int32_t n_groups, int *refused, hhx_reassign **out);
 
 /* Multi-GPU exchange step (ingest).  The aggregated table of a finalized handle, device
  * SoA in no particular order: key = (i << 29) | j, first-seen global ordinals of the key in
@@ -965,6 +982,13 @@ int hhx_fasta_open_bytes(const uint8_t *text, int64_t n_bytes, int keep_letter_c
 int hhx_fasta_counts(const hhx_fasta *f, int64_t *n_ctg, int64_t *n_seq_bytes, int64_t *n_name_bytes);
 int hhx_fasta_table(const hhx_fasta *f, int64_t *seq_off, int64_t *seq_len, int64_t *name_off, uint8_t *names);
 int hhx_fasta_sequences(hhx_fasta *f, uint8_t *seq_host);
+/* hhx_fasta_re_counts: hhx_count_re_sites (count_RE_sites :75-84) on the sequences the handle holds in HBM — the same matcher, no sequence byte crosses
+ *   the bus.  Segments are in the handle's sequence coordinates (contig k: [seq_off[k], seq_off[k] + seq_len[k])) and checked against its sequence
+ *   bytes; a match never crosses a segment end, so none straddles two contigs.
+ * hhx_fasta_fetch: bytes [off, off + len) of the resident sequences into host memory; a range outside the sequences is refused (return 1). */
+int hhx_fasta_re_counts(hhx_fasta *f, int64_t n_seg, const int64_t *seg_off, const int64_t *seg_len, int32_t n_sites, const uint8_t *sites,
+                        const int32_t *site_len, int64_t *counts_host);
+int hhx_fasta_fetch(hhx_fasta *f, int64_t off, int64_t len, uint8_t *out_host);
 int hhx_fasta_emit(hhx_fasta *f, const char *path, int64_t n_rec, const uint8_t *rec_names, const int64_t *rec_name_off, const int64_t *piece_off,
                    const int32_t *piece_ctg, const uint8_t *piece_rev, int64_t Ns, int64_t max_width, int64_t *n_bytes);
 int hhx_fasta_close(hhx_fasta *f);
