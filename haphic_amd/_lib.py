@@ -283,15 +283,100 @@ def load():
     return _lib
 
 
+HHX_UNSUPPORTED = 2                  # "not served here": the caller takes the reference's path, the handle is untouched
+
+
+def last_error():
+    return load().hhx_last_error().decode('utf-8', 'replace')
+
+
 def check(rc):
     if rc != 0:
-        raise RuntimeError('libhaphic_hip: ' + load().hhx_last_error().decode('utf-8', 'replace'))
+        raise RuntimeError('libhaphic_hip: ' + last_error())
+
+
+def check_served(rc, unsupported=None):
+    """check(rc), except for HHX_UNSUPPORTED: raises unsupported(last_error()), or with no class given returns False (else True)"""
+    if rc == HHX_UNSUPPORTED:
+        if unsupported is None:
+            return False
+        raise unsupported(last_error())
+    check(rc)
+    return True
+
+
+_PY_ERRORS = {'IndexError': IndexError, 'ValueError': ValueError}
+
+
+def check_py(rc):
+    """check(rc) for the calls that fail as the reference's own statement would: a message 'IndexError: ...' / 'ValueError: ...' raises that
+    exception with the text behind the prefix"""
+    if rc:
+        msg = last_error()
+        kind, sep, text = msg.partition(': ')
+        if sep and kind in _PY_ERRORS:
+            raise _PY_ERRORS[kind](text)
+        raise RuntimeError('libhaphic_hip: ' + msg)
+
+
+def new_handle(symbol, *args):
+    """symbol(*args, &out) of the library -> the handle it left in that last parameter"""
+    out = C.c_void_p()
+    check(getattr(load(), symbol)(*args, C.byref(out)))
+    return out
+
+
+class Handle:
+    """One handle of the library: self.h, released once by the symbol the subclass names in _release — by close() (free() and destroy() are the
+    same call under the names older callers use), at the end of a `with` block, or by the finaliser when nobody did."""
+    _release = None
+    _finalise = True
+
+    def __init__(self, handle):
+        self.h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+
+    def close(self):
+        h, self.h = getattr(self, 'h', None), None
+        if h:                           # neither None nor a null pointer
+            getattr(load(), self._release)(h)
+
+    def free(self):
+        return self.close()
+
+    def destroy(self):
+        return self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            if self._finalise:
+                self.close()
+        except Exception:
+            pass
 
 
 def device_count():
     n = C.c_int(0)
     check(load().hhx_device_count(C.byref(n)))
     return n.value
+
+
+def set_device(i):
+    check(load().hhx_set_device(int(i)))
+
+
+def synchronize():
+    check(load().hhx_synchronize())
+
+
+def pool_trim(keep_bytes=None):
+    """the pool's cached blocks back to the driver; keep_bytes: all but that much of them (hhx_pool_trim_keep)"""
+    check(load().hhx_pool_trim() if keep_bytes is None else load().hhx_pool_trim_keep(int(keep_bytes)))
 
 
 def tune(name, value):
@@ -324,11 +409,9 @@ def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-class DeviceCSR:
+class DeviceCSR(Handle):
     """Device-resident CSR(T) == the reference's CSC(M) triple (hhx_csr handle)."""
-
-    def __init__(self, handle):
-        self.h = C.c_void_p(handle) if not isinstance(handle, C.c_void_p) else handle
+    _release = 'hhx_csr_free'
 
     @classmethod
     def from_arrays(cls, indptr, indices, data, n_cols=None):
@@ -341,10 +424,7 @@ class DeviceCSR:
         indices = np.ascontiguousarray(indices, np.int32)
         data = np.ascontiguousarray(data, np.float32)
         n_rows = len(indptr) - 1
-        out = C.c_void_p()
-        check(load().hhx_csr_from_host(n_rows, n_rows if n_cols is None else n_cols, ptr(indptr), ptr(indices),
-                                       ptr(data), C.byref(out)))
-        return cls(out)
+        return cls(new_handle('hhx_csr_from_host', n_rows, n_rows if n_cols is None else n_cols, ptr(indptr), ptr(indices), ptr(data)))
 
     @classmethod
     def from_scipy_csc(cls, m):
@@ -358,10 +438,7 @@ class DeviceCSR:
 
     @classmethod
     def from_device(cls, n_rows, n_cols, nnz, indptr_ptr, indices_ptr, data_ptr):
-        out = C.c_void_p()
-        check(load().hhx_csr_from_device(n_rows, n_cols, nnz, C.c_void_p(indptr_ptr), C.c_void_p(indices_ptr),
-                                         C.c_void_p(data_ptr), C.byref(out)))
-        return cls(out)
+        return cls(new_handle('hhx_csr_from_device', n_rows, n_cols, nnz, C.c_void_p(indptr_ptr), C.c_void_p(indices_ptr), C.c_void_p(data_ptr)))
 
     @property
     def shape3(self):
@@ -393,49 +470,28 @@ class DeviceCSR:
         return a.value or 0, b.value or 0, d.value or 0
 
     def copy(self):
-        out = C.c_void_p()
-        check(load().hhx_csr_copy(self.h, C.byref(out)))
-        return DeviceCSR(out)
+        return DeviceCSR(new_handle('hhx_csr_copy', self.h))
 
     def row_block(self, r0, r1):
-        out = C.c_void_p()
-        check(load().hhx_csr_row_block(self.h, r0, r1, C.byref(out)))
-        return DeviceCSR(out)
-
-    def free(self):
-        if self.h is not None and self.h.value:
-            load().hhx_csr_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        return DeviceCSR(new_handle('hhx_csr_row_block', self.h, r0, r1))
 
 
-class DenseMatrix:
+class DenseMatrix(Handle):
     """Device-resident n x n float32 matrix M of the --dense_matrix mode (hhx_dmat handle; stored transposed and padded, every array in and
     out is M as the reference has it)."""
-
-    def __init__(self, handle):
-        self.h = C.c_void_p(handle) if not isinstance(handle, C.c_void_p) else handle
+    _release = 'hhx_dmat_free'
 
     @classmethod
     def from_numpy(cls, m):
         m = np.ascontiguousarray(m, np.float32)
         if m.ndim != 2 or m.shape[0] != m.shape[1]:
             raise ValueError('the dense mode needs a square matrix, got shape {}'.format(m.shape))
-        out = C.c_void_p()
-        check(load().hhx_dmat_from_host(m.shape[0], ptr(m), C.byref(out)))
-        return cls(out)
+        return cls(new_handle('hhx_dmat_from_host', m.shape[0], ptr(m)))
 
     @classmethod
     def from_csr(cls, t):
         """t: DeviceCSR, CSR(T) == CSC(M); densified on the device"""
-        out = C.c_void_p()
-        check(load().hhx_dmat_from_csr(t.h, C.byref(out)))
-        return cls(out)
+        return cls(new_handle('hhx_dmat_from_csr', t.h))
 
     @property
     def shape(self):
@@ -456,32 +512,15 @@ class DenseMatrix:
         return out
 
     def to_csr(self):
-        out = C.c_void_p()
-        check(load().hhx_dmat_to_csr(self.h, C.byref(out)))
-        return DeviceCSR(out)
+        return DeviceCSR(new_handle('hhx_dmat_to_csr', self.h))
 
     def copy(self):
-        out = C.c_void_p()
-        check(load().hhx_dmat_copy(self.h, C.byref(out)))
-        return DenseMatrix(out)
-
-    def free(self):
-        if self.h is not None and self.h.value:
-            load().hhx_dmat_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        return DenseMatrix(new_handle('hhx_dmat_copy', self.h))
 
 
 def dmat_gemm(a, b):
     """a @ b of two DenseMatrix (float32 in, float32 accumulate, k ascending)"""
-    out = C.c_void_p()
-    check(load().hhx_dmat_gemm(a.h, b.h, C.byref(out)))
-    return DenseMatrix(out)
+    return DenseMatrix(new_handle('hhx_dmat_gemm', a.h, b.h))
 
 
 def dmat_normalize_l1(m):
@@ -490,15 +529,11 @@ def dmat_normalize_l1(m):
 
 
 def dmat_prune(m, pruning):
-    out = C.c_void_p()
-    check(load().hhx_dmat_prune(m.h, float(pruning), C.byref(out)))
-    return DenseMatrix(out)
+    return DenseMatrix(new_handle('hhx_dmat_prune', m.h, float(pruning)))
 
 
 def dmat_power(m, expansion):
-    out = C.c_void_p()
-    check(load().hhx_dmat_power(m.h, int(expansion), C.byref(out)))
-    return DenseMatrix(out)
+    return DenseMatrix(new_handle('hhx_dmat_power', m.h, int(expansion)))
 
 
 def dmat_mcl(pre_expanded, expansion, inflation, max_iter, pruning, done=0):
@@ -521,28 +556,20 @@ def inflate(m, inflation):
 
 
 def prune(m, pruning):
-    out = C.c_void_p()
-    check(load().hhx_prune(m.h, float(pruning), C.byref(out)))
-    return DeviceCSR(out)
+    return DeviceCSR(new_handle('hhx_prune', m.h, float(pruning)))
 
 
 def inflate_prune(c, inflation, pruning):
-    out = C.c_void_p()
-    check(load().hhx_inflate_prune(c.h, float(inflation), float(pruning), C.byref(out)))
-    return DeviceCSR(out)
+    return DeviceCSR(new_handle('hhx_inflate_prune', c.h, float(inflation), float(pruning)))
 
 
 def inflate_prune_keep(c, inflation, pruning):
-    out = C.c_void_p()
-    check(load().hhx_inflate_prune_keep(c.h, float(inflation), float(pruning), C.byref(out)))
-    return DeviceCSR(out)
+    return DeviceCSR(new_handle('hhx_inflate_prune_keep', c.h, float(inflation), float(pruning)))
 
 
 def vstack(blocks):
     arr = (C.c_void_p * len(blocks))(*[b.h.value for b in blocks])
-    out = C.c_void_p()
-    check(load().hhx_csr_vstack(len(blocks), arr, C.byref(out)))
-    return DeviceCSR(out)
+    return DeviceCSR(new_handle('hhx_csr_vstack', len(blocks), arr))
 
 
 def mem_info():
@@ -563,8 +590,9 @@ def pool_cached_bytes():
     return b.value
 
 
-class DenseRows:
+class DenseRows(Handle):
     """hhx_dense: rows [r0, r1) of the pre-expanded matrix M^2 as float32 in HBM — one expansion for a whole inflation sweep"""
+    _release = 'hhx_dense_free'
 
     def __init__(self, links, r0, r1, fx_shift=52, upper_only=False):
         """upper_only: only the blocks (I, J >= I) of the rows are filled (integer arithmetic); the caller mirrors the rest"""
@@ -582,9 +610,7 @@ class DenseRows:
 
     def inflate_prune(self, inflation, pruning):
         """iteration 0 of mcl() (:2037-2042) of these rows at `inflation`"""
-        out = C.c_void_p()
-        check(load().hhx_dense_inflate_prune(self.h, float(inflation), float(pruning), C.byref(out)))
-        return DeviceCSR(out)
+        return DeviceCSR(new_handle('hhx_dense_inflate_prune', self.h, float(inflation), float(pruning)))
 
     MULTI = 8       # inflations per pass of inflate_prune_multi (hhx_expand.hip: MULTI_MAX)
 
@@ -601,16 +627,68 @@ class DenseRows:
             res.extend(DeviceCSR(o) for o in outs)
         return res
 
-    def free(self):
-        if self.h is not None and self.h.value:
-            load().hhx_dense_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+# ---------------------------------------------------------------- the pieces of the multi-rank driver (sharded.py): device addresses as ints
+class ShardBuild(Handle):
+    """hhx_shard: one rank's part of the sharded link-matrix build over `src`, its finalized Ingest"""
+    _release = 'hhx_shard_destroy'
+
+    def __init__(self, src, in_set):
+        in_set = np.ascontiguousarray(in_set, np.uint8)
+        self.n_frag = src.n_frag
+        self.h = new_handle('hhx_shard_create', src.h, ptr(in_set))
+
+    def first(self):
+        """device address of the first positions, int64 [n_frag]"""
+        p = C.c_void_p()
+        check(load().hhx_shard_first(self.h, C.byref(p)))
+        return p.value or 0
+
+    def emit(self, fidx_ptr, bounds):
+        """-> (w0, w1, counts): device addresses of the entries' two int64 words, ordered by owner, and the entries per owner (int64 array)"""
+        b = np.ascontiguousarray(bounds, np.int32)
+        counts = np.zeros(len(b) - 1, np.int64)
+        w0, w1 = C.c_void_p(), C.c_void_p()
+        check(load().hhx_shard_emit(self.h, C.c_void_p(fidx_ptr), len(b), b.ctypes.data_as(c_i32p), C.byref(w0), C.byref(w1),
+                                    counts.ctypes.data_as(c_i64p)))
+        return w0.value or 0, w1.value or 0, counts
+
+
+def rank_first(n, first_ptr, fidx_ptr):
+    """fills fidx (int32 [n]) from the first positions (int64 [n]); -> the number of linked fragments"""
+    nl = C.c_int32(0)
+    check(load().hhx_rank_first(int(n), C.c_void_p(first_ptr), C.c_void_p(fidx_ptr), C.byref(nl)))
+    return nl.value
+
+
+def rows_from_entries(n, w0_ptr, w1_ptr, r0, r1, shape):
+    return DeviceCSR(new_handle('hhx_rows_from_entries', int(n), C.c_void_p(w0_ptr), C.c_void_p(w1_ptr), int(r0), int(r1), int(shape), 1))
+
+
+def rows_from_runs(run_counts, w0_ptr, w1_ptr, r0, r1, shape):
+    """rows_from_entries for entries that lie run after run (run_counts entries each), every run in row order already"""
+    off = np.zeros(len(run_counts) + 1, np.int64)
+    off[1:] = np.cumsum(run_counts)
+    return DeviceCSR(new_handle('hhx_rows_from_runs', len(run_counts), off.ctypes.data_as(c_i64p), C.c_void_p(w0_ptr), C.c_void_p(w1_ptr), int(r0),
+                                int(r1), int(shape), 1))
+
+
+def csr_pack_block(m, buf_ptr, words):
+    check(load().hhx_csr_pack_block(m.h, C.c_void_p(buf_ptr), int(words)))
+
+
+def csr_unpack_blocks(rows, nnzs, packed_ptr, stride, n_cols):
+    rows, nnzs = np.ascontiguousarray(rows, np.int64), np.ascontiguousarray(nnzs, np.int64)
+    return DeviceCSR(new_handle('hhx_csr_unpack_blocks', len(rows), rows.ctypes.data_as(c_i64p), nnzs.ctypes.data_as(c_i64p), C.c_void_p(packed_ptr),
+                                int(stride), int(n_cols)))
+
+
+def transpose_f32(src_ptr, src_ld, dst_ptr, dst_ld, rows, cols):
+    check(load().hhx_transpose_f32(C.c_void_p(src_ptr), int(src_ld), C.c_void_p(dst_ptr), int(dst_ld), int(rows), int(cols)))
+
+
+def copy_rect_f32(src_ptr, src_ld, dst_ptr, dst_ld, rows, cols):
+    check(load().hhx_copy_rect_f32(C.c_void_p(src_ptr), int(src_ld), C.c_void_p(dst_ptr), int(dst_ld), int(rows), int(cols)))
 
 
 def links_integer_ok(links):
@@ -677,9 +755,9 @@ def link_weights(frag_i, frag_j, value, mode, n_frag, per_frag=None, tag=None, p
     return nz.value
 
 
-def names_blob(names):
-    """names -> (uint8 array of the UTF-8 bytes back to back, int64 offsets [len(names) + 1])"""
-    enc = [n.encode() for n in names]
+def names_blob(names, encode=str.encode):
+    """names -> (uint8 array of the UTF-8 bytes back to back, int64 offsets [len(names) + 1]); encode: os.fsencode for paths"""
+    enc = [encode(n) for n in names]
     off = np.zeros(len(enc) + 1, np.int64)
     if enc:
         np.cumsum(np.fromiter(map(len, enc), np.int64, len(enc)), out=off[1:])
@@ -700,14 +778,15 @@ def write_link_pickle(path, i, j, count, names):
     return n_bytes.value
 
 
-PICKLE_NOT_OURS = 2                  # HHX_PICKLE_NOT_OURS
+PICKLE_NOT_OURS = HHX_UNSUPPORTED
 PICKLE_REFUSALS = []                 # hhx_last_error() of every file read_link_pickle handed back in this process
 
 
-class LinkPickle:
+class LinkPickle(Handle):
     """hhx_pickle: full_links.pkl / HT_links.pkl read into arrays that stay in the memory of the device (hhx_pickle_open) until close().
     LinkPickle.open(path) -> the handle, or None for a file the reader does not answer (the reason goes to PICKLE_REFUSALS; the caller runs
     pickle.load).  tests/sort_heads_cases.py holds a host engine with the same interface."""
+    _release = 'hhx_pickle_free'
 
     def __init__(self, h):
         self.h = h
@@ -717,18 +796,11 @@ class LinkPickle:
 
     @classmethod
     def open(cls, path):
-        L = load()
         h = C.c_void_p()
-        rc = L.hhx_pickle_open(os.fsencode(path), C.byref(h))
-        if rc == PICKLE_NOT_OURS:
-            PICKLE_REFUSALS.append(L.hhx_last_error().decode('utf-8', 'replace'))
+        if not check_served(load().hhx_pickle_open(os.fsencode(path), C.byref(h))):
+            PICKLE_REFUSALS.append(last_error())
             return None
-        check(rc)
-        try:
-            return cls(h)
-        except BaseException:
-            L.hhx_pickle_free(h)
-            raise
+        return cls(h)                   # (released by the finaliser if the sizes cannot be read)
 
     def _decode(self, blob, off):
         text, bounds = blob.tobytes(), off.tolist()
@@ -775,17 +847,6 @@ class LinkPickle:
         if n.value:
             check(load().hhx_pickle_group_heads_fetch(self.h, ptr(ei), ptr(ej), ptr(w)))
         return ei, ej, w
-
-    def close(self):
-        if self.h is not None and self.h.value:
-            load().hhx_pickle_free(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def read_link_pickle(path):
@@ -846,15 +907,19 @@ def files_join():
     check(rc)
 
 
-class ByteSink:
-    """hhx_byte_sink: a file fed from device buffers through the library's file-writer thread (alignments.bed, deferred)"""
+class ByteSink(Handle):
+    """hhx_byte_sink: a file fed from device buffers through the library's file-writer thread (alignments.bed, deferred).
+    The one handle whose close() is an action with a result — it queues the file's close, returns the bytes handed over and raises when that
+    failed — so it is never closed behind the caller's back: `with` closes it, the finaliser does not (closing a half-fed or never-based deferred
+    sink from the garbage collector would change what reaches the disk)."""
+    _release = 'hhx_byte_sink_close'
+    _finalise = False
 
     def __init__(self, path, hbm_budget_bytes=0, expected_bytes=0, deferred=False):
         """deferred: the bytes go to the file at an offset given later by set_base() (hhx_byte_sink_open_deferred)"""
-        self.h = C.c_void_p()
         _register_join()
-        fn = load().hhx_byte_sink_open_deferred if deferred else load().hhx_byte_sink_open
-        check(fn(os.fsencode(path), int(hbm_budget_bytes), int(expected_bytes), C.byref(self.h)))
+        self.h = new_handle('hhx_byte_sink_open_deferred' if deferred else 'hhx_byte_sink_open', os.fsencode(path), int(hbm_budget_bytes),
+                            int(expected_bytes))
 
     def set_base(self, base):
         check(load().hhx_byte_sink_set_base(self.h, int(base)))
@@ -862,25 +927,24 @@ class ByteSink:
     def close(self):
         """queue the close (the file is complete after files_join()); returns the bytes handed to the sink"""
         n = C.c_int64(0)
-        if self.h is not None and self.h.value:
+        if getattr(self, 'h', None):
             check(load().hhx_byte_sink_close(self.h, C.byref(n)))
-            self.h = None
+        self.h = None
         return n.value
 
 
-class TextReader:
+class TextReader(Handle):
     """hhx_text_reader: a text file as chunks of whole lines in pinned host memory, read ahead by threads of the library"""
+    _release = 'hhx_text_reader_close'
 
     def __init__(self, path, chunk_bytes=256 << 20, threads=4, bgzf=False, byte_range=None):
         """bgzf: the file is bgzipped (BGZF blocks inflated by the threads); RuntimeError('... is not a BGZF file ...') for anything else.
         byte_range (begin, end): only the lines whose first byte lies in it (hhx_text_reader_open_range; BGZF: compressed offsets)"""
-        self.h = C.c_void_p()
         if byte_range is not None:
-            check(load().hhx_text_reader_open_range(os.fsencode(path), int(byte_range[0]), int(byte_range[1]), int(chunk_bytes), int(threads),
-                                                    int(bool(bgzf)), C.byref(self.h)))
+            self.h = new_handle('hhx_text_reader_open_range', os.fsencode(path), int(byte_range[0]), int(byte_range[1]), int(chunk_bytes), int(threads),
+                                int(bool(bgzf)))
             return
-        fn = load().hhx_text_reader_open_bgzf if bgzf else load().hhx_text_reader_open
-        check(fn(os.fsencode(path), int(chunk_bytes), int(threads), C.byref(self.h)))
+        self.h = new_handle('hhx_text_reader_open_bgzf' if bgzf else 'hhx_text_reader_open', os.fsencode(path), int(chunk_bytes), int(threads))
 
     def __iter__(self):
         """(host pointer, bytes) per chunk; a pointer is valid until the next one is asked for"""
@@ -891,63 +955,38 @@ class TextReader:
                 return
             yield host.value, n.value
 
-    def close(self):
-        if self.h is not None and self.h.value:
-            load().hhx_text_reader_close(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ClmSplit:
+class ClmSplit(Handle):
     """hhx_clm_split: CLM text, pushed in pieces cut anywhere, routed line by line to one file per group (split_clm_file,
     HapHiC_reassign.py:581-622).  names[k] belongs to group group_of_name[k] (-1: to none); paths[g] is the file of group g."""
     STATS = ('lines', 'kept', 'heads', 'seams', 'continuations', 'multi_line_tiles', 'multi_tile_lines')
+    _release = 'hhx_clm_split_destroy'
 
     def __init__(self, names, group_of_name, paths):
         blob, off = names_blob(names)
         grp = np.ascontiguousarray(group_of_name, np.int32)
         if grp.size != len(names):
             raise ValueError('ClmSplit: {} names, {} groups of names'.format(len(names), grp.size))
-        enc = [os.fsencode(p) for p in paths]
-        poff = np.zeros(len(enc) + 1, np.int64)
-        if enc:
-            poff[1:] = np.cumsum([len(b) for b in enc])
-        pblob = np.frombuffer(b''.join(enc) or b'\0', np.uint8)
-        self.n_groups = len(enc)
-        self.h = C.c_void_p()
-        check(load().hhx_clm_split_create(len(names), ptr(blob), ptr(off), ptr(grp) if grp.size else None, self.n_groups, ptr(pblob), ptr(poff),
-                                          C.byref(self.h)))
-
-    @staticmethod
-    def _raise(rc):
-        """IndexError as the reference's cols[1] raises it; everything else is the library's RuntimeError"""
-        if rc:
-            msg = load().hhx_last_error().decode('utf-8', 'replace')
-            if msg.startswith('IndexError: '):
-                raise IndexError(msg.split(': ', 1)[1])
-            raise RuntimeError('libhaphic_hip: ' + msg)
+        pblob, poff = names_blob(paths, os.fsencode)
+        self.n_groups = len(poff) - 1
+        self.h = new_handle('hhx_clm_split_create', len(names), ptr(blob), ptr(off), ptr(grp) if grp.size else None, self.n_groups, ptr(pblob), ptr(poff))
 
     def push(self, text=None, device_ptr=None, n_bytes=None):
-        """the next bytes of the file: bytes-like, or a device pointer + n_bytes"""
+        """the next bytes of the file: bytes-like, or a device pointer + n_bytes; IndexError as the reference's cols[1] raises it"""
         if device_ptr is not None:
-            return self._raise(load().hhx_clm_split_push(self.h, C.c_void_p(device_ptr), int(n_bytes), 1))
+            return check_py(load().hhx_clm_split_push(self.h, C.c_void_p(device_ptr), int(n_bytes), 1))
         buf = np.frombuffer(text, np.uint8)
-        self._raise(load().hhx_clm_split_push(self.h, ptr(buf) if buf.size else None, buf.size, 0))
+        check_py(load().hhx_clm_split_push(self.h, ptr(buf) if buf.size else None, buf.size, 0))
 
     def push_file(self, path, chunk_bytes=64 << 20, threads=4):
         """the whole file through the library's pinned read-ahead reader, in raw chunks of chunk_bytes"""
-        self._raise(load().hhx_clm_split_file(self.h, os.fsencode(path), int(chunk_bytes), int(threads)))
+        check_py(load().hhx_clm_split_file(self.h, os.fsencode(path), int(chunk_bytes), int(threads)))
 
     def finish(self):
         """flushes the open line; the files are complete on return.  -> (lines, lines kept, bytes per group)"""
         nl, nk = C.c_int64(0), C.c_int64(0)
         per = np.zeros(max(self.n_groups, 1), np.int64)
-        self._raise(load().hhx_clm_split_finish(self.h, C.byref(nl), C.byref(nk), ptr(per)))
+        check_py(load().hhx_clm_split_finish(self.h, C.byref(nl), C.byref(nk), ptr(per)))
         return nl.value, nk.value, per[:self.n_groups]
 
     def stats(self):
@@ -955,33 +994,22 @@ class ClmSplit:
         check(load().hhx_clm_split_stats(self.h, ptr(v)))
         return dict(zip(self.STATS, (int(x) for x in v)))
 
-    def close(self):
-        if self.h is not None and self.h.value:
-            load().hhx_clm_split_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SortGraph:
+class SortGraph(Handle):
     """hhx_sort_graph: the dense work of one group of `haphic sort`'s fast sorting (HapHiC_sort.py :60-88 :158-244 :406-435 :456-467), per round.
     Built from the round-1 edges (index pairs, integer weights); tests/sort_cases.py holds a numpy engine with the same interface."""
     METHODS = {'sum': 0, 'multiplication': 1, 'geometric_mean': 2}
     STATS = ('lds_aggregations', 'global_aggregations', 'cells_over', 'pairs_flagged')
     FOREST_STATS = ('lds_forests', 'hbm_forests', 'boruvka_rounds', 'jump_rounds', 'confidence_copies')
+    _release = 'hhx_sort_graph_destroy'
 
     def __init__(self, shape, ei, ej, w):
         ei, ej = np.ascontiguousarray(ei, np.int32), np.ascontiguousarray(ej, np.int32)
         w = np.ascontiguousarray(w, np.int64)
         if not (ei.size == ej.size == w.size):
             raise ValueError('SortGraph: {} / {} indices, {} weights'.format(ei.size, ej.size, w.size))
-        self.h = C.c_void_p()
-        check(load().hhx_sort_graph_create(int(shape), ei.size, ptr(ei) if ei.size else None, ptr(ej) if ei.size else None, ptr(w) if ei.size else None,
-                                           C.byref(self.h)))
+        self.h = new_handle('hhx_sort_graph_create', int(shape), ei.size, ptr(ei) if ei.size else None, ptr(ej) if ei.size else None,
+                            ptr(w) if ei.size else None)
 
     @property
     def shape(self):
@@ -1083,17 +1111,6 @@ class SortGraph:
         check(load().hhx_sort_graph_stats(self.h, ptr(v)))
         return dict(zip(self.STATS, (int(x) for x in v)))
 
-    def close(self):
-        if self.h is not None and self.h.value:
-            load().hhx_sort_graph_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class SortVerdictUnsupported(RuntimeError):
     """hhx_sort_verdict_sums answered HHX_UNSUPPORTED: the caller takes the reference's function"""
@@ -1115,9 +1132,7 @@ def sort_verdict_sums(value, lengths, r0=0, r1=None, want_stats=False):
     sums = np.zeros(max(r1 - int(r0), 0), np.int64)
     stats = np.zeros(len(SORT_VERDICT_STATS), np.int64)
     rc = load().hhx_sort_verdict_sums(n, ptr(v), ptr(ln), int(r0), r1, ptr(sums), ptr(stats))
-    if rc == GROUP_STATS_UNSUPPORTED:
-        raise SortVerdictUnsupported(load().hhx_last_error().decode('utf-8', 'replace'))
-    check(rc)
+    check_served(rc, SortVerdictUnsupported)
     return (sums, dict(zip(SORT_VERDICT_STATS, (int(x) for x in stats)))) if want_stats else sums
 
 
@@ -1154,7 +1169,7 @@ def _group_stats_args(group, n_groups, group_re, ctg_re):
     return grp, ng, gre, cre, out
 
 
-GROUP_STATS_UNSUPPORTED = 2       # HHX_UNSUPPORTED
+GROUP_STATS_UNSUPPORTED = HHX_UNSUPPORTED
 
 
 def group_stats(frag_i, frag_j, links, group, n_groups, group_re, ctg_re, sum_mode=0):
@@ -1167,16 +1182,14 @@ def group_stats(frag_i, frag_j, links, group, n_groups, group_re, ctg_re, sum_mo
     grp, ng, gre, cre, out = _group_stats_args(group, n_groups, group_re, ctg_re)
     rc = load().hhx_group_stats(len(lk), ptr(fi), ptr(fj), ptr(lk), 0, grp.shape[1], grp.shape[0], ptr(grp), ptr(ng), ptr(gre), ptr(cre), int(sum_mode),
                                 *[ptr(a) for a in out])
-    if rc == GROUP_STATS_UNSUPPORTED:
-        return None
-    check(rc)
-    return out
+    return out if check_served(rc) else None
 
 
-class Reassign:
+class Reassign(Handle):
     """hhx_reassign: the cells, the adjacency and the keys of one full_link_dict in HBM for the rounds of `haphic reassign` (run_reassignment
     :266-427) and the group-pair sums of its agglomerative step (include/haphic_hip.h).  tests/reassign_cases.py holds a numpy engine with the
     same interface.  Raises Unsupported where the library answers HHX_UNSUPPORTED."""
+    _release = 'hhx_reassign_destroy'
 
     class Unsupported(RuntimeError):
         pass
@@ -1193,7 +1206,8 @@ class Reassign:
         self.rounds = 0                 # device rounds so far: the tables are the reference's dicts only while it is 0
         self.launches = 0               # launch pairs of the last round
         self.h = C.c_void_p()
-        self._check(load().hhx_reassign_create(fi.size, ptr(fi), ptr(fj), ptr(lk), self.n_ctg, ptr(grp), self.n_groups, C.byref(self.h)))
+        rc = load().hhx_reassign_create(fi.size, ptr(fi), ptr(fj), ptr(lk), self.n_ctg, ptr(grp), self.n_groups, C.byref(self.h))
+        check_served(rc, Reassign.Unsupported)
 
     @classmethod
     def from_pickle(cls, link_pickle, n_ctg, group, n_groups):
@@ -1209,16 +1223,12 @@ class Reassign:
         self.rounds = self.launches = 0
         self.h = C.c_void_p()
         refused = C.c_int(0)
-        self._check(load().hhx_reassign_create_from_pickle(link_pickle.h, self.n_ctg, ptr(grp), self.n_groups, C.byref(refused), C.byref(self.h)))
+        rc = load().hhx_reassign_create_from_pickle(link_pickle.h, self.n_ctg, ptr(grp), self.n_groups, C.byref(refused), C.byref(self.h))
+        check_served(rc, Reassign.Unsupported)
         if refused.value:
-            cls.REFUSALS.append((refused.value, load().hhx_last_error().decode('utf-8', 'replace')))
+            cls.REFUSALS.append((refused.value, last_error()))
             return None
         return self
-
-    def _check(self, rc):
-        if rc == GROUP_STATS_UNSUPPORTED:
-            raise Reassign.Unsupported(load().hhx_last_error().decode('utf-8', 'replace'))
-        check(rc)
 
     def cells(self):
         """(sums, first) int64 [n_ctg, n_groups] as group_link_sums returns them"""
@@ -1239,9 +1249,10 @@ class Reassign:
         if cre.shape != (self.n_ctg,) or fl.shape != (self.n_ctg,) or (dm is not None and dm.shape != (self.n_groups,)):
             raise ValueError('Reassign.round: ctg_re and flags per contig, dismissed per group')
         counts, launches = np.zeros(4, np.int64), C.c_int64(0)
-        self._check(load().hhx_reassign_round(self.h, ptr(group), ptr(group_re), ptr(cre), od.size, ptr(od), ptr(fl), ptr(dm), float(min_links),
-                                              float(min_link_density), float(min_density_ratio), float(ambiguous_cutoff), int(bool(is_rescue_round)),
-                                              int(bool(gfa)), int(sum_mode), ptr(counts), C.byref(launches)))
+        rc = load().hhx_reassign_round(self.h, ptr(group), ptr(group_re), ptr(cre), od.size, ptr(od), ptr(fl), ptr(dm), float(min_links),
+                                       float(min_link_density), float(min_density_ratio), float(ambiguous_cutoff), int(bool(is_rescue_round)),
+                                       int(bool(gfa)), int(sum_mode), ptr(counts), C.byref(launches))
+        check_served(rc, Reassign.Unsupported)
         self.rounds += 1
         self.launches = launches.value
         return counts
@@ -1256,22 +1267,12 @@ class Reassign:
         check(load().hhx_reassign_pair_sums(self.h, ptr(mb), ptr(grp), int(n_groups), ptr(sums), ptr(first)))
         return sums, first
 
-    def close(self):
-        if self.h is not None and self.h.value:
-            load().hhx_reassign_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Fasta:
+class Fasta(Handle):
     """hhx_fasta: one FASTA file parsed on the device (parse_fasta, HapHiC_cluster.py:87-113) — the sequences back to back in HBM, the table on the
     host — and the writer of scaffolds.fa over it (build_final_scaffolds, HapHiC_build.py:153-168).  source: a path (str / os.PathLike) or the bytes
     of the file.  tests/build_cases.py holds a numpy engine with the same interface.  Raises Unsupported where the library answers HHX_UNSUPPORTED."""
+    _release = 'hhx_fasta_close'
 
     class Unsupported(RuntimeError):
         pass
@@ -1283,7 +1284,7 @@ class Fasta:
         else:
             buf = np.frombuffer(source, np.uint8)
             rc = load().hhx_fasta_open_bytes(ptr(buf) if buf.size else None, buf.size, int(bool(keep_letter_case)), C.byref(self.h))
-        self._check(rc)
+        check_served(rc, Fasta.Unsupported)
         n, ns, nn = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(load().hhx_fasta_counts(self.h, C.byref(n), C.byref(ns), C.byref(nn)))
         self.n_ctg, self.n_seq_bytes = n.value, ns.value
@@ -1291,12 +1292,6 @@ class Fasta:
         self.name_off, self.name_bytes = np.zeros(self.n_ctg + 1, np.int64), np.zeros(max(nn.value, 1), np.uint8)
         check(load().hhx_fasta_table(self.h, ptr(self.seq_off), ptr(self.seq_len), ptr(self.name_off), ptr(self.name_bytes)))
         self.name_bytes = self.name_bytes[:nn.value]
-
-    @staticmethod
-    def _check(rc):
-        if rc == GROUP_STATS_UNSUPPORTED:
-            raise Fasta.Unsupported(load().hhx_last_error().decode('utf-8', 'replace'))
-        check(rc)
 
     def names(self):
         """the contig names in file order (the text is ASCII: a byte >= 0x80 is refused)"""
@@ -1341,20 +1336,10 @@ class Fasta:
         if po.size != len(rec_names) + 1 or pc.size != pr.size or (po.size and pc.size != po[-1]):
             raise ValueError('Fasta.emit: {} records, {} piece offsets, {} / {} pieces'.format(len(rec_names), po.size, pc.size, pr.size))
         n = C.c_int64(0)
-        self._check(load().hhx_fasta_emit(self.h, os.fsencode(path), len(rec_names), ptr(blob), ptr(off), ptr(po), ptr(pc) if pc.size else None,
-                                          ptr(pr) if pr.size else None, int(Ns), int(max_width), C.byref(n)))
+        rc = load().hhx_fasta_emit(self.h, os.fsencode(path), len(rec_names), ptr(blob), ptr(off), ptr(po), ptr(pc) if pc.size else None,
+                                   ptr(pr) if pr.size else None, int(Ns), int(max_width), C.byref(n))
+        check_served(rc, Fasta.Unsupported)
         return n.value
-
-    def close(self):
-        if self.h is not None and self.h.value:
-            load().hhx_fasta_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def allelic_nonmax(ki, kj, kcnt, n_ctg, gptr, gmem):
@@ -1368,9 +1353,8 @@ def allelic_nonmax(ki, kj, kcnt, n_ctg, gptr, gmem):
         raise ValueError('allelic_nonmax: ki, kj, kcnt of one length; gptr[-1] == len(gmem)')
     mask, counters, bad = np.zeros(len(ki), np.uint8), np.zeros(3, np.int64), C.c_int32(0)
     rc = load().hhx_allelic_nonmax(len(ki), ptr(ki), ptr(kj), ptr(kcnt), int(n_ctg), len(gptr) - 1, ptr(gptr), ptr(gmem), ptr(mask), ptr(counters), C.byref(bad))
-    if rc == Ingest.UNSUPPORTED:
+    if not check_served(rc):
         return NotImplemented
-    check(rc)
     return None if bad.value else (mask, counters)
 
 
@@ -1429,7 +1413,6 @@ def dict_to_matrix(frag_i, frag_j, value, n_frag, in_set, n_rest, add_self_loops
     in_set = np.ascontiguousarray(in_set, np.uint8)
     frag_index = np.empty(max(n_frag, 1), np.int32)
     n_linked = C.c_int32(0)
-    out = C.c_void_p()
     if on_device:
         a, b, v = C.c_void_p(frag_i), C.c_void_p(frag_j), C.c_void_p(value)
         nk = int(n_keys)
@@ -1439,8 +1422,8 @@ def dict_to_matrix(frag_i, frag_j, value, n_frag, in_set, n_rest, add_self_loops
         fv = np.ascontiguousarray(value, np.float64)
         a, b, v = ptr(fi), ptr(fj), ptr(fv)
         nk = fi.size
-    check(load().hhx_dict_to_matrix(nk, a, b, v, int(on_device), int(n_frag), ptr(in_set), int(n_rest),
-                                    int(add_self_loops), ptr(frag_index), C.byref(n_linked), C.byref(out)))
+    out = new_handle('hhx_dict_to_matrix', nk, a, b, v, int(on_device), int(n_frag), ptr(in_set), int(n_rest), int(add_self_loops), ptr(frag_index),
+                     C.byref(n_linked))
     return DeviceCSR(out), frag_index[:n_frag], n_linked.value
 
 
@@ -1464,15 +1447,19 @@ def count_re_sites(seq, seg_off, seg_len, sites):
     return out[:off.size]
 
 
-class BamReader:
+class BamReader(Handle):
     """hhx_bam: BGZF / BAM container -> batches of device id / position arrays (f4)."""
+    _release = 'hhx_bam_close'
 
     def __init__(self, path, threads=0):
-        self.h = C.c_void_p()
-        check(load().hhx_bam_open(os.fsencode(path), int(threads), C.byref(self.h)))
+        self.h = new_handle('hhx_bam_open', os.fsencode(path), int(threads))
         n_ref, text, tlen = C.c_int32(0), C.c_char_p(), C.c_int64(0)
         names, offs = C.c_void_p(), C.c_void_p()
-        check(load().hhx_bam_header(self.h, C.byref(n_ref), C.byref(text), C.byref(tlen), C.byref(names), C.byref(offs)))
+        try:
+            check(load().hhx_bam_header(self.h, C.byref(n_ref), C.byref(text), C.byref(tlen), C.byref(names), C.byref(offs)))
+        except RuntimeError:
+            self.close()                # not left to the finaliser: the file and the reader threads go now
+            raise
         self.header_text = C.string_at(text, tlen.value).decode('utf-8', 'replace') if tlen.value else ''
         off = np.ctypeslib.as_array(C.cast(offs, C.POINTER(C.c_int64)), (n_ref.value + 1,)).copy() if n_ref.value else np.zeros(1, np.int64)
         blob = C.string_at(names, int(off[-1])) if n_ref.value and off[-1] else b''
@@ -1500,14 +1487,10 @@ class BamReader:
         check(load().hhx_bam_fetch(self.h, *[ptr(a) for a in out]))
         return out
 
-    def close(self):
-        if self.h:
-            load().hhx_bam_close(self.h)
-            self.h = None
 
-
-class ContactMap:
+class ContactMap(Handle):
     """hhx_contact_map: the dense scaffold-bin contact matrix of `haphic plot` (f4).  Tables as include/haphic_hip.h lists them."""
+    _release = 'hhx_contact_map_destroy'
 
     def __init__(self, in_set, aln_ptr, list_ptr, seg_lo, seg_hi, seg_bin, bin_size, n_total_bins):
         self.in_set = np.ascontiguousarray(in_set, np.uint8)
@@ -1515,9 +1498,8 @@ class ContactMap:
         self.list_ptr = np.ascontiguousarray(list_ptr, np.int32)
         self.seg = [np.ascontiguousarray(a, np.int32) for a in (seg_lo, seg_hi, seg_bin)]
         self.n_bins = int(n_total_bins)
-        self.h = C.c_void_p()
-        check(load().hhx_contact_map_create(len(self.in_set), ptr(self.in_set), ptr(self.aln_ptr), ptr(self.list_ptr), len(self.seg[0]),
-                                            ptr(self.seg[0]), ptr(self.seg[1]), ptr(self.seg[2]), int(bin_size), self.n_bins, C.byref(self.h)))
+        self.h = new_handle('hhx_contact_map_create', len(self.in_set), ptr(self.in_set), ptr(self.aln_ptr), ptr(self.list_ptr), len(self.seg[0]),
+                            ptr(self.seg[0]), ptr(self.seg[1]), ptr(self.seg[2]), int(bin_size), self.n_bins)
 
     def _push(self, n, p, on_device, pos_offset):
         bad = C.c_int64(-1)
@@ -1537,15 +1519,11 @@ class ContactMap:
         check(load().hhx_contact_map_fetch(self.h, ptr(out)))
         return out
 
-    def destroy(self):
-        if self.h:
-            load().hhx_contact_map_destroy(self.h)
-            self.h = None
 
-
-class PlotNorm:
+class PlotNorm(Handle):
     """hhx_plotnorm: the scaffold-bin matrix of `haphic plot` in HBM as int32 counts, for the Knight-Ruiz balancing, the scaled matrix and the
     off-diagonal median of HapHiC_plot.py normalize_matrix :407-504 (include/haphic_hip.h).  .max / .min / .symmetric describe the upload."""
+    _release = 'hhx_plotnorm_destroy'
 
     def __init__(self, matrix):
         matrix = np.ascontiguousarray(matrix, np.int64)
@@ -1593,11 +1571,6 @@ class PlotNorm:
         check(load().hhx_plotnorm_matvec(self.h, int(lo), int(hi), ptr(v), ptr(out)))
         return out
 
-    def destroy(self):
-        if self.h:
-            load().hhx_plotnorm_destroy(self.h)
-            self.h = None
-
 
 def select_middle(values):
     """the two middle values of a non-negative float64 array (radix select over the bit patterns on the device); None when it is empty"""
@@ -1607,17 +1580,13 @@ def select_middle(values):
     return np.array([lo.value, hi.value], np.uint64).view(np.float64) if len(values) else None
 
 
-class PairsParser:
+class PairsParser(Handle):
     """hhx_pairs_parser: .pairs text chunks -> device id / position arrays (+ the alignments.bed bytes)."""
+    _release = 'hhx_pairs_parser_destroy'
 
     def __init__(self, names):
-        enc = [n.encode() for n in names]
-        off = np.zeros(len(enc) + 1, np.int64)
-        if enc:
-            off[1:] = np.cumsum([len(b) for b in enc])
-        blob = np.frombuffer(b''.join(enc) or b'\0', np.uint8)
-        self.h = C.c_void_p()
-        check(load().hhx_pairs_parser_create(len(enc), ptr(blob), ptr(off), C.byref(self.h)))
+        blob, off = names_blob(names)
+        self.h = new_handle('hhx_pairs_parser_create', len(off) - 1, ptr(blob), ptr(off))
         self.n_lines = self.bed_bytes = 0
         self.wide = False
 
@@ -1637,12 +1606,7 @@ class PairsParser:
             rc = load().hhx_pairs_parse(self.h, ptr(buf) if buf.size else None, buf.size, 0, int(want_bed), C.byref(nl), C.byref(nb))
         else:
             rc = load().hhx_pairs_parse(self.h, C.c_void_p(device_ptr), int(n_bytes), 1, int(want_bed), C.byref(nl), C.byref(nb))
-        if rc:
-            msg = load().hhx_last_error().decode('utf-8', 'replace')
-            kind = {'IndexError': IndexError, 'ValueError': ValueError}.get(msg.split(':', 1)[0])
-            if kind:
-                raise kind(msg.split(': ', 1)[1])
-            raise RuntimeError('libhaphic_hip: ' + msg)
+        check_py(rc)
         self.n_lines, self.bed_bytes = nl.value, nb.value
         return self.n_lines
 
@@ -1687,20 +1651,10 @@ class PairsParser:
             check(load().hhx_pairs_parser_fetch(self.h, None, None, None, None, ptr(bed)))
         return bed
 
-    def destroy(self):
-        if self.h is not None and self.h.value:
-            load().hhx_pairs_parser_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class Ingest:
+class Ingest(Handle):
     """hhx_ingest handle: push batches of (id1, pos1, id2, pos2), then finalize/fetch."""
+    _release = 'hhx_ingest_destroy'
 
     def __init__(self, table, flank, bins=False, skip_intra=False, expected_keys=0):
         self._keep = table      # keeps the numpy arrays alive during create
@@ -1717,8 +1671,7 @@ class Ingest:
         cfg.bins, cfg.skip_intra = int(bool(bins)), int(bool(skip_intra))
         cfg.expected_keys = int(expected_keys)
         self.n_frag = table.n_frag
-        self.h = C.c_void_p()
-        check(load().hhx_ingest_create(C.byref(cfg), C.byref(self.h)))
+        self.h = new_handle('hhx_ingest_create', C.byref(cfg))
         self.n_full = self.n_flank = None
 
     def push(self, id1, pos1, id2, pos2, wide=None):
@@ -1827,7 +1780,7 @@ class Ingest:
         check(load().hhx_ingest_fetch_ht_items(self.h, C.byref(n), None, None, None))
         return n.value
 
-    UNSUPPORTED = 2      # HHX_UNSUPPORTED: "not served here, take the reference's loop" (the handle is untouched)
+    UNSUPPORTED = HHX_UNSUPPORTED
 
     def concordance_counts(self, max_read_pairs, nwindows, min_read_pairs=0):
         """cal_concordance_ratio :419-428 as integers (hhx_ingest_concordance): (m, diag, anti) int32 arrays in full_link_dict order —
@@ -1838,10 +1791,7 @@ class Ingest:
             self.finalize()
         m, diag, anti = (np.zeros(self.n_full, np.int32) for _ in range(3))
         rc = load().hhx_ingest_concordance(self.h, int(max_read_pairs), int(min_read_pairs), int(nwindows), ptr(m), ptr(diag), ptr(anti))
-        if rc == self.UNSUPPORTED:
-            return None
-        check(rc)
-        return m, diag, anti
+        return (m, diag, anti) if check_served(rc) else None
 
     def drop_links(self, full_drop, in_set):
         """update_link_dicts :488-509 for a whole verdict (hhx_ingest_drop_links): full_drop — one flag per full_link_dict key, in_set — one per
@@ -1859,9 +1809,8 @@ class Ingest:
         remaining = np.zeros(self.n_frag, np.uint8)
         first_row = np.full(self.n_frag, -1, np.int64)
         rc = load().hhx_ingest_drop_links(self.h, ptr(full_drop), ptr(in_set), C.byref(a), C.byref(b), ptr(gone), ptr(remaining), ptr(first_row))
-        if rc == self.UNSUPPORTED:
+        if not check_served(rc):
             return None
-        check(rc)
         self.n_full, self.n_flank = a.value, b.value
         self.first_row = first_row
         return self.n_full, self.n_flank, gone, remaining
@@ -1873,10 +1822,7 @@ class Ingest:
             self.finalize()
         grp, ng, gre, cre, out = _group_stats_args(group, n_groups, group_re, ctg_re)
         rc = load().hhx_ingest_group_stats(self.h, grp.shape[0], ptr(grp), ptr(ng), ptr(gre), ptr(cre), int(sum_mode), *[ptr(a) for a in out])
-        if rc == self.UNSUPPORTED:
-            return None
-        check(rc)
-        return out
+        return out if check_served(rc) else None
 
     def keep_frag_pairs(self, on=True):
         check(load().hhx_ingest_keep_frag_pairs(self.h, int(on)))
@@ -1906,9 +1852,7 @@ class Ingest:
                                   n_keys=self.n_flank)
         frag_index = np.empty(max(self.n_frag, 1), np.int32)
         n_linked = C.c_int32(0)
-        out = C.c_void_p()
-        check(load().hhx_ingest_link_matrix(self.h, ptr(in_set), int(n_rest), int(add_self_loops), ptr(frag_index),
-                                            C.byref(n_linked), C.byref(out)))
+        out = new_handle('hhx_ingest_link_matrix', self.h, ptr(in_set), int(n_rest), int(add_self_loops), ptr(frag_index), C.byref(n_linked))
         return DeviceCSR(out), frag_index[:self.n_frag], n_linked.value
 
     def write_clm(self, path, ctg_names):
@@ -1948,28 +1892,17 @@ class Ingest:
         check(load().hhx_ingest_push_table(self.h, int(which), int(n_rows), C.c_void_p(key_ptr), C.c_void_p(ord_full_ptr),
                                            C.c_void_p(ord_flank_ptr), C.c_void_p(ht_ptr), C.c_void_p(flank_ptr)))
 
-    def destroy(self):
-        if self.h is not None and self.h.value:
-            load().hhx_ingest_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class CorrectTable:
+class CorrectTable(Handle):
     """hhx_correct: coverage bins and (lo, hi) position lists of the intra-contig read pairs (pass one of --correct_nrounds), the
     break-point detection and the per-pair half of the breaking on them.  Segments = the contigs of the FASTA after finalize(), the
     children of the broken contigs after break_()."""
+    _release = 'hhx_correct_destroy'
 
     def __init__(self, ctg_len, resolution):
         lens = np.ascontiguousarray(ctg_len, np.int64)
         self.resolution = int(resolution)
-        self.h = C.c_void_p()
-        check(load().hhx_correct_create(len(lens), ptr(lens), self.resolution, C.byref(self.h)))
+        self.h = new_handle('hhx_correct_create', len(lens), ptr(lens), self.resolution)
 
     def push(self, id1, pos1, id2, pos2):
         arrs = [np.ascontiguousarray(a, np.int32) for a in (id1, pos1, id2, pos2)]
@@ -2067,37 +2000,14 @@ class CorrectTable:
         bp_off, zero = np.ascontiguousarray(bp_off, np.int64), np.ascontiguousarray(zero, np.uint8)
         check(load().hhx_correct_break(self.h, len(seg), ptr(seg), ptr(bp_off), ptr(bp_pos), ptr(zero)))
 
-    def destroy(self):
-        if self.h is not None and self.h.value:
-            load().hhx_correct_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class ContigRemap:
+class ContigRemap(Handle):
     """hhx_remap: (original contig id, position) -> (corrected contig id, position - break offset) in place on device arrays."""
+    _release = 'hhx_remap_destroy'
 
     def __init__(self, off, break_pos, new_id):
         off, break_pos, new_id = (np.ascontiguousarray(a, np.int32) for a in (off, break_pos, new_id))
-        self.h = C.c_void_p()
-        check(load().hhx_remap_create(len(off) - 1, ptr(off), ptr(break_pos) if break_pos.size else None, ptr(new_id) if new_id.size else None,
-                                      C.byref(self.h)))
+        self.h = new_handle('hhx_remap_create', len(off) - 1, ptr(off), ptr(break_pos) if break_pos.size else None, ptr(new_id) if new_id.size else None)
 
     def apply(self, n, id_ptr, pos_ptr):
         check(load().hhx_remap_apply(self.h, int(n), C.c_void_p(id_ptr), C.c_void_p(pos_ptr)))
-
-    def destroy(self):
-        if self.h is not None and self.h.value:
-            load().hhx_remap_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass

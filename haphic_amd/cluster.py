@@ -727,7 +727,7 @@ class DenseSweep:
                 # triangle was planned): back to row blocks within the budget
                 if not self._budget_rows or self._budget_rows >= self.n:
                     raise
-                _lib.load().hhx_pool_trim()
+                _lib.check(_lib.load().hhx_pool_trim())
                 self.bounds = list(range(0, self.n, int(self._budget_rows))) + [self.n]
         self._warm = warm if len(self.bounds) == 2 and self.resident is not None else None
         if len(self.bounds) == 2:

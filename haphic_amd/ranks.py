@@ -187,7 +187,7 @@ def init(host_transport=None):
     device = local % n_dev
     if host_transport is None:
         host_transport = os.environ.get('HAPHIC_HOST_TRANSPORT', '') == '1' or world > n_dev
-    _lib.check(_lib.load().hhx_set_device(device))
+    _lib.set_device(device)
     torch.cuda.set_device(device)
     timeout = datetime.timedelta(seconds=TIMEOUT_S)
     if host_transport:
@@ -372,7 +372,7 @@ def _take(parser, k, wide):
     import torch
     from . import _lib
     from .sharded import HipEngine
-    _lib.check(_lib.load().hhx_synchronize())
+    _lib.synchronize()
     eng = HipEngine('cuda:%d' % _CTX.device)
     p = parser.device_arrays()
     pt, pd = ('<i8', torch.int64) if wide else ('<i4', torch.int32)

@@ -69,18 +69,13 @@ class HipEngine:
     def pack_block(self, m, words):
         """m's exchange message [row lengths | column indices | value bits] in an int32 tensor of `words` elements"""
         buf = self.scratch('msg', int(words), self.torch.int32)
-        _lib.check(_lib.load().hhx_csr_pack_block(m.h, _lib.C.c_void_p(buf.data_ptr()), int(words)))
+        _lib.csr_pack_block(m, buf.data_ptr(), words)
         return buf
 
     def unpack_blocks(self, rows, nnzs, packed, stride, n_cols):
         """the gathered messages (message b at packed[b * stride:]) stacked into one matrix"""
-        rows = np.ascontiguousarray(rows, np.int64)
-        nnzs = np.ascontiguousarray(nnzs, np.int64)
         self.torch.cuda.current_stream(self.device).synchronize()
-        out = _lib.C.c_void_p()
-        _lib.check(_lib.load().hhx_csr_unpack_blocks(len(rows), rows.ctypes.data_as(_lib.c_i64p), nnzs.ctypes.data_as(_lib.c_i64p),
-                                                     _lib.C.c_void_p(packed.data_ptr()), int(stride), int(n_cols), _lib.C.byref(out)))
-        return _lib.DeviceCSR(out)
+        return _lib.csr_unpack_blocks(rows, nnzs, packed.data_ptr(), stride, n_cols)
 
     def shape(self, m):
         return m.shape3
@@ -122,20 +117,20 @@ class HipEngine:
     # rectangles of the dense block between the ranks: hand-written tile transposes / one strided copy on the library's stream
     # (y: the [rows, n] view of dense_upper, rows y.stride(0) floats apart)
     def _at(self, y, r, c):
-        return _lib.C.c_void_p(y.data_ptr() + 4 * (int(r) * int(y.stride(0)) + int(c)))
+        return y.data_ptr() + 4 * (int(r) * int(y.stride(0)) + int(c))
 
     def mirror_block(self, y, r_src, c_src, rows, cols, r_dst, c_dst):
         """y[r_dst : r_dst + cols, c_dst : c_dst + rows] = y[r_src : r_src + rows, c_src : c_src + cols] transposed (disjoint regions)"""
-        _lib.check(_lib.load().hhx_transpose_f32(self._at(y, r_src, c_src), int(y.stride(0)), self._at(y, r_dst, c_dst), int(y.stride(0)), int(rows), int(cols)))
+        _lib.transpose_f32(self._at(y, r_src, c_src), y.stride(0), self._at(y, r_dst, c_dst), y.stride(0), rows, cols)
 
     def pack_columns(self, y, c0, c1, out):
         """out (1-D, y.shape[0] * (c1 - c0) floats) = the rectangle y[:, c0:c1], row-major"""
-        _lib.check(_lib.load().hhx_copy_rect_f32(self._at(y, 0, c0), int(y.stride(0)), _lib.C.c_void_p(out.data_ptr()), int(c1 - c0), int(y.shape[0]), int(c1 - c0)))
+        _lib.copy_rect_f32(self._at(y, 0, c0), y.stride(0), out.data_ptr(), c1 - c0, y.shape[0], c1 - c0)
 
     def unpack_transposed(self, y, c0, buf, rows_s):
         """y[:, c0 : c0 + rows_s] = buf viewed as [rows_s, y.shape[0]] (another rank's rows), transposed"""
         self.torch.cuda.current_stream(self.device).synchronize()           # the collective that filled buf ran on torch's stream
-        _lib.check(_lib.load().hhx_transpose_f32(_lib.C.c_void_p(buf.data_ptr()), int(y.shape[0]), self._at(y, 0, c0), int(y.stride(0)), int(rows_s), int(y.shape[0])))
+        _lib.transpose_f32(buf.data_ptr(), y.shape[0], self._at(y, 0, c0), y.stride(0), rows_s, y.shape[0])
 
     def dense_finish(self, d, inflation, pruning):
         """the rows finished from the completed block: (pruned rows, products, nnz of the expanded rows)"""
@@ -175,55 +170,37 @@ class HipEngine:
         m.free()
 
     def sync(self):
-        _lib.check(_lib.load().hhx_synchronize())
+        _lib.synchronize()
         if self.device.type == 'cuda':
             self.torch.cuda.current_stream(self.device).synchronize()       # the collectives run on torch's stream
 
     # ---- sharded link-matrix build (hhx_shard_*): `src` is this rank's finalized _lib.Ingest
     def shard_open(self, src, in_set):
-        in_set = np.ascontiguousarray(in_set, np.uint8)
-        h = _lib.C.c_void_p()
-        _lib.check(_lib.load().hhx_shard_create(src.h, _lib.ptr(in_set), _lib.C.byref(h)))
-        return {'h': h, 'n_frag': src.n_frag}
+        return _lib.ShardBuild(src, in_set)
 
     def shard_first(self, st):
-        p = _lib.C.c_void_p()
-        _lib.check(_lib.load().hhx_shard_first(st['h'], _lib.C.byref(p)))
-        return self.view(p.value, st['n_frag'], '<i8', self.torch.int64)
+        return self.view(st.first(), st.n_frag, '<i8', self.torch.int64)
 
     def rank_first(self, first):
         fidx = self.torch.empty(first.numel(), dtype=self.torch.int32, device=self.device)
-        nl = _lib.C.c_int32(0)
         self.torch.cuda.current_stream(self.device).synchronize()
-        _lib.check(_lib.load().hhx_rank_first(first.numel(), _lib.C.c_void_p(first.data_ptr()), _lib.C.c_void_p(fidx.data_ptr()), _lib.C.byref(nl)))
-        return fidx, nl.value
+        return fidx, _lib.rank_first(first.numel(), first.data_ptr(), fidx.data_ptr())
 
     def shard_emit(self, st, fidx, bounds):
-        b = np.ascontiguousarray(bounds, np.int32)
-        counts = np.zeros(len(b) - 1, np.int64)
-        w0, w1 = _lib.C.c_void_p(), _lib.C.c_void_p()
-        _lib.check(_lib.load().hhx_shard_emit(st['h'], _lib.C.c_void_p(fidx.data_ptr()), len(b), b.ctypes.data_as(_lib.c_i32p), _lib.C.byref(w0),
-                                              _lib.C.byref(w1), counts.ctypes.data_as(_lib.c_i64p)))
+        w0, w1, counts = st.emit(fidx.data_ptr(), bounds)
         n = int(counts.sum())
-        return self.view(w0.value, n, '<i8', self.torch.int64), self.view(w1.value, n, '<i8', self.torch.int64), counts.tolist()
+        return self.view(w0, n, '<i8', self.torch.int64), self.view(w1, n, '<i8', self.torch.int64), counts.tolist()
 
     def shard_close(self, st):
-        _lib.load().hhx_shard_destroy(st['h'])
+        st.close()
 
     def rows_from_entries(self, w0, w1, r0, r1, shape, recv_counts=None):
         """the owner's CSR row block from the entries it received; recv_counts (entries per source rank, in the order they lie in
         w0 / w1): every source's run is already in row order, so the rows are merged straight from the runs (hhx_rows_from_runs)"""
         self.torch.cuda.current_stream(self.device).synchronize()
-        out = _lib.C.c_void_p()
         if recv_counts is not None and 1 <= len(recv_counts) <= 64:
-            off = np.zeros(len(recv_counts) + 1, np.int64)
-            off[1:] = np.cumsum(recv_counts)
-            _lib.check(_lib.load().hhx_rows_from_runs(len(recv_counts), off.ctypes.data_as(_lib.c_i64p), _lib.C.c_void_p(w0.data_ptr()),
-                                                      _lib.C.c_void_p(w1.data_ptr()), int(r0), int(r1), int(shape), 1, _lib.C.byref(out)))
-            return _lib.DeviceCSR(out)
-        _lib.check(_lib.load().hhx_rows_from_entries(int(w0.numel()), _lib.C.c_void_p(w0.data_ptr()), _lib.C.c_void_p(w1.data_ptr()), int(r0), int(r1),
-                                                     int(shape), 1, _lib.C.byref(out)))
-        return _lib.DeviceCSR(out)
+            return _lib.rows_from_runs(recv_counts, w0.data_ptr(), w1.data_ptr(), r0, r1, shape)
+        return _lib.rows_from_entries(w0.numel(), w0.data_ptr(), w1.data_ptr(), r0, r1, shape)
 
     def normalize_l1(self, m):
         _lib.normalize_l1(m)

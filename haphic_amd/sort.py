@@ -46,7 +46,7 @@ DEVICE = None                         # the HIP device of `--device N`: HIP's cu
 def _default_engine(shape, ei, ej, w):
     from . import _lib
     if DEVICE is not None:
-        _lib.check(_lib.load().hhx_set_device(DEVICE))
+        _lib.set_device(DEVICE)
     return _lib.SortGraph(shape, ei, ej, w)
 
 
@@ -461,7 +461,7 @@ class VerdictUnsupported(RuntimeError):
 def _default_verdict_engine(value, lengths, r0, r1):
     from . import _lib
     if DEVICE is not None:
-        _lib.check(_lib.load().hhx_set_device(DEVICE))
+        _lib.set_device(DEVICE)
     try:
         return _lib.sort_verdict_sums(value, lengths, r0, r1)
     except _lib.SortVerdictUnsupported as e:
@@ -622,7 +622,7 @@ class PickleProxy:
 def _default_heads_engine(path):
     from . import _lib
     if DEVICE is not None:
-        _lib.check(_lib.load().hhx_set_device(DEVICE))
+        _lib.set_device(DEVICE)
     return _lib.LinkPickle.open(path)
 
 
