@@ -3,6 +3,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <condition_variable>
 #include <deque>
 #include <thread>
@@ -17,6 +18,7 @@ namespace hhx {
 struct FileSink {
     static constexpr size_t PIECE = (size_t)64 << 20;
     static constexpr int NBUF = 4, NWRITE = 2;       // one file takes ~5 GB/s on a RAM disk whatever the number of writers (measured: tools/fs_write_bench.c)
+    size_t piece = PIECE;                            // bytes per piece: hhx_tune "sink_piece", read once in open_fd (the buffers stay PIECE bytes)
     int fd = -1;
     i64 pos = 0;
     void *pin[NBUF] = {};
@@ -31,6 +33,7 @@ struct FileSink {
 
     int open_fd(int fd_) {
         fd = fd_;
+        piece = (size_t)std::max<i64>(4096, std::min<i64>((i64)PIECE, tune_get("sink_piece", (i64)PIECE)));
         for (int b = 0; b < NBUF; ++b) HHX_HIP(hipHostMalloc(&pin[b], PIECE, hipHostMallocDefault));
         for (auto &w : worker) w = std::thread([this] {
             for (;;) {
@@ -60,8 +63,8 @@ struct FileSink {
         return open_fd(f);
     }
     int write_device(const unsigned char *dev, size_t n) {
-        for (size_t o = 0; o < n; o += PIECE) {
-            const size_t m = n - o < PIECE ? n - o : PIECE;
+        for (size_t o = 0; o < n; o += piece) {
+            const size_t m = n - o < piece ? n - o : piece;
             const int b = next; next = (next + 1) % NBUF;
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !busy[b]; }); if (err) return fail("write failed: %s", strerror(err)); }
             HHX_HIP(hipMemcpyAsync(pin[b], dev + o, m, hipMemcpyDeviceToHost, g_stream));
@@ -69,6 +72,7 @@ struct FileSink {
             { std::lock_guard<std::mutex> lk(mu); busy[b] = true; q.push_back(Job{b, m, pos}); }
             cv.notify_all();
             pos += (i64)m;
+            prof_count("sink_pieces", 1);
         }
         return 0;
     }

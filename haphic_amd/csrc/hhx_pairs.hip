@@ -410,7 +410,7 @@ extern "C" int hhx_ingest_fetch_ht_items(hhx_ingest *h, int64_t *n_items, int32_
 
 namespace {
 
-constexpr i64 CLM_CHUNK = (i64)1 << 27;            // distances per chunk (1 GB of sort keys, ~2 GB of text)
+constexpr i64 CLM_CHUNK = (i64)1 << 27;            // distances per chunk (1 GB of sort keys, ~2 GB of text); hhx_tune "clm_chunk"
 constexpr int CW_T = 256, CW_OUT_CAP = 24 * 1024;
 
 __device__ __forceinline__ i32 dlen(u64 a) { i32 n = 0; do { ++n; a /= 10; } while (a); return n; }
@@ -479,7 +479,8 @@ __global__ __launch_bounds__(256) void k_clm_len(i64 E, const u64 *__restrict__ 
 // contig names) writes to HBM directly
 __global__ __launch_bounds__(CW_T) void k_clm_write(i64 E, const u64 *__restrict__ sk, int dbits, i64 kr0, const i64 *__restrict__ kept_g,
                                                     const i64 *__restrict__ kept_cnt, const u64 *__restrict__ stk, const unsigned char *__restrict__ names,
-                                                    const i64 *__restrict__ name_off, const i64 *__restrict__ off, unsigned char *__restrict__ text) {
+                                                    const i64 *__restrict__ name_off, const i64 *__restrict__ off, unsigned char *__restrict__ text,
+                                                    unsigned int *__restrict__ n_direct) {
     __shared__ __attribute__((aligned(16))) unsigned char s_out[CW_OUT_CAP];
     const u64 dmask = (1ull << dbits) - 1;
     for (i64 e0 = (i64)blockIdx.x * CW_T; e0 < E; e0 += (i64)gridDim.x * CW_T) {
@@ -487,6 +488,7 @@ __global__ __launch_bounds__(CW_T) void k_clm_write(i64 E, const u64 *__restrict
         const i64 b0 = off[e0], b1 = off[e1];
         const i64 out_bias = b0 & ~(i64)15;                      // text is 16-byte aligned (pool allocation)
         const bool staged = b1 - out_bias <= CW_OUT_CAP;
+        if (!staged && threadIdx.x == 0) atomicAdd(n_direct, 1u);   // "clm_blocks_direct"
         const i64 e = e0 + threadIdx.x;
         if (e < e1) {
             const u64 k = sk[e];
@@ -565,13 +567,15 @@ int hhx::ingest_write_clm_fd(hhx_ingest *h, int fd, const uint8_t *names_blob, c
     HHX_HIP(hipMemcpyAsync(h_eoff.data(), eoff.p, sizeof(i64) * ((size_t)nk + 1), hipMemcpyDeviceToHost, g_stream));
     HHX_HIP(hipStreamSynchronize(g_stream));
     const int dbits = bits_for((u64)(2 * h->max_ctg_len));           // every distance is at most len_i + len_j
-    DevBuf<unsigned int> bad;
-    if (bad.alloc(1)) return 1;
-    HHX_HIP(hipMemsetAsync(bad.p, 0, sizeof(unsigned int), g_stream));
+    DevBuf<unsigned int> bad;                                        // [0]: a position beyond its contig, [1]: blocks k_clm_write wrote directly
+    if (bad.alloc(2)) return 1;
+    HHX_HIP(hipMemsetAsync(bad.p, 0, 2 * sizeof(unsigned int), g_stream));
+    const i64 chunk = std::max<i64>(4, std::min<i64>(CLM_CHUNK, tune_get("clm_chunk", CLM_CHUNK)));
     i64 lines = 0;
+    unsigned int direct_seen = 0;
     for (i64 kr0 = 0; kr0 < nk;) {
-        // as many whole groups as fit CLM_CHUNK distances (at least one)
-        const i64 limit = h_eoff[(size_t)kr0] + CLM_CHUNK / 4;
+        // as many whole groups as fit `chunk` distances (at least one)
+        const i64 limit = h_eoff[(size_t)kr0] + chunk / 4;
         i64 kr1 = (i64)(std::upper_bound(h_eoff.begin() + kr0 + 1, h_eoff.end(), limit) - h_eoff.begin()) - 1;
         if (kr1 <= kr0) kr1 = kr0 + 1;
         const i64 E = 4 * (h_eoff[(size_t)kr1] - h_eoff[(size_t)kr0]);
@@ -597,9 +601,14 @@ int hhx::ingest_write_clm_fd(hhx_ingest *h, int fd, const uint8_t *names_blob, c
         DevBuf<unsigned char> text;
         if (text.alloc((size_t)B + 16)) return 1;
         k_clm_write<<<(unsigned)std::min<i64>((E + CW_T - 1) / CW_T, 256 * 32), CW_T, 0, g_stream>>>(E, skeys.p, dbits, kr0, kept_g.p, kept_cnt.p, G.stk.p,
-                                                                                                      d_names.p, d_noff.p, off.p, text.p);
+                                                                                                      d_names.p, d_noff.p, off.p, text.p, bad.p + 1);
         HHX_LAUNCH_CHECK();
-        HHX_TRY(sink.write_device(text.p, (size_t)B));
+        unsigned int direct = direct_seen;
+        if (prof_enabled()) HHX_HIP(hipMemcpyAsync(&direct, bad.p + 1, sizeof direct, hipMemcpyDeviceToHost, g_stream));
+        HHX_TRY(sink.write_device(text.p, (size_t)B));              // synchronises the stream
+        prof_count("clm_chunks", 1);
+        prof_count("clm_blocks_direct", (i64)(direct - direct_seen));
+        direct_seen = direct;
         lines += 4 * (kr1 - kr0);
         kr0 = kr1;
     }

@@ -402,6 +402,7 @@ static const char *const k_tune_names[] = {"cls", "cls_nc", "cls_balance", "link
                                            "cache_slice_mb", "dense_tri", "reuse", "row_order", "dense_seed_hint", "block_tiles", "correct_agg",
                                            "plotnorm_small", "plotnorm_chunk_cells", "sort_lds_shape", "groupstats_lds_slots", "reassign_window",
                                            "fasta_slab", "sort_verdict_lds_n", "pkl_chunk", "heads_bitmap", "heads_grid", "sort_forest_lds", "reassign_check_grid",
+                                           "clm_chunk", "sink_piece",
 #ifdef HHX_PROBE_BUILD
                                            "probe",          // measurement build only: the LDS atomics switched off, results are garbage
 #endif

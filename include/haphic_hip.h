@@ -85,7 +85,10 @@ int hhx_pool_prewarm(int32_t n, const int64_t *bytes);
  * of the passes of hhx_pickle_group_heads, clamped to [1, 1536] (default 1536; fewer: more steps per wavefront; same arrays); "sort_forest_lds" = the largest shape whose hhx_sort_graph_forest runs as one
  * workgroup on LDS arrays, clamped to [0, 2048] (default 2048; 0: always the multi-launch form in HBM; same arrays); "reassign_check_grid" = the
  * most workgroups of the pass over the keys that hhx_reassign_create_from_pickle runs before it builds a handle, clamped to [1, 2048] (default 2048;
- * fewer: more steps per lane; same answers).  value INT64_MIN: back
+ * fewer: more steps per lane; same answers); "clm_chunk" = the most distances (four per kept read pair) hhx_ingest_write_clm sorts and formats
+ * at once, clamped to [4, 2^27] (default 2^27; whole contig pairs per chunk, at least one; read once per file; the same file, other seams);
+ * "sink_piece" = bytes per piece the file writer of paired_links.clm, scaffolds.fa and alignments.bed copies to a pinned buffer and hands to
+ * its pwrite() threads, clamped to [4096, 2^26] (default 2^26; read once when the file is opened; the same file).  value INT64_MIN: back
  * to the default.  Unset knobs fall back to the
  * environment variable HHX_<NAME>. */
 int hhx_tune(const char *name, int64_t value);
@@ -100,7 +103,9 @@ int hhx_profile_get(const char *kernel, double *total_ms, int64_t *launches);
  * ("expand_window_n_win") and the survivor-pool retries ("expand_pool_retries"); per hhx_pairs_parse, the blocks of 128 lines whose
  * text was staged in LDS / read from HBM directly ("text_blocks_staged", "text_blocks_direct": a span beyond the LDS window, or a
  * device buffer that is not 16-byte aligned) and, of the blocks that write alignments.bed bytes, those formatted in LDS / straight
- * into HBM ("bed_blocks_lds", "bed_blocks_direct") */
+ * into HBM ("bed_blocks_lds", "bed_blocks_direct"); per hhx_ingest_write_clm, the chunks of the file ("clm_chunks") and the blocks of 256
+ * distances whose text, beyond the 24 KiB LDS window, went straight into HBM ("clm_blocks_direct"); the pieces every device-fed file left
+ * in ("sink_pieces") */
 int hhx_profile_counter(const char *name, int64_t *value);
 
 /* ---------------------------------------------------------------- matrices */
