@@ -56,6 +56,19 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              whose rows hold length and RE sites; a row copies its sequence from the device only if something reads it (run() never
                              does).  The reference's function still takes a file with a byte >= 0x80, with a sequence line before the first header,
                              with repeated contig names, or beyond half of the device's memory
+  --device-front             cluster only, OPT-IN (tools/cluster_front_bench.py has not been run at full size yet; the default follows its record):
+                             run the front of run() :2785-2831 on the device.  The FASTA file is parsed there and the rows of fa_dict carry views of
+                             the sequences that stay there (haphic_amd/assembly.py): stat_fragments counts the bins and flanks of all contigs in one
+                             call on them, the children of a --correct_nrounds round are views counted in one call, and only corrected_asm.fa
+                             :1267-1269 reads sequences (one copy of all of them); every GFA file (--gfa) is read on the device (csrc/hhx_gfa.hip) and
+                             only the table of its S records comes to the host.  Without the flag parse_fasta is the per-line loop, which joins every
+                             sequence into a Python string, stat_fragments and the correction slice those strings and copy them to the device to
+                             count RE sites, and parse_gfa is the reference's per-line loop.  parse_fasta hands back what --keep-reference-fasta
+                             lists; parse_gfa hands the whole call to the reference's function when a file has an S record with fewer than five
+                             fields, an integer that is not 1 to 18 digits, a name beyond 255 bytes, a byte >= 0x80, is larger than half of the
+                             device's memory or is no regular file.  No effect with --keep-reference-ingest
+  --device-gfa               reassign only, OPT-IN for the same reason: read the files of --gfa (parse_gfa, HapHiC_cluster.py:150-185) on the device as
+                             --device-front does; the same files go back to the reference's function
   --keep-host-keys           reassign only: copy the keys of full_links.pkl to the host after reading, as parse_link_dict's host passes over them
                              need (renumbering, the check for a key that names one contig twice, the total).  Without the flag the table stays open
                              on the device, those checks are one pass over the keys there and the handle of the rounds is built from them by
@@ -167,6 +180,8 @@ def main(argv=None):
     keep_verdict = bool(_take(argv, '--keep-reference-verdict', False))
     keep_heads = bool(_take(argv, '--keep-reference-heads', False))
     keep_forest = bool(_take(argv, '--keep-reference-forest', False))
+    device_front = bool(_take(argv, '--device-front', False))
+    device_gfa = bool(_take(argv, '--device-gfa', False))
     stub = bool(_take(argv, '--stub-missing-imports', False))
     scripts = _reference_scripts(ref)
     if stub:
@@ -193,7 +208,7 @@ def main(argv=None):
     if command == 'reassign':
         import HapHiC_reassign as R                                 # needs pysam / sklearn, as the reference does
         patch.patch_reassign(R, rounds=not keep_rounds, pickle=not keep_pickle, resident=not (keep_pickle or keep_rounds or keep_host_keys),
-                             fasta=not keep_fasta)
+                             fasta=not keep_fasta, gfa=device_gfa)
         sys.argv = ['haphic reassign'] + argv
         R.run(R.parse_arguments(), 'HapHiC_reassign.log')           # == HapHiC_reassign.main() :919-924
         return 0
@@ -218,7 +233,8 @@ def main(argv=None):
         return 0
     import HapHiC_cluster as H                                      # the unmodified reference module
     patch.patch_reference(H, ingest=not keep_ingest, allelic=not keep_allelic and ctx is None,      # the allelic, statistics and dense seams: one-rank jobs only
-                          statistics=not keep_statistics and ctx is None, dense=not keep_dense and ctx is None)
+                          statistics=not keep_statistics and ctx is None, dense=not keep_dense and ctx is None,
+                          front=device_front)                       # rank 0 alone runs the front; the other ranks never see fa_dict
     sys.argv = ['haphic cluster'] + argv
     return ranks.run_rank(lambda: H.run(H.parse_arguments(), 'HapHiC_cluster.log'))      # == HapHiC_cluster.main() :2962-2967
 

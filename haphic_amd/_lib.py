@@ -242,6 +242,11 @@ SIGNATURES = {
     'hhx_fasta_re_counts': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_fasta_fetch': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'hhx_fasta_close': (C.c_int, [C.c_void_p]),
+    'hhx_gfa_open': (C.c_int, [C.c_char_p, c_vpp]),
+    'hhx_gfa_open_bytes': (C.c_int, [C.c_void_p, C.c_int64, c_vpp]),
+    'hhx_gfa_counts': (C.c_int, [C.c_void_p, c_i64p, c_i64p]),
+    'hhx_gfa_table': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'hhx_gfa_close': (C.c_int, [C.c_void_p]),
     'hhx_dmat_from_host': (C.c_int, [C.c_int32, C.c_void_p, c_vpp]),
     'hhx_dmat_from_csr': (C.c_int, [C.c_void_p, c_vpp]),
     'hhx_dmat_to_host': (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1340,6 +1345,50 @@ class Fasta(Handle):
                                    ptr(pr) if pr.size else None, int(Ns), int(max_width), C.byref(n))
         check_served(rc, Fasta.Unsupported)
         return n.value
+
+
+class Gfa:
+    """hhx_gfa: the S records of one GFA file read on the device (parse_gfa, HapHiC_cluster.py:150-185).  source: a path (str / os.PathLike) or the
+    bytes of the file.  The library's handle holds the table on the host and nothing on the device, so the constructor copies the table —
+    names() in file order, lengths and depths int64 — and releases the handle before it returns, whatever happens: the object owns nothing and is
+    no Handle; close() and `with` exist for callers that treat every reader alike.  tests/assembly_cases.py holds a host stand-in with the same
+    interface.  Raises Unsupported where the library answers HHX_UNSUPPORTED (include/haphic_hip.h lists the cases); no handle was made then."""
+
+    class Unsupported(RuntimeError):
+        pass
+
+    def __init__(self, source):
+        h = C.c_void_p()
+        if isinstance(source, (str, os.PathLike)):
+            rc = load().hhx_gfa_open(os.fsencode(source), C.byref(h))
+        else:
+            buf = np.frombuffer(source, np.uint8)
+            rc = load().hhx_gfa_open_bytes(ptr(buf) if buf.size else None, buf.size, C.byref(h))
+        check_served(rc, Gfa.Unsupported)
+        try:
+            n, nn = C.c_int64(0), C.c_int64(0)
+            check(load().hhx_gfa_counts(h, C.byref(n), C.byref(nn)))
+            self.n_rec = n.value
+            self.name_off, self.name_bytes = np.zeros(self.n_rec + 1, np.int64), np.zeros(max(nn.value, 1), np.uint8)
+            self.lengths, self.depths = np.zeros(self.n_rec, np.int64), np.zeros(self.n_rec, np.int64)
+            check(load().hhx_gfa_table(h, ptr(self.name_off), ptr(self.name_bytes), ptr(self.lengths), ptr(self.depths)))
+            self.name_bytes = self.name_bytes[:nn.value]
+        finally:
+            load().hhx_gfa_close(h)
+
+    def names(self):
+        """field 1 of every record in file order (the text is ASCII: a byte >= 0x80 is refused)"""
+        blob, off = self.name_bytes.tobytes().decode('ascii'), self.name_off.tolist()
+        return [blob[off[k]:off[k + 1]] for k in range(self.n_rec)]
+
+    def close(self):
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        pass
 
 
 def allelic_nonmax(ki, kj, kcnt, n_ctg, gptr, gmem):

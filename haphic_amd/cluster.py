@@ -158,7 +158,8 @@ class _ReCountBatch:
         self.flank, self.pieces, self.cursor = flank, [], 0
         self.keys, self.off, self.len = [], [], []
 
-    def add_sequence(self, seq):
+    def add_sequence(self, info):
+        seq = info[0]
         self.base = self.cursor
         self.pieces.append(seq)
         self.cursor += len(seq)
@@ -179,22 +180,62 @@ class _ReCountBatch:
         return totals
 
 
+class _ViewCountBatch:
+    """_ReCountBatch for rows whose sequences lie in the memory of one engine (haphic_amd/assembly.py ViewRow): a slice is a segment of the
+    resident sequences, the flank rule :192-199 is applied to all of them at once, and ONE re_counts_device call counts them where they lie."""
+
+    def __init__(self, flank, engine):
+        self.flank, self.engine = flank, engine
+        self.keys, self.off, self.len = [], [], []
+
+    def add_sequence(self, info):
+        self.base = info.view[1]
+
+    def want(self, key, start, length):
+        self.keys.append(key); self.off.append(self.base + start); self.len.append(length)
+
+    def resolve(self, RE):
+        if not self.keys:
+            return {}
+        off, length, f = np.array(self.off, np.int64), np.array(self.len, np.int64), self.flank
+        two = length > 2 * f if f else np.zeros(len(off), bool)       # longer than both flanks together: the flanks alone
+        seg_off = np.concatenate([off, off[two] + length[two] - f])
+        seg_len = np.concatenate([np.where(two, f, length), np.full(int(two.sum()), f, np.int64)])
+        counts = np.asarray(self.engine.re_counts_device(_sites_of(RE), seg_off, seg_len), np.int64)
+        total = counts[:len(off)] + 1                                 # the pseudo-count :196
+        total[two] += counts[len(off):]
+        return dict(zip(self.keys, total.tolist()))
+
+
+def _count_batch(fa_dict, flank):
+    """the view batch while EVERY row still has a view on one engine, else the string batch"""
+    engine = None
+    for info in fa_dict.values():
+        view = getattr(info, 'view', None)
+        if view is None or (engine is not None and view[0] is not engine):
+            return _ReCountBatch(flank)
+        engine = view[0]
+    return _ReCountBatch(flank) if engine is None else _ViewCountBatch(flank, engine)
+
+
 def stat_fragments(fa_dict, RE, read_depth_dict, whitelist, nchrs=0, flank=0, Nx=100, bin_size=0, logger=logger):
     """stat_fragments() :188-296 with every RE-site count of the bins / flanks coming from one device call.  Same seven
     return values, same side effects on fa_dict (sequences dropped) and read_depth_dict (bins inherit their contig's
-    entry), same seeded shuffle before the length sort that defines the Nx set."""
+    entry), same seeded shuffle before the length sort that defines the Nx set.  While every row of fa_dict still has a view of
+    sequences that lie on the device (haphic_amd/assembly.py) the slices are counted there and no sequence is read; one row without
+    a view — a plain list, a row whose element 0 was assigned — sends the whole call through the strings."""
     import random
     logger.info('Making some statistics of fragments (contigs / bins)')
     total_len = sum(info[1] for info in fa_dict.values())
     bin_size = _resolve_bin_size(bin_size, total_len, nchrs, logger)
-    batch = _ReCountBatch(flank * 1000)
+    batch = _count_batch(fa_dict, flank * 1000)
     frag_len_dict, known_sites = {}, {}
     bin_set, split_ctg_set = set(), set()
     for ctg, info in fa_dict.items():
-        seq, ctg_len, whole_contig_sites = info
+        ctg_len, whole_contig_sites = info[1], info[2]               # (element 0 is read by the string batch alone: a row with a view stays on the device)
         if ctg_len > bin_size:                                       # :230 — the contig becomes ceil(len / bin_size) bins
             split_ctg_set.add(ctg)
-            batch.add_sequence(seq)
+            batch.add_sequence(info)
             starts = range(0, ctg_len, bin_size)
             for m, start in enumerate(starts, 1):
                 name = '{}_bin{}'.format(ctg, m)
@@ -211,7 +252,7 @@ def stat_fragments(fa_dict, RE, read_depth_dict, whitelist, nchrs=0, flank=0, Nx
             if not batch.flank or ctg_len <= 2 * batch.flank:
                 known_sites[ctg] = whole_contig_sites                # parse_fasta already counted the whole contig
             else:
-                batch.add_sequence(seq)
+                batch.add_sequence(info)
                 batch.want(ctg, 0, ctg_len)
         info[0] = None                                               # :266
     known_sites.update(batch.resolve(RE))

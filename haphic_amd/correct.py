@@ -213,11 +213,17 @@ def update_bookkeeping(ctg_break_point_dict, frag_source_dict, final_break_pos_d
     """The dict half of break_and_update_ctgs (:1028-1034 :1115-1187): every broken contig leaves fa_dict / read_depth_dict, its children
     `raw:start-end` (1-based, closed, on the ORIGINAL contig) enter them in order, and take the parent's place — in descending order of
     position, which is what convert_ctg :1405-1411 walks — in the two final_break_* lists of their source contig.
+    A parent whose row has a view of sequences on the device (haphic_amd/assembly.py) gets children that are views of its view, and the RE sites
+    :1031 of all such children of the call come from one re_counts_device call; a parent without a view is sliced and counted as a string.
     -> {contig: [child names]} in ctg_break_point_dict order."""
+    from . import assembly
     count_re = count_re or cluster.count_RE_sites
-    children = {}
+    children, resident = {}, []
     for ctg, break_points in ctg_break_point_dict.items():
-        seq, length = fa_dict[ctg][0], fa_dict[ctg][1]
+        parent = fa_dict[ctg]
+        length = parent[1]
+        on_device = getattr(parent, 'view', None) is not None
+        seq = None if on_device else parent[0]
         if ctg in unbroken_ctgs:
             raw, shift = ctg, 0
         else:
@@ -236,12 +242,18 @@ def update_bookkeeping(ctg_break_point_dict, frag_source_dict, final_break_pos_d
             frag_source_dict[name] = source
             if read_depth_dict:
                 read_depth_dict[name] = read_depth_dict[ctg]
-            piece = seq[s:e]
-            fa_dict[name] = [piece, e - s, count_re(piece, args.RE)]
+            if on_device:
+                fa_dict[name] = assembly.child_row(parent, s, e)
+                resident.append(fa_dict[name])
+            else:
+                piece = seq[s:e]
+                fa_dict[name] = [piece, e - s, count_re(piece, args.RE)]
         del fa_dict[ctg]
         if read_depth_dict:
             del read_depth_dict[ctg]
         children[ctg] = names
+    if resident:
+        assembly.count_children(resident, args.RE)
     return children
 
 

@@ -69,6 +69,13 @@ ALLELIC_SEAMS = {
 STATISTICS_SEAMS = {
     'output_statistics': ('HapHiC_cluster.py:2279-2478', statistics.output_statistics),
 }
+# the front of run() :2785-2831 on the device (haphic_amd/assembly.py).  OPT-IN at this level, like the seams above: parse_fasta returns rows whose
+# sequences stay in HBM, parse_gfa reads every file there; stat_fragments and correct.update_bookkeeping, bound by default, work on such rows
+# without reading a sequence.  Files the readers refuse go to the original functions.
+FRONT_SEAMS = {
+    'parse_fasta': 'HapHiC_cluster.py:87-113',
+    'parse_gfa': 'HapHiC_cluster.py:150-185',
+}
 
 
 # position of `dense_matrix` in the reference signatures.  --dense_matrix (:2723) is the reference's own numpy mode (also what every
@@ -124,12 +131,15 @@ def _run_then_join(original):
     return run
 
 
-def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics=False, dense=False):
+def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics=False, dense=False, front=False, front_engine=None, gfa_engine=None):
     """H: the imported reference module (HapHiC_cluster).  Returns {name: original} so the caller can undo.  allelic=True (together with
     ingest): remove_allelic_HiC_links :474-692 is re-bound too (ALLELIC_SEAMS); `python -m haphic_amd cluster` asks for it on one-rank jobs.
     statistics=True (together with ingest): output_statistics :2279-2478 likewise (STATISTICS_SEAMS).  dense=True: the four seams of DENSE_ARG
     take their dense_matrix=True calls (--dense_matrix) themselves instead of handing them back to the reference's numpy code, and
-    dict_to_matrix leaves the clustering matrix of a frozen table in HBM for them."""
+    dict_to_matrix leaves the clustering matrix of a frozen table in HBM for them.  front=True (together with ingest): parse_fasta :87-113 and
+    parse_gfa :150-185 are re-bound too (FRONT_SEAMS, haphic_amd/assembly.py): the sequences stay on the device behind the rows of fa_dict, and
+    stat_fragments and the bookkeeping of --correct_nrounds — the mirrors bound above — count on them there; front_engine / gfa_engine: stand-ins
+    for _lib.Fasta / _lib.Gfa (the tests' host engines)."""
     from . import _lib
     _lib.load()                          # fail loudly here if the HIP library is missing
     saved = {}
@@ -154,6 +164,11 @@ def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics
             fn = _with_original(fn, saved[name])
         setattr(H, name, _dense_dispatch(fn, saved[name], DENSE_ARG[name]) if name in DENSE_ARG and not dense else fn)
     cluster.DENSE_SEAM_BOUND = bool(dense)
+    if ingest and front:
+        from . import assembly
+        saved.setdefault('parse_gfa', getattr(H, 'parse_gfa', None))
+        H.parse_fasta = assembly.bind_fasta(H, front_engine, original=saved['parse_fasta'])
+        H.parse_gfa = assembly.bind_gfa(H, gfa_engine, original=saved['parse_gfa'])
     if ingest and getattr(H, 'run', None) is not None:
         saved['run'] = H.run
         H.run = _run_then_join(H.run)    # main() :2967 and HapHiC_pipeline.py:358 resolve `run` through the module, like every seam
@@ -162,7 +177,8 @@ def patch_reference(H, ingest=True, matrix_build=True, allelic=False, statistics
     return saved
 
 
-def patch_reassign(R, rounds=False, engine=None, pickle=False, pickle_engine=None, resident=False, fasta=False, fasta_engine=None):
+def patch_reassign(R, rounds=False, engine=None, pickle=False, pickle_engine=None, resident=False, fasta=False, fasta_engine=None, gfa=False,
+                   gfa_engine=None):
     """R: the imported HapHiC_reassign module.  f3: parse_link_dict :217-263 (the per-group link sums behind reassign's
     link densities) on the device for integer link counts; float / normalised links go to the original function.
     split_clm_file :581-622 (paired_links.clm routed line by line to split_clms/<group>.clm) goes through the device too
@@ -176,11 +192,13 @@ def patch_reassign(R, rounds=False, engine=None, pickle=False, pickle_engine=Non
     the host only when somebody asks for the arrays; with rounds=True parse_link_dict builds its handle from it there (reassign.bind_pickle,
     reassign.bind_rounds); pickle_engine is then a stand-in for _lib.LinkPickle.open.  fasta=True: parse_fasta (HapHiC_cluster.py:87-113, imported
     :23) is re-bound too (reassign.bind_fasta): the file is parsed and its RE sites counted on the device, fa_dict is a plain dict of
-    containers.FastaRow whose sequences stay there; fasta_engine: a stand-in for _lib.Fasta.  Returns {name: original}."""
+    containers.FastaRow whose sequences stay there; fasta_engine: a stand-in for _lib.Fasta.  gfa=True: parse_gfa (HapHiC_cluster.py:150-185,
+    imported :23, called :790) is re-bound too (assembly.bind_gfa): every file is read on the device and only the table of its S records comes to
+    the host; gfa_engine: a stand-in for _lib.Gfa.  Returns {name: original}."""
     from . import reassign
     if not rounds:
         engine = None
-    if engine is None or (pickle and pickle_engine is None) or (fasta and fasta_engine is None):
+    if engine is None or (pickle and pickle_engine is None) or (fasta and fasta_engine is None) or (gfa and gfa_engine is None):
         from . import _lib
         _lib.load()
     original = R.parse_link_dict
@@ -201,6 +219,9 @@ def patch_reassign(R, rounds=False, engine=None, pickle=False, pickle_engine=Non
         mirrors['parse_pickle'] = reassign.bind_pickle(R, pickle_engine, resident) if resident else reassign.bind_pickle(R, pickle_engine)
     if fasta:
         mirrors['parse_fasta'] = reassign.bind_fasta(R, fasta_engine)
+    if gfa:
+        from . import assembly
+        mirrors['parse_gfa'] = assembly.bind_gfa(R, gfa_engine)
     for name, fn in mirrors.items():
         saved.setdefault(name, getattr(R, name))
         setattr(R, name, fn)

@@ -194,16 +194,18 @@ def bind_pickle(R, engine=None, resident=False):
 
 
 # ------------------------------------------------------------------ parse_fasta (patch_reassign(R, fasta=True))
-def bind_fasta(R, engine=None):
+def bind_fasta(R, engine=None, original=None, rows=None):
     """-> the mirror of parse_fasta (HapHiC_cluster.py:87-113, as HapHiC_reassign imports it :23) for the module R.  run() :782-916 never reads a
     sequence: it asks fa_dict for lengths, RE sites, iteration and `in`.  So the file is parsed on the device (_lib.Fasta), the RE sites of all
     contigs are counted there in one call on the sequences where they lie (re_counts_device), and fa_dict is a plain dict {name: containers.FastaRow}
     in file order whose rows fetch their sequence only if somebody looks at it.  The log line is the reference's, through the logger given.  The
     original function takes the call for a file the reader refuses (a byte >= 0x80, a sequence line before the first header, a text beyond half of
     the device's memory), for repeated contig names, and for a path that is no file (its own exception is raised).  engine: a stand-in for _lib.Fasta
-    (the tests' numpy engine)."""
+    (the tests' numpy engine).  original: the function that takes those calls (by default what R binds now).  rows(fa, off, lengths, re_sites) -> the
+    rows of fa_dict in file order, for a caller whose rows carry more than a fetch (haphic_amd/assembly.py: the views of `haphic cluster`)."""
     Engine = engine if engine is not None else _lib.Fasta
-    original = R.parse_fasta
+    if original is None:
+        original = R.parse_fasta
     try:
         import inspect
         default_logger = inspect.signature(original).parameters['logger'].default
@@ -224,6 +226,8 @@ def bind_fasta(R, engine=None):
         logger.info('Parsing input FASTA file...')
         counts = fa.re_counts_device(cluster._sites_of(RE)) if names else np.zeros(0, np.int64)
         off, lengths = np.asarray(fa.seq_off, np.int64).tolist(), np.asarray(fa.seq_len, np.int64).tolist()
+        if rows is not None:
+            return dict(zip(names, rows(fa, off, lengths, (counts + 1).tolist())))
 
         def fetch(k):
             return fa.fetch(off[k], lengths[k]).decode('ascii')

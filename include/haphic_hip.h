@@ -998,6 +998,27 @@ int hhx_fasta_emit(hhx_fasta *f, const char *path, int64_t n_rec, const uint8_t 
                    const int32_t *piece_ctg, const uint8_t *piece_rev, int64_t Ns, int64_t max_width, int64_t *n_bytes);
 int hhx_fasta_close(hhx_fasta *f);
 
+/* ---------------------------------------------------------------- the GFA reader of parse_gfa, scripts/HapHiC_cluster.py:150-185 (haphic_amd/csrc/hhx_gfa.hip)
+ * hhx_gfa_open / hhx_gfa_open_bytes: a file (through the pinned read-ahead of hhx_text_reader_open_raw) or bytes in host memory go to HBM in one piece and
+ *   the table of the S records comes back; nothing stays on the device.  Lines are Python's text-mode lines ('\n', "\r\n" and a lone '\r' end a
+ *   line).  A record is a line that begins with the two bytes 'S', TAB :160; field k is line.split('\t')[k] :161.  Per record, in file order: the
+ *   bytes of field 1 :162, the integer behind the last ':' of field 3 (the whole field without one) :163, the same of field 4 :164.  An integer is
+ *   served as 1 to 18 ASCII digits that end the field — or, where field 4 is the last field of the line, stand in front of the line break.
+ *   HHX_UNSUPPORTED (hhx_last_error() names the line and the reason; no handle is made): a record with fewer than five fields (the TABs of the
+ *   lines behind it are never credited to it); any other spelling of an integer (signs, blanks, underscores, more digits, none: Python's int()
+ *   decides); a name longer than 255 bytes; a byte >= 0x80 anywhere in the text (the reference decodes the file by the locale); a text beyond half
+ *   of the device's memory; a path that is no regular file.  No lane walks a line: a sequence field of any length costs a binary search in the
+ *   scanned TAB counts of the 4 KB blocks.  The passes are grid-stride; the environment variable HHX_GFA_GRID (read at every launch) caps their
+ *   workgroups, so that tests walk the loops on one and two of them.
+ * hhx_gfa_counts: records, name bytes (any pointer may be null).  hhx_gfa_table: name_off [n_rec + 1], the names one after the other, len [n_rec],
+ *   depth [n_rec] (any pointer may be null). */
+typedef struct hhx_gfa hhx_gfa;
+int hhx_gfa_open(const char *path, hhx_gfa **out);
+int hhx_gfa_open_bytes(const uint8_t *text, int64_t n_bytes, hhx_gfa **out);
+int hhx_gfa_counts(const hhx_gfa *g, int64_t *n_rec, int64_t *n_name_bytes);
+int hhx_gfa_table(const hhx_gfa *g, int64_t *name_off, uint8_t *names, int64_t *len, int64_t *depth);
+int hhx_gfa_close(hhx_gfa *g);
+
 #ifdef __cplusplus
 }
 #endif
