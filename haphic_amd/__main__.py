@@ -22,6 +22,12 @@ The front of run() :898-923 runs on the device too: HT_links.pkl is read into ar
 and is compacted there into the contigs' sequences, haphic_amd/scaffolds.py) and build_final_scaffolds :74-179 (scaffolds.fa gathered, reverse-complemented and
 wrapped on the device, written slab by slab; both AGP files from the host arrays) run on the device (haphic_amd.patch.patch_build); parse_tours, the juicebox
 script and run() :244-283 are the reference's, called as its main() :286-291 calls it.
+`python -m haphic_amd refsort <arguments of "haphic refsort">` wraps HapHiC_refsort.py: parse_fasta as for `build`; parse_paf :81-134 (the PAF file goes to HBM in
+one piece, the first 12 fields of every line are located there whatever the length of its cg:Z: tag, csrc/hhx_paf.hip, and the nested dict is built from the
+table with numpy); order_and_orient_groups :151-342 (both weighted longest-increasing-subsequence sums of all groups from one device call, csrc/hhx_sortverdict.hip
+hhx_lis_sums; the AGP lines from host code; scaffolds.refsort.fa sliced, reverse-complemented and wrapped on the device and written slab by slab to the PATH of
+--fout, haphic_amd/refsort.py) run on the device (haphic_amd.patch.patch_refsort; parse_paf only with --device-paf); parse_agp, alignment_check and run() :383-412 are the reference's, called as its
+main() :415-420 calls it.
 
 The reference checkout is found through --reference DIR or $HAPHIC_REFERENCE (the repository root or its scripts/
 directory).  Extra flags of the wrapper (removed before the reference parses the command line):
@@ -89,6 +95,18 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
   --keep-reference-build     build only: leave parse_fasta and build_final_scaffolds to the reference's per-line and per-60-bases Python loops.  Without the
                              flag a call still goes to the reference's function for a FASTA file with a byte >= 0x80, with a sequence line in front of
                              the first header, with a contig name that repeats, or beyond half of the device's memory, and for --max_width < 1 or --Ns < 0
+  --keep-reference-refsort   refsort only: leave parse_fasta, parse_paf and order_and_orient_groups to the reference's loops (line.split() over every cg:Z: tag, two
+                             O(n^2) find_lis passes per group in Python, 60 bases per fout.write).  Without the flag parse_fasta and
+                             order_and_orient_groups run on the device; a call still goes to the reference's function, whole and before it logs a
+                             line, for a FASTA file as --keep-reference-build lists; for --max_width < 1, an AGP slice that is not
+                             1 <= start <= end <= len(contig), a negative N count, an orientation that is neither + nor -, a group of more than 2^18
+                             alignments, an alignment length <= 0, a group_ref_dict that does not flatten into arrays
+  --device-paf               refsort only, OPT-IN: run parse_paf on the device too.  Measured (tools/refsort_bench.py, profiles/refsort_bench.json): at 3 Gb /
+                             940 500 lines 0.22 s against the reference's 2.4 s (bare) and 0.41 s against 7.6 s (2.9 GB of text with cg:Z: tails), but at
+                             30 Mb / 9 405 lines its slowest repeats, 14 and 27 ms, stand against 15 and 51 ms of the reference measured on another box: not
+                             the factor of 2 the rule asks of a yardstick from another box, so the piece stays opt-in.  With the flag a file still goes
+                             to the reference's function for a line of fewer than 12 fields, an integer field that is not 1 to 18 digits, a name beyond
+                             255 bytes, a byte >= 0x80, a coordinate of 2^52 or more, beyond half of the device's memory or when it is no regular file
   --keep-reference-verdict   sort only: leave compare_fast_sort_and_allhic :645-724 (fast sorting or ALLHiC, per group) to the reference's loop: for each of the
                              n - 1 rotations of the fast-sort tour two O(n^2) weighted longest-increasing-subsequence passes in Python.  Without the flag the
                              sums of all rotations come from one device call (haphic_amd/sort.py bind_verdict: one wavefront per rotation, csrc/hhx_sortverdict.hip)
@@ -114,7 +132,8 @@ directory).  Extra flags of the wrapper (removed before the reference parses the
                              dict_to_matrix decides in round 1, or after foreign code touched its sub_HT_dict or the confidence token), beyond shape
                              65535, and when maximum_spanning_tree is called with anything but algorithm='kruskal'
   --stub-missing-imports     development boxes only: empty stand-ins for pysam / portion when they are not installed
-                             (the .pairs path needs neither; BAM input then fails loudly inside the reference)
+                             (the .pairs path needs neither; BAM input then fails loudly inside the reference); for refsort the stand-in of
+                             portion is haphic_amd/intervals.py, closed intervals that work, because the calls handed back build them
   --gpus N                   cluster only: run the job as N ranks, one fresh process per rank (haphic_amd/ranks.py); the files are
                              byte-identical to the one-rank run; with --correct_nrounds both correction passes over a .pairs file are shared
                              across the ranks too.  Under torchrun (RANK / WORLD_SIZE set) its ranks are used instead.
@@ -153,15 +172,15 @@ def main(argv=None):
         print(__doc__)
         return 0
     command = argv.pop(0)
-    if command not in ('cluster', 'plot', 'reassign', 'sort', 'build'):
-        raise SystemExit('haphic_amd wraps the "cluster", "plot", "reassign", "sort" and "build" steps only (got {!r}); run the other steps with the reference'.format(command))
+    if command not in ('cluster', 'plot', 'reassign', 'sort', 'build', 'refsort'):
+        raise SystemExit('haphic_amd wraps the "cluster", "plot", "reassign", "sort", "build" and "refsort" steps only (got {!r}); run the other steps with the reference'.format(command))
     if command == 'sort' and not argv:
         # nothing to hand to the reference: say what the wrapper is, as for a step it does not wrap, rather than go looking for the checkout
         raise SystemExit('haphic_amd wraps the "cluster", "plot", "reassign", "sort" and "build" steps only and hands them the arguments of the reference\'s '
                          'command; {!r} came without any (haphic sort: fasta HT_links clm_dir groups ...)'.format(command))
     from . import ranks
     gpus, host_transport = ranks.take_args(argv)
-    if command in ('plot', 'reassign', 'sort', 'build') and (gpus or 1) > 1:
+    if command in ('plot', 'reassign', 'sort', 'build', 'refsort') and (gpus or 1) > 1:
         raise SystemExit('--gpus is a flag of the "cluster" step only')
     if (gpus or 1) > 1 and not ranks.in_torchrun():
         # one fresh child process per rank (never exec: this process may not replace itself), each with RANK / WORLD_SIZE / LOCAL_RANK
@@ -177,6 +196,8 @@ def main(argv=None):
     keep_fasta = bool(_take(argv, '--keep-reference-fasta', False))
     keep_host_keys = bool(_take(argv, '--keep-host-keys', False))
     keep_build = bool(_take(argv, '--keep-reference-build', False))
+    keep_refsort = bool(_take(argv, '--keep-reference-refsort', False))
+    device_paf = bool(_take(argv, '--device-paf', False))
     keep_verdict = bool(_take(argv, '--keep-reference-verdict', False))
     keep_heads = bool(_take(argv, '--keep-reference-heads', False))
     keep_forest = bool(_take(argv, '--keep-reference-forest', False))
@@ -191,6 +212,9 @@ def main(argv=None):
             except ImportError:
                 m = types.ModuleType(name)
                 m.__dict__.update(attrs)
+                if name == 'portion' and command == 'refsort':       # the calls handed back to the reference build intervals (:72, :229)
+                    from . import intervals
+                    m.closed = intervals.closed
                 sys.modules[name] = m
     from . import _lib, patch
     _lib.check(_lib.load().hhx_set_device(device))                 # fails here, loudly, without a GPU or the library
@@ -230,6 +254,13 @@ def main(argv=None):
             patch.patch_build(B)
         sys.argv = ['haphic build'] + argv
         B.run(B.parse_arguments(), 'HapHiC_build.log')              # == HapHiC_build.main() :286-291
+        return 0
+    if command == 'refsort':
+        import HapHiC_refsort as F                                  # imports HapHiC_cluster for parse_fasta :16, with all it needs
+        if not keep_refsort:
+            patch.patch_refsort(F, paf=device_paf)                  # parse_paf: opt-in, as profiles/refsort_bench.json decides
+        sys.argv = ['haphic refsort'] + argv
+        F.run(F.parse_arguments(), 'HapHiC_refsort.log')            # == HapHiC_refsort.main() :415-420
         return 0
     import HapHiC_cluster as H                                      # the unmodified reference module
     patch.patch_reference(H, ingest=not keep_ingest, allelic=not keep_allelic and ctx is None,      # the allelic, statistics and dense seams: one-rank jobs only

@@ -247,6 +247,14 @@ SIGNATURES = {
     'hhx_gfa_counts': (C.c_int, [C.c_void_p, c_i64p, c_i64p]),
     'hhx_gfa_table': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_gfa_close': (C.c_int, [C.c_void_p]),
+    'hhx_fasta_emit_segments': (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int64, c_i64p]),
+    'hhx_paf_open': (C.c_int, [C.c_char_p, c_vpp]),
+    'hhx_paf_open_bytes': (C.c_int, [C.c_void_p, C.c_int64, c_vpp]),
+    'hhx_paf_counts': (C.c_int, [C.c_void_p, c_i64p, c_i64p, c_i64p]),
+    'hhx_paf_table': (C.c_int, [C.c_void_p] + [C.c_void_p] * 10),
+    'hhx_paf_close': (C.c_int, [C.c_void_p]),
+    'hhx_lis_sums': (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'hhx_dmat_from_host': (C.c_int, [C.c_int32, C.c_void_p, c_vpp]),
     'hhx_dmat_from_csr': (C.c_int, [C.c_void_p, c_vpp]),
     'hhx_dmat_to_host': (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -1345,6 +1353,91 @@ class Fasta(Handle):
                                    ptr(pr) if pr.size else None, int(Ns), int(max_width), C.byref(n))
         check_served(rc, Fasta.Unsupported)
         return n.value
+
+    def emit_segments(self, path, rec_names, piece_off, piece_ctg, piece_start, piece_len, piece_rev, max_width):
+        """hhx_fasta_emit_segments: the records (rec_names: list of str; record r: pieces [piece_off[r], piece_off[r + 1])) as a FASTA file of
+        max_width columns; piece k is bytes [piece_start[k], piece_start[k] + piece_len[k]) of contig piece_ctg[k], reversed and complemented where
+        piece_rev[k], or piece_len[k] 'N' where piece_ctg[k] == -1; nothing between the pieces.  -> bytes written"""
+        blob, off = names_blob(rec_names)
+        po, pc = np.ascontiguousarray(piece_off, np.int64), np.ascontiguousarray(piece_ctg, np.int32)
+        ps, pl = np.ascontiguousarray(piece_start, np.int64), np.ascontiguousarray(piece_len, np.int64)
+        pr = np.ascontiguousarray(piece_rev, np.uint8)
+        if po.size != len(rec_names) + 1 or not (pc.size == ps.size == pl.size == pr.size) or (po.size and pc.size != po[-1]):
+            raise ValueError('Fasta.emit_segments: {} records, {} piece offsets, {} / {} / {} / {} pieces'.format(len(rec_names), po.size, pc.size, ps.size,
+                                                                                                                  pl.size, pr.size))
+        n = C.c_int64(0)
+        some = pc.size > 0
+        rc = load().hhx_fasta_emit_segments(self.h, os.fsencode(path), len(rec_names), ptr(blob), ptr(off), ptr(po), ptr(pc) if some else None,
+                                            ptr(ps) if some else None, ptr(pl) if some else None, ptr(pr) if some else None, int(max_width), C.byref(n))
+        check_served(rc, Fasta.Unsupported)
+        return n.value
+
+
+class Paf:
+    """hhx_paf: the lines of one PAF file read on the device (parse_paf, HapHiC_refsort.py:81-134).  source: a path (str / os.PathLike) or the bytes
+    of the file.  As with Gfa the library's handle holds the table on the host and nothing on the device, so the constructor copies the table —
+    names() in first-seen order, query / target (name ids, int32), query_start, query_end, target_start, target_end, mapq (int64), plus (bool) per
+    line that is not blank — and releases the handle before it returns, whatever happens: the object owns nothing and is no Handle; close() and
+    `with` exist for callers that treat every reader alike.  tests/refsort_cases.py holds a host stand-in with the same interface.  Raises
+    Unsupported where the library answers HHX_UNSUPPORTED (include/haphic_hip.h lists the cases); no handle was made then."""
+
+    class Unsupported(RuntimeError):
+        pass
+
+    def __init__(self, source):
+        h = C.c_void_p()
+        if isinstance(source, (str, os.PathLike)):
+            rc = load().hhx_paf_open(os.fsencode(source), C.byref(h))
+        else:
+            buf = np.frombuffer(source, np.uint8)
+            rc = load().hhx_paf_open_bytes(ptr(buf) if buf.size else None, buf.size, C.byref(h))
+        check_served(rc, Paf.Unsupported)
+        try:
+            n, nn, nb = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+            check(load().hhx_paf_counts(h, C.byref(n), C.byref(nn), C.byref(nb)))
+            self.n_rec, self.n_names = n.value, nn.value
+            self.name_off, self.name_bytes = np.zeros(self.n_names + 1, np.int64), np.zeros(max(nb.value, 1), np.uint8)
+            self.query, self.target = np.zeros(self.n_rec, np.int32), np.zeros(self.n_rec, np.int32)
+            self.query_start, self.query_end, self.target_start, self.target_end, self.mapq = (np.zeros(self.n_rec, np.int64) for _ in range(5))
+            plus = np.zeros(self.n_rec, np.uint8)
+            check(load().hhx_paf_table(h, ptr(self.name_off), ptr(self.name_bytes), ptr(self.query), ptr(self.target), ptr(self.query_start),
+                                       ptr(self.query_end), ptr(self.target_start), ptr(self.target_end), ptr(self.mapq), ptr(plus)))
+            self.name_bytes = self.name_bytes[:nb.value]
+            self.plus = plus.astype(bool)
+        finally:
+            load().hhx_paf_close(h)
+
+    def names(self):
+        """fields 0 and 5 of all lines, each name once, in first-seen order (the text is ASCII: a byte >= 0x80 is refused)"""
+        blob, off = self.name_bytes.tobytes().decode('ascii'), self.name_off.tolist()
+        return [blob[off[k]:off[k + 1]] for k in range(self.n_names)]
+
+    def close(self):
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        pass
+
+
+class LisUnsupported(RuntimeError):
+    """hhx_lis_sums answered HHX_UNSUPPORTED: the caller takes the reference's function"""
+
+
+def lis_sums(ptr_, value, weight):
+    """hhx_lis_sums: (sums_f, sums_r), int64 per sequence — both find_lis sums (HapHiC_refsort.py:175-214) of the sequences
+    [ptr_[s], ptr_[s + 1]) of value (int64 keys) and weight.  tests/refsort_cases.py holds a host engine with the same signature.  Raises
+    LisUnsupported where the library answers HHX_UNSUPPORTED."""
+    p, v, w = np.ascontiguousarray(ptr_, np.int64), np.ascontiguousarray(value, np.int64), np.ascontiguousarray(weight, np.int64)
+    if p.ndim != 1 or p.size < 1 or v.shape != w.shape or v.ndim != 1 or int(p[-1]) != v.size:
+        raise ValueError('lis_sums: {} offsets, {} values, {} weights'.format(p.shape, v.shape, w.shape))
+    n = p.size - 1
+    sf, sr = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+    rc = load().hhx_lis_sums(n, ptr(p), ptr(v) if v.size else None, ptr(w) if w.size else None, ptr(sf), ptr(sr))
+    check_served(rc, LisUnsupported)
+    return sf[:n], sr[:n]
 
 
 class Gfa:

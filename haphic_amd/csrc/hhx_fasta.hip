@@ -528,38 +528,13 @@ extern "C" int hhx_fasta_fetch(hhx_fasta *f, int64_t off, int64_t len, uint8_t *
     return 0;
 }
 
-extern "C" int hhx_fasta_emit(hhx_fasta *f, const char *path, int64_t n_rec, const uint8_t *rec_names, const int64_t *rec_name_off, const int64_t *piece_off,
-                              const int32_t *piece_ctg, const uint8_t *piece_rev, int64_t Ns, int64_t max_width, int64_t *n_bytes) {
-    if (!f) return fail("hhx_fasta_emit: null handle");
-    if (!path || n_rec < 0 || (n_rec && (!rec_name_off || !piece_off))) return fail("hhx_fasta_emit: bad argument");
-    if (max_width < 1) return unsupported("hhx_fasta_emit: max_width %lld (the reference's range() raises or writes nothing)", (long long)max_width);
-    if (Ns < 0 || Ns > SPAN_MAX >> 20) return unsupported("hhx_fasta_emit: Ns %lld", (long long)Ns);
-    const i64 W = std::min<i64>(max_width, SPAN_MAX);
-    const i64 n_pieces = n_rec ? piece_off[n_rec] : 0;
-    if (n_rec && (rec_name_off[0] != 0 || piece_off[0] != 0 || (rec_name_off[n_rec] && !rec_names) || (n_pieces && (!piece_ctg || !piece_rev))))
-        return fail("hhx_fasta_emit: bad argument");
-    std::vector<i64> rec_off((size_t)n_rec + 1, 0), rec_slen((size_t)n_rec + 1, 0), rec_seg0((size_t)n_rec + 1, 0), seg_end, seg_src;
-    seg_end.push_back(0);                                        // entry -1 of the first record's search
-    for (i64 r = 0; r < n_rec; ++r) {
-        const i64 name_len = rec_name_off[r + 1] - rec_name_off[r], np = piece_off[r + 1] - piece_off[r];
-        if (name_len < 0 || np < 0) return fail("hhx_fasta_emit: offsets of record %lld run backwards", (long long)r);
-        i64 x = 0;
-        rec_seg0[(size_t)r] = (i64)seg_src.size();
-        for (i64 k = piece_off[r]; k < piece_off[r + 1]; ++k) {
-            const i64 c = piece_ctg[k];
-            if (c < 0 || c >= f->n_ctg) return fail("hhx_fasta_emit: piece %lld names contig %lld of %lld", (long long)k, (long long)c, (long long)f->n_ctg);
-            if (k > piece_off[r] && Ns > 0) { x += Ns; seg_end.push_back(x); seg_src.push_back(-1); }
-            x += f->h_seq_len[(size_t)c];
-            seg_end.push_back(x);
-            seg_src.push_back(f->h_seq_off[(size_t)c] | ((i64)(piece_rev[k] ? 1 : 0) << 62));
-            if (x > SPAN_MAX) return unsupported("hhx_fasta_emit: record %lld is longer than 2^60 bytes", (long long)r);
-        }
-        rec_slen[(size_t)r] = x;
-        rec_off[(size_t)r + 1] = rec_off[(size_t)r] + name_len + 2 + x + (x + W - 1) / W;
-        if (rec_off[(size_t)r + 1] > SPAN_MAX) return unsupported("hhx_fasta_emit: the file is longer than 2^60 bytes");
-    }
-    rec_seg0[(size_t)n_rec] = (i64)seg_src.size();
-    seg_src.push_back(-1);                                       // seg_src is read as seg_end + 1 is: one entry behind
+namespace {
+
+// the file of both emits from its tables: rec_off [n_rec + 1], rec_slen and rec_seg0 [n_rec + 1], seg_end with entry -1 in front, seg_src with one
+// entry behind (EmitTab); slab by slab, each written while the next is produced
+int emit_file(hhx_fasta *f, const char *path, i64 n_rec, const uint8_t *rec_names, const int64_t *rec_name_off, const std::vector<i64> &rec_off,
+              const std::vector<i64> &rec_slen, const std::vector<i64> &rec_seg0, const std::vector<i64> &seg_end, const std::vector<i64> &seg_src, i64 W,
+              int64_t *n_bytes) {
     const i64 total = rec_off[(size_t)n_rec];
     const i64 slab = std::min<i64>(slab_bytes(), std::max<i64>(16, (total + 15) & ~(i64)15));
 
@@ -604,6 +579,92 @@ extern "C" int hhx_fasta_emit(hhx_fasta *f, const char *path, int64_t n_rec, con
     if (rc || rc_close) { (void)::unlink(path); return rc ? rc : rc_close; }
     if (n_bytes) *n_bytes = total;
     return 0;
+}
+
+}  // namespace
+
+extern "C" int hhx_fasta_emit(hhx_fasta *f, const char *path, int64_t n_rec, const uint8_t *rec_names, const int64_t *rec_name_off, const int64_t *piece_off,
+                              const int32_t *piece_ctg, const uint8_t *piece_rev, int64_t Ns, int64_t max_width, int64_t *n_bytes) {
+    if (!f) return fail("hhx_fasta_emit: null handle");
+    if (!path || n_rec < 0 || (n_rec && (!rec_name_off || !piece_off))) return fail("hhx_fasta_emit: bad argument");
+    if (max_width < 1) return unsupported("hhx_fasta_emit: max_width %lld (the reference's range() raises or writes nothing)", (long long)max_width);
+    if (Ns < 0 || Ns > SPAN_MAX >> 20) return unsupported("hhx_fasta_emit: Ns %lld", (long long)Ns);
+    const i64 W = std::min<i64>(max_width, SPAN_MAX);
+    const i64 n_pieces = n_rec ? piece_off[n_rec] : 0;
+    if (n_rec && (rec_name_off[0] != 0 || piece_off[0] != 0 || (rec_name_off[n_rec] && !rec_names) || (n_pieces && (!piece_ctg || !piece_rev))))
+        return fail("hhx_fasta_emit: bad argument");
+    std::vector<i64> rec_off((size_t)n_rec + 1, 0), rec_slen((size_t)n_rec + 1, 0), rec_seg0((size_t)n_rec + 1, 0), seg_end, seg_src;
+    seg_end.push_back(0);                                        // entry -1 of the first record's search
+    for (i64 r = 0; r < n_rec; ++r) {
+        const i64 name_len = rec_name_off[r + 1] - rec_name_off[r], np = piece_off[r + 1] - piece_off[r];
+        if (name_len < 0 || np < 0) return fail("hhx_fasta_emit: offsets of record %lld run backwards", (long long)r);
+        i64 x = 0;
+        rec_seg0[(size_t)r] = (i64)seg_src.size();
+        for (i64 k = piece_off[r]; k < piece_off[r + 1]; ++k) {
+            const i64 c = piece_ctg[k];
+            if (c < 0 || c >= f->n_ctg) return fail("hhx_fasta_emit: piece %lld names contig %lld of %lld", (long long)k, (long long)c, (long long)f->n_ctg);
+            if (k > piece_off[r] && Ns > 0) { x += Ns; seg_end.push_back(x); seg_src.push_back(-1); }
+            x += f->h_seq_len[(size_t)c];
+            seg_end.push_back(x);
+            seg_src.push_back(f->h_seq_off[(size_t)c] | ((i64)(piece_rev[k] ? 1 : 0) << 62));
+            if (x > SPAN_MAX) return unsupported("hhx_fasta_emit: record %lld is longer than 2^60 bytes", (long long)r);
+        }
+        rec_slen[(size_t)r] = x;
+        rec_off[(size_t)r + 1] = rec_off[(size_t)r] + name_len + 2 + x + (x + W - 1) / W;
+        if (rec_off[(size_t)r + 1] > SPAN_MAX) return unsupported("hhx_fasta_emit: the file is longer than 2^60 bytes");
+    }
+    rec_seg0[(size_t)n_rec] = (i64)seg_src.size();
+    seg_src.push_back(-1);                                       // seg_src is read as seg_end + 1 is: one entry behind
+    return emit_file(f, path, n_rec, rec_names, rec_name_off, rec_off, rec_slen, rec_seg0, seg_end, seg_src, W, n_bytes);
+}
+
+// the FASTA half of order_and_orient_groups, scripts/HapHiC_refsort.py:269-342: the tables of k_fa_emit from sub-ranges and N runs, no joiner
+extern "C" int hhx_fasta_emit_segments(hhx_fasta *f, const char *path, int64_t n_rec, const uint8_t *rec_names, const int64_t *rec_name_off,
+                                       const int64_t *piece_off, const int32_t *piece_ctg, const int64_t *piece_start, const int64_t *piece_len,
+                                       const uint8_t *piece_rev, int64_t max_width, int64_t *n_bytes) {
+    if (!f) return fail("hhx_fasta_emit_segments: null handle");
+    if (!path || n_rec < 0 || (n_rec && (!rec_name_off || !piece_off))) return fail("hhx_fasta_emit_segments: bad argument");
+    if (max_width < 1) return unsupported("hhx_fasta_emit_segments: max_width %lld (the reference's range() raises or writes nothing)", (long long)max_width);
+    const i64 W = std::min<i64>(max_width, SPAN_MAX);
+    const i64 n_pieces = n_rec ? piece_off[n_rec] : 0;
+    if (n_rec && (rec_name_off[0] != 0 || piece_off[0] != 0 || (rec_name_off[n_rec] && !rec_names) ||
+                  (n_pieces && (!piece_ctg || !piece_start || !piece_len || !piece_rev))))
+        return fail("hhx_fasta_emit_segments: bad argument");
+    std::vector<i64> rec_off((size_t)n_rec + 1, 0), rec_slen((size_t)n_rec + 1, 0), rec_seg0((size_t)n_rec + 1, 0), seg_end, seg_src;
+    seg_end.push_back(0);                                        // entry -1 of the first record's search
+    for (i64 r = 0; r < n_rec; ++r) {
+        const i64 name_len = rec_name_off[r + 1] - rec_name_off[r], np = piece_off[r + 1] - piece_off[r];
+        if (name_len < 0 || np < 0) return fail("hhx_fasta_emit_segments: offsets of record %lld run backwards", (long long)r);
+        i64 x = 0;
+        rec_seg0[(size_t)r] = (i64)seg_src.size();
+        for (i64 k = piece_off[r]; k < piece_off[r + 1]; ++k) {
+            const i64 c = piece_ctg[k], m = piece_len[k];
+            if (m < 0) return unsupported("hhx_fasta_emit_segments: piece %lld has length %lld", (long long)k, (long long)m);
+            if (m > SPAN_MAX) return unsupported("hhx_fasta_emit_segments: record %lld is longer than 2^60 bytes", (long long)r);
+            i64 src = -1;
+            if (c >= 0) {
+                if (c >= f->n_ctg) return fail("hhx_fasta_emit_segments: piece %lld names contig %lld of %lld", (long long)k, (long long)c, (long long)f->n_ctg);
+                const i64 s = piece_start[k];
+                if (s < 0 || s > f->h_seq_len[(size_t)c] || m > f->h_seq_len[(size_t)c] - s)
+                    return unsupported("hhx_fasta_emit_segments: piece %lld, bytes [%lld, %lld + %lld), lies outside its contig of %lld bytes", (long long)k,
+                                       (long long)s, (long long)s, (long long)m, (long long)f->h_seq_len[(size_t)c]);
+                src = (f->h_seq_off[(size_t)c] + s) | ((i64)(piece_rev[k] ? 1 : 0) << 62);
+            } else if (c != -1) {
+                return fail("hhx_fasta_emit_segments: piece %lld names contig %lld (-1: a run of N)", (long long)k, (long long)c);
+            }
+            if (m == 0) continue;                                // contributes nothing: no segment
+            x += m;
+            if (x > SPAN_MAX) return unsupported("hhx_fasta_emit_segments: record %lld is longer than 2^60 bytes", (long long)r);
+            seg_end.push_back(x);
+            seg_src.push_back(src);
+        }
+        rec_slen[(size_t)r] = x;
+        rec_off[(size_t)r + 1] = rec_off[(size_t)r] + name_len + 2 + x + (x + W - 1) / W;
+        if (rec_off[(size_t)r + 1] > SPAN_MAX) return unsupported("hhx_fasta_emit_segments: the file is longer than 2^60 bytes");
+    }
+    rec_seg0[(size_t)n_rec] = (i64)seg_src.size();
+    seg_src.push_back(-1);                                       // seg_src is read as seg_end + 1 is: one entry behind
+    return emit_file(f, path, n_rec, rec_names, rec_name_off, rec_off, rec_slen, rec_seg0, seg_end, seg_src, W, n_bytes);
 }
 
 extern "C" int hhx_fasta_close(hhx_fasta *f) {

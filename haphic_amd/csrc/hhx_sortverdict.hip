@@ -167,3 +167,167 @@ extern "C" int hhx_sort_verdict_sums(int32_t n, const int32_t *value, const int6
     if (r1 == r0) return 0;
     return total < 1ull << 32 ? sv_run<u32>(n, n_pos, enc, len, r0, r1, sums, stats) : sv_run<u64>(n, n_pos, enc, len, r0, r1, sums, stats);
 }
+
+// ---------------------------------------------------------------- `haphic refsort`: both LIS sums of many sequences (HapHiC_refsort.py find_lis :175-214)
+// The same wave step as k_sv_rotations on a batch: one wavefront per (sequence, class), a job.  The forward class of a sequence is its elements with
+// value >= 0, the reverse class those with value <= 0 (:182-185); inside a class an element whose value stood earlier in the sequence is dropped
+// (:186-187) and the rest are ranked by ascending signed value, so "strictly increasing" is "rank below" and a job owns one tree of m + 1 cells, m its
+// kept elements.  Ranking and dropping repeats are done HERE, by the entry's host code (a sort of each class; the kernel sees ranks and weights only):
+// neither on the device nor by the caller.  The tree of a job lives in LDS up to the seam of hhx_sort_verdict_sums (the same knob
+// "sort_verdict_lds_n", the same 4-byte cells while every sequence's weights sum to less than 2^32 and 8-byte cells otherwise) and in a
+// per-workgroup slab of HBM scratch above it; the jobs of either form are taken grid-stride by one launch each.
+template <class V, bool LDS>
+static __global__ __launch_bounds__(SV_T) void k_lis_jobs(i32 n_jobs, const i32 *__restrict__ job, const i64 *__restrict__ jptr, const i32 *__restrict__ rank,
+                                                         const V *__restrict__ len, i64 slab_cells, V *scratch, i64 *__restrict__ sums) {
+    extern __shared__ __align__(8) unsigned char sv_lds[];
+    V *T = LDS ? (V *)sv_lds : scratch + (i64)blockIdx.x * slab_cells;
+    const int lane = threadIdx.x;
+    const u32 below = (1u << (lane & 31)) - 1u;
+    const bool low = lane < 32;
+    for (i32 jj = (i32)blockIdx.x; jj < n_jobs; jj += (i32)gridDim.x) {
+        const i32 j = job[jj];
+        const i64 a = jptr[j];
+        const i32 m = (i32)(jptr[j + 1] - a);
+        for (i32 k = lane; k <= m; k += SV_T) T[k] = 0;
+        if (LDS) __builtin_amdgcn_wave_barrier();
+        else __syncthreads();
+        V best = 0;
+        for (i32 k0 = 0; k0 < m; k0 += SV_T) {
+            const i32 idx = k0 + lane;
+            const i32 my_q = idx < m ? rank[a + idx] : 0;
+            const V my_w = idx < m ? len[a + idx] : (V)0;
+            const int cnt = min(SV_T, m - k0);
+            for (int t = 0; t < cnt; ++t) {
+                const u32 q = (u32)sv_lane(my_q, t);          // 0-based rank: the query is the prefix of q cells, the update cell q + 1
+                const V w = sv_lane(my_w, t);
+                const u32 un = q | below;
+                const bool ask = low && ((q >> (lane & 31)) & 1u);
+                const bool upd = low && (lane == 0 || !((q >> ((lane - 1) & 31)) & 1u)) && un < (u32)m;
+                V mx = ask ? T[q & ~below] : (V)0;
+                const V old = upd ? T[un + 1] : (V)0;
+                mx = sv_max32(mx);
+                const V dp = mx + w;
+                if (upd) T[un + 1] = sv_mx(old, dp);
+                best = sv_mx(best, dp);
+                if (LDS) __builtin_amdgcn_wave_barrier();
+                else __syncthreads();
+            }
+        }
+        if (lane == 0) sums[j] = (i64)best;
+    }
+}
+
+template <class V>
+static int lis_run(const std::vector<i64> &jptr, const std::vector<i32> &rank, const std::vector<i64> &w64, std::vector<i64> &sums) {
+    const i32 n_jobs = (i32)jptr.size() - 1;
+    const i64 cap = SV_LDS_BYTES / (i64)sizeof(V) - 1;
+    const i64 lds_n = std::max<i64>(0, std::min<i64>(tune_get("sort_verdict_lds_n", SV_LDS_DEFAULT_BYTES / (i64)sizeof(V) - 1), cap));
+    std::vector<i32> jobs[2];                                   // 0: LDS, 1: HBM
+    i64 m_max[2] = {0, 0};
+    for (i32 j = 0; j < n_jobs; ++j) {
+        const i64 m = jptr[(size_t)j + 1] - jptr[(size_t)j];
+        if (m == 0) continue;                                    // an empty class: 0 (:192-193)
+        const int form = m <= lds_n ? 0 : 1;
+        jobs[form].push_back(j);
+        m_max[form] = std::max(m_max[form], m);
+    }
+    if (jobs[0].empty() && jobs[1].empty()) return 0;
+    std::vector<V> hw(w64.size());
+    for (size_t i = 0; i < w64.size(); ++i) hw[i] = (V)w64[i];
+    DevBuf<i64> d_jptr, d_sums;
+    DevBuf<i32> d_rank, d_jobs[2];
+    DevBuf<V> d_w, scratch;
+    if (d_jptr.alloc(jptr.size()) || d_sums.alloc((size_t)n_jobs) || d_rank.alloc(rank.size()) || d_w.alloc(hw.size())) return 1;
+    HHX_HIP(hipMemcpyAsync(d_jptr.p, jptr.data(), jptr.size() * sizeof(i64), hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemcpyAsync(d_rank.p, rank.data(), rank.size() * sizeof(i32), hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemcpyAsync(d_w.p, hw.data(), hw.size() * sizeof(V), hipMemcpyHostToDevice, g_stream));
+    HHX_HIP(hipMemsetAsync(d_sums.p, 0, (size_t)n_jobs * sizeof(i64), g_stream));
+    for (int form = 0; form < 2; ++form) {
+        if (jobs[form].empty()) continue;
+        if (d_jobs[form].alloc(jobs[form].size())) return 1;
+        HHX_HIP(hipMemcpyAsync(d_jobs[form].p, jobs[form].data(), jobs[form].size() * sizeof(i32), hipMemcpyHostToDevice, g_stream));
+    }
+    if (!jobs[0].empty()) {
+        HHX_TRY((raise_dynamic_lds<k_lis_jobs<V, true>>(SV_LDS_BYTES)));
+        const i64 grid = std::min<i64>((i64)jobs[0].size(), (i64)1 << 20);
+        KTimer kt("lis_sums");
+        k_lis_jobs<V, true><<<(unsigned)grid, SV_T, ((size_t)m_max[0] + 1) * sizeof(V), g_stream>>>((i32)jobs[0].size(), d_jobs[0].p, d_jptr.p, d_rank.p,
+                                                                                                     d_w.p, 0, nullptr, d_sums.p);
+        HHX_LAUNCH_CHECK();
+    }
+    if (!jobs[1].empty()) {
+        const i64 cells = m_max[1] + 1, bytes = cells * (i64)sizeof(V);
+        const i64 grid = std::min<i64>((i64)jobs[1].size(), std::max<i64>(1, std::min<i64>(SV_SCRATCH_BYTES / bytes, SV_HBM_GRID)));
+        if (scratch.alloc((size_t)(grid * cells))) return 1;
+        KTimer kt("lis_sums");
+        k_lis_jobs<V, false><<<(unsigned)grid, SV_T, 0, g_stream>>>((i32)jobs[1].size(), d_jobs[1].p, d_jptr.p, d_rank.p, d_w.p, cells, scratch.p, d_sums.p);
+        HHX_LAUNCH_CHECK();
+    }
+    HHX_HIP(hipMemcpyAsync(sums.data(), d_sums.p, (size_t)n_jobs * sizeof(i64), hipMemcpyDeviceToHost, g_stream));
+    HHX_HIP(hipStreamSynchronize(g_stream));
+    return 0;
+}
+
+static int lis_unsupported(const char *fmt, ...) {
+    char buf[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return HHX_UNSUPPORTED;
+}
+
+extern "C" int hhx_lis_sums(int64_t n_seq, const int64_t *ptr, const int64_t *value, const int64_t *len, int64_t *sums_f, int64_t *sums_r) {
+    if (n_seq < 0 || (n_seq && (!ptr || !sums_f || !sums_r))) return fail("hhx_lis_sums: bad argument");
+    if (n_seq == 0) return 0;
+    if (n_seq >= (i64)1 << 30) return lis_unsupported("hhx_lis_sums: %lld sequences", (long long)n_seq);
+    if (ptr[0] != 0) return fail("hhx_lis_sums: ptr[0] = %lld", (long long)ptr[0]);
+    for (i64 s = 0; s < n_seq; ++s) {
+        if (ptr[s + 1] < ptr[s]) return fail("hhx_lis_sums: ptr runs backwards at sequence %lld", (long long)s);
+        if (ptr[s + 1] - ptr[s] > SV_MAX_N)
+            return lis_unsupported("hhx_lis_sums: sequence %lld has %lld elements, beyond the %d served", (long long)s, (long long)(ptr[s + 1] - ptr[s]), SV_MAX_N);
+    }
+    if (ptr[n_seq] && (!value || !len)) return fail("hhx_lis_sums: null value or len");
+    bool wide = false;
+    for (i64 s = 0; s < n_seq; ++s) {
+        u64 total = 0;
+        for (i64 i = ptr[s]; i < ptr[s + 1]; ++i) {
+            if (len[i] <= 0) return lis_unsupported("hhx_lis_sums: len[%lld] = %lld (a weight is positive)", (long long)i, (long long)len[i]);
+            if ((u64)len[i] >= 1ull << 62 || (total += (u64)len[i]) >= 1ull << 62)
+                return lis_unsupported("hhx_lis_sums: the weights of sequence %lld sum to 2^62 or more", (long long)s);
+        }
+        wide = wide || total >= 1ull << 32;
+    }
+    // job 2 s: the forward class of sequence s, job 2 s + 1: its reverse class; kept elements in sequence order with their rank
+    std::vector<i64> jptr(1, 0), w;
+    std::vector<i32> rank;
+    std::vector<std::pair<i64, i32>> order;                      // (value, position among the kept)
+    for (i64 s = 0; s < n_seq; ++s)
+        for (int cls = 0; cls < 2; ++cls) {
+            order.clear();
+            for (i64 i = ptr[s]; i < ptr[s + 1]; ++i)
+                if (cls == 0 ? value[i] >= 0 : value[i] <= 0) order.emplace_back(value[i], (i32)(i - ptr[s]));
+            std::sort(order.begin(), order.end());               // equal values: the earliest first, the others are the repeats
+            const size_t at = rank.size();
+            std::vector<std::pair<i32, i32>> kept;               // (position, rank)
+            i32 r = 0;
+            for (size_t k = 0; k < order.size(); ++k)
+                if (k == 0 || order[k].first != order[k - 1].first) kept.emplace_back(order[k].second, r++);
+            std::sort(kept.begin(), kept.end());
+            rank.resize(at + kept.size());
+            w.resize(at + kept.size());
+            for (size_t k = 0; k < kept.size(); ++k) {
+                rank[at + k] = kept[k].second;
+                w[at + k] = len[ptr[s] + kept[k].first];
+            }
+            jptr.push_back((i64)rank.size());
+        }
+    std::vector<i64> sums((size_t)(2 * n_seq), 0);
+    HHX_TRY(wide ? lis_run<u64>(jptr, rank, w, sums) : lis_run<u32>(jptr, rank, w, sums));
+    for (i64 s = 0; s < n_seq; ++s) {
+        sums_f[s] = sums[(size_t)(2 * s)];
+        sums_r[s] = sums[(size_t)(2 * s + 1)];
+    }
+    return 0;
+}

@@ -355,6 +355,52 @@ def patch_build(B, engine=None):
     return saved
 
 
+# `haphic refsort`: the three module globals run() :383-412 resolves at call time (haphic_amd/refsort.py)
+REFSORT_SEAMS = {
+    'parse_fasta': 'HapHiC_cluster.py:87-113',           # bound into HapHiC_refsort by `from HapHiC_cluster import parse_fasta` :16
+    'parse_paf': 'HapHiC_refsort.py:81-134',
+    'order_and_orient_groups': 'HapHiC_refsort.py:151-342',
+}
+
+
+def patch_refsort(F, engine=None, paf=True):
+    """F: the imported HapHiC_refsort module.  parse_fasta reads the FASTA file on the device and returns a containers.FastaTable (the mirror
+    patch_build binds); parse_paf reads the PAF file on the device and builds the reference's nested dict from the table with numpy;
+    order_and_orient_groups takes both find_lis sums of all groups from one library call, prints the AGP lines from host code and writes the FASTA
+    records by one library call on the path fout.name (haphic_amd/refsort.py, which lists what is handed back to the reference's own functions).
+    parse_agp, get_max_ovl_group, alignment_check and run() stay the reference's.  engine: a stand-in for the _lib module with Fasta, Paf,
+    lis_sums and LisUnsupported (the tests' numpy engine).  paf=False leaves parse_paf the reference's (the wrapper's default, which follows
+    profiles/refsort_bench.json); order_and_orient_groups flattens the reference's dict as it does the mirror's.  Returns {name: original}."""
+    from . import refsort, scaffolds
+    from .containers import FastaTable
+    if engine is None:
+        from . import _lib
+        _lib.load()
+    saved = {name: getattr(F, name) for name in REFSORT_SEAMS}
+    original_fasta, original_paf, original_order = saved['parse_fasta'], saved['parse_paf'], saved['order_and_orient_groups']
+    refsort.STATS.clear()
+
+    def parse_fasta(fasta, RE='GATC', keep_letter_case=False, logger=F.logger):
+        out = scaffolds.parse_fasta(fasta, RE, keep_letter_case, logger, _original=original_fasta, _engine=None if engine is None else engine.Fasta)
+        refsort.STATS['parse_fasta'] = 'device' if isinstance(out, FastaTable) else 'reference'
+        return out
+    parse_fasta.__wrapped__ = scaffolds.parse_fasta
+    F.parse_fasta = parse_fasta
+
+    def parse_paf(paf, ctg_group_dict, aln_len_cutoff):
+        return refsort.parse_paf(paf, ctg_group_dict, aln_len_cutoff, _original=original_paf, _engine=engine, _logger=F.logger)
+    parse_paf.__wrapped__ = refsort.parse_paf
+    if paf:
+        F.parse_paf = parse_paf
+
+    def order_and_orient_groups(ctg_group_dict, group_ref_dict, group_agp_lines, group_len_dict, one_ctg_groups, args, fa_dict=None, fout=None):
+        return refsort.order_and_orient_groups(ctg_group_dict, group_ref_dict, group_agp_lines, group_len_dict, one_ctg_groups, args, fa_dict, fout,
+                                               _original=original_order, _engine=engine, _logger=F.logger)
+    order_and_orient_groups.__wrapped__ = refsort.order_and_orient_groups
+    F.order_and_orient_groups = order_and_orient_groups
+    return saved
+
+
 def unpatch_reference(H, saved):
     cluster.DENSE_SEAM_BOUND = False
     for name, fn in saved.items():

@@ -996,6 +996,16 @@ int hhx_fasta_re_counts(hhx_fasta *f, int64_t n_seg, const int64_t *seg_off, con
 int hhx_fasta_fetch(hhx_fasta *f, int64_t off, int64_t len, uint8_t *out_host);
 int hhx_fasta_emit(hhx_fasta *f, const char *path, int64_t n_rec, const uint8_t *rec_names, const int64_t *rec_name_off, const int64_t *piece_off,
                    const int32_t *piece_ctg, const uint8_t *piece_rev, int64_t Ns, int64_t max_width, int64_t *n_bytes);
+/* hhx_fasta_emit_segments — the FASTA half of order_and_orient_groups, scripts/HapHiC_refsort.py:269-342, on an open handle: hhx_fasta_emit without a
+ *   joiner, whose pieces are sub-ranges and N runs.  Piece k with piece_ctg[k] >= 0 is bytes [piece_start[k], piece_start[k] + piece_len[k]) of
+ *   that contig (fa_dict[ctg][0][start - 1:end] :290, :305, :334), as they are or (piece_rev[k] != 0) reversed and mapped through ATCGNatcgn ->
+ *   TAGCNtagcn, every other byte unchanged (revcom :155-160); piece_ctg[k] == -1 is piece_len[k] bytes of 'N' :293 (start and rev are not read).
+ *   Header lines, lines of max_width bytes :319-320, no sequence line for an empty record, slabs of "fasta_slab" bytes each written while the next is
+ *   produced, *n_bytes, the file complete and closed on return and removed after a failure: as hhx_fasta_emit.  HHX_UNSUPPORTED before the file is
+ *   touched: a piece outside its contig, a negative length, max_width < 1, a record beyond 2^60 bytes.  Error: a contig id the table does not have. */
+int hhx_fasta_emit_segments(hhx_fasta *f, const char *path, int64_t n_rec, const uint8_t *rec_names, const int64_t *rec_name_off, const int64_t *piece_off,
+                            const int32_t *piece_ctg, const int64_t *piece_start, const int64_t *piece_len, const uint8_t *piece_rev, int64_t max_width,
+                            int64_t *n_bytes);
 int hhx_fasta_close(hhx_fasta *f);
 
 /* ---------------------------------------------------------------- the GFA reader of parse_gfa, scripts/HapHiC_cluster.py:150-185 (haphic_amd/csrc/hhx_gfa.hip)
@@ -1018,6 +1028,42 @@ int hhx_gfa_open_bytes(const uint8_t *text, int64_t n_bytes, hhx_gfa **out);
 int hhx_gfa_counts(const hhx_gfa *g, int64_t *n_rec, int64_t *n_name_bytes);
 int hhx_gfa_table(const hhx_gfa *g, int64_t *name_off, uint8_t *names, int64_t *len, int64_t *depth);
 int hhx_gfa_close(hhx_gfa *g);
+
+/* ---------------------------------------------------------------- `haphic refsort`: the PAF reader of parse_paf, scripts/HapHiC_refsort.py:81-134 (haphic_amd/csrc/hhx_paf.hip)
+ * hhx_paf_open / hhx_paf_open_bytes: a file (through the pinned read-ahead of hhx_text_reader_open_raw) or bytes in host memory go to HBM in one piece and
+ *   the table of its lines comes back; nothing stays on the device.  Lines are Python's text-mode lines ('\n', "\r\n" and a lone '\r' end a line); a
+ *   line that is blank under line.strip() is skipped :88; field k is line.split()[k] :90 (runs of the ASCII whitespace of str.split(), leading
+ *   whitespace ignored).  Per line, in file order: the ids of field 0 (the contig :93) and of field 5 (the reference sequence :93) in ONE name table
+ *   whose names stand in first-seen order (field 0 of a line before its field 5), the integers of fields 2, 3 :93, 7, 8 :107 and 11 :91, and
+ *   whether field 4 is exactly "+" :94.  An integer is served as 1 to 18 ASCII digits that are the whole field.
+ *   HHX_UNSUPPORTED (hhx_last_error() names the line and the reason; no handle is made): a line that is not blank with fewer than 12 fields (the
+ *   reference raises IndexError); any other spelling of an integer (signs, underscores, more digits: Python's int() decides) — of EVERY line, also
+ *   where the reference would not convert the field (:91 mapq 0, :101-105 contigs it skips): handing such a file back whole is still exact; a name
+ *   longer than 255 bytes; a byte >= 0x80 anywhere in the text; a text beyond half of the device's memory, or whose per-line tables (288 bytes a line) do not fit beside
+ *   it there; 2^30 lines or more; a path that is no
+ *   regular file.  No lane walks a line: only the first 12 fields are located, each by a binary search in the scanned field-start counts of the
+ *   4 KB blocks, so a cg:Z: tag of any length costs nothing.  The passes are grid-stride; the environment variable HHX_PAF_GRID (read at every
+ *   launch) caps their workgroups, so that tests walk the loops on one and two of them.
+ * hhx_paf_counts: lines, names, name bytes (any pointer may be null).  hhx_paf_table: name_off [n_names + 1], the names one after the other, query
+ *   and target [n_rec] (name ids), query_start, query_end, target_start, target_end, mapq [n_rec], plus [n_rec] (any pointer may be null). */
+typedef struct hhx_paf hhx_paf;
+int hhx_paf_open(const char *path, hhx_paf **out);
+int hhx_paf_open_bytes(const uint8_t *text, int64_t n_bytes, hhx_paf **out);
+int hhx_paf_counts(const hhx_paf *g, int64_t *n_rec, int64_t *n_names, int64_t *n_name_bytes);
+int hhx_paf_table(const hhx_paf *g, int64_t *name_off, uint8_t *names, int32_t *query, int32_t *target, int64_t *query_start, int64_t *query_end,
+                  int64_t *target_start, int64_t *target_end, int64_t *mapq, uint8_t *plus);
+int hhx_paf_close(hhx_paf *g);
+
+/* hhx_lis_sums — both find_lis sums (scripts/HapHiC_refsort.py:175-214, called twice per group :246-247) of n_seq sequences in one call
+ *   (csrc/hhx_sortverdict.hip, the wave step of hhx_sort_verdict_sums).  Sequence s is elements ptr[s] .. ptr[s + 1] (ptr[0] = 0); value[]: a signed
+ *   64-bit key (the caller passes 2 * order: orders are multiples of 0.5), len[]: the weight.  The forward class is the elements with value >= 0
+ *   :182-183, the reverse class those with value <= 0 :184-185; within a class an element whose value stood earlier in the sequence is dropped
+ *   :186-187; sums_f[s] / sums_r[s] = the largest total weight of a subsequence of the class with strictly increasing values :199-207, 0 for an empty
+ *   class :192-193 — exact int64.  The ranks and the dropping of repeats are computed by the entry's host code; one wavefront per (sequence, class);
+ *   the tree in LDS up to hhx_tune "sort_verdict_lds_n" kept elements and in HBM scratch above, 4-byte cells while every sequence's weights sum to
+ *   less than 2^32 and 8-byte cells otherwise.  HHX_UNSUPPORTED: a weight <= 0, the weights of one sequence summing to 2^62 or more, a sequence
+ *   beyond HHX_SORT_VERDICT_MAX_N elements. */
+int hhx_lis_sums(int64_t n_seq, const int64_t *ptr, const int64_t *value, const int64_t *len, int64_t *sums_f, int64_t *sums_r);
 
 #ifdef __cplusplus
 }
